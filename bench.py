@@ -8,8 +8,11 @@ rows are already resident in HBM (index E = U.R built once, outside the timed re
     ->  overlap counts for top_k in {1,10,50,100}  ->  reference-format recall statistics on the host.
 value = queries / second over all ranks (weak scaling: every rank evaluates its own Q queries).
 
-    python bench.py --gpus N --steps K --warmup W
-prints ONE JSON line on rank 0 (metric, value, roofline, cpu_baseline, ...).
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+prints ONE JSON line on rank 0 (metric, value, unit, ms_per_step, recall, ...).  A plain run sets up, warms up, times the K steps and
+prints the line; --full adds every side measurement (sustained rate, per-kernel roofline figures, retrieve-only, entry A's cell, the
+sweep ceiling, the IVF side-line, the CPU baseline, solo_rank0 and, at N > 1, the cfg4 sub-object).  --dump-outputs DIR writes what the
+last timed step computed (exact and retrieved top-k, overlap counts, recall) as DIR/<name>.npy; the inputs are seeded (--seed).
 
 N > 1: one process per GPU.  Under torchrun (RANK / WORLD_SIZE in the environment) this process is one of the ranks; started
 plainly with --gpus N > 1 it launches the N ranks itself (torch.distributed.run, before any GPU call) and relays their result.
@@ -188,6 +191,25 @@ CONFIGS = {
 }
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0
+SETTLE_S = 2.0             # a plain run's clock-settling loop before the warm-up (the sustained loop's length with --full)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, step, counts, recall):
+	"""--dump-outputs: what the last timed step computed, one DIR/<name>.npy each -- the exact top-k of A_test and the retrieved top-k_retvr
+	(scores float32, item ids float64), the overlap counts [len(top_k) x Q] of the two and the recall@top_k means (float64)."""
+	arrays = {"exact_topk_values": step["exact"].values.float().cpu().numpy(),
+			  "exact_topk_indices": step["exact"].indices.cpu().numpy().astype(np.float64),
+			  "retrieved_topk_values": step["approx"].values.float().cpu().numpy(),
+			  "retrieved_topk_indices": step["approx"].indices.cpu().numpy().astype(np.float64),
+			  "overlap_counts": np.asarray(counts, dtype=np.float64),
+			  "recall": np.asarray(recall, dtype=np.float64)}
+	total = sum(a.nbytes for a in arrays.values())
+	if total > DUMP_LIMIT_BYTES:
+		raise SystemExit(f"[bench] --dump-outputs: {total} bytes of outputs, more than {DUMP_LIMIT_BYTES}")
+	os.makedirs(out_dir, exist_ok=True)
+	for name, a in arrays.items():
+		np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def synth_device(cfg, device, seed, row_seed=None):
@@ -354,12 +376,16 @@ def run_config(args, cfg_name, ctx, light=False):
 	def build_index():
 		return CURApprox(rows=A_train, cols=ops.gather_cols(A_train, anc_dev), row_idxs=np.arange(cfg["Kq"]), col_idxs=anc,
 						 approx_preference="rows", compute_dtype="bf16")
-	build_index()   # first call: code objects, allocator
-	torch.cuda.synchronize()
-	t0 = time.perf_counter()
-	cur = build_index()
-	torch.cuda.synchronize()
-	index_build_s = time.perf_counter() - t0
+	index_build_s = None
+	if args.full:
+		build_index()   # first call: code objects, allocator
+		torch.cuda.synchronize()
+		t0 = time.perf_counter()
+		cur = build_index()
+		torch.cuda.synchronize()
+		index_build_s = time.perf_counter() - t0
+	else:
+		cur = build_index()
 	_mark("index built")
 	Kp = cur._Etp.shape[1]
 	Q, I, k, kr = cfg["Q"], cfg["I"], cfg["k"], cfg["k_retvr"]
@@ -394,6 +420,8 @@ def run_config(args, cfg_name, ctx, light=False):
 	# three runs each: 96 CUs 0.904-0.908 ms, 128 0.880-0.883, 160 0.908-0.915 (the scan before the change at 160: 0.891-0.893).
 	scan_cus = args.scan_cus if args.scan_cus else (128 if Kp <= 256 else 64)
 	rounds_rows = int(os.environ.get("ANNCUR_BENCH_ROUND_ROWS", "4096"))
+	# the exact and retrieved top-k of the last step launched on each result slot (a graph replay rewrites the same tensors): --dump-outputs
+	kept = [{} for _ in range(2)]
 
 	def retrieve(workspace=None):
 		Xq = ops.gather_cols(A_test, anc_dev)                          # a2: C_q
@@ -410,7 +438,7 @@ def run_config(args, cfg_name, ctx, light=False):
 		  tail / chunks / serial   earlier schedules, kept for A/B."""
 		side = ops.aux_stream(device) if mode in ("side", "tail") else None
 
-		def gpu_step_tail():
+		def gpu_step_tail(slot):
 			# The exact scan runs one wave per row and keeps `rounds_rows` rows in flight; a launch costs whole rounds: a FULL round is
 			# bandwidth-bound (4096 rows of 200 KB: 145 us = 5.7 TB/s), a partial one is latency-bound (92 us however few rows).  So: the
 			# full rounds first, alone on the chip; the partial round on the second stream beside the retrieval's latency-bound head
@@ -426,11 +454,12 @@ def run_config(args, cfg_name, ctx, light=False):
 					ops.rowwise_topk(A_test[full:], k, out=(ev[full:], ei[full:]))
 			approx = retrieve()
 			main.wait_stream(side)
+			kept[slot].update(exact=ops.TopK(ev, ei), approx=approx)
 			return ops.overlap_counts(ei, approx.indices, cells)
 
-		def gpu_step():
+		def gpu_step(slot):
 			if mode == "tail":
-				return gpu_step_tail()
+				return gpu_step_tail(slot)
 			main = torch.cuda.current_stream()
 			if mode == "side":
 				# the exact scan (HBM-bound, a8) is independent of the retrieval until the overlap count: it starts on a second stream with the
@@ -447,6 +476,7 @@ def run_config(args, cfg_name, ctx, light=False):
 				if Xq.shape[1] != Kp:
 					Xq = ops.pack_bf16(Xq, Kp)
 				exact, approx = ops.eval_topk(A_test, k, Xq, cur._Etp_sorted, I, kr, leading_sample=True, item_ids=cur._item_ids, staged=args.sweep_staged, serial=mode == "serial")
+			kept[slot].update(exact=exact, approx=approx)
 			return ops.overlap_counts(exact.indices, approx.indices, cells)   # a8 rerank (closed form) + a10
 
 		if mode == "partition":
@@ -467,7 +497,7 @@ def run_config(args, cfg_name, ctx, light=False):
 			wss = [ops.fused_workspace(Q, I, Kp, kr, device) for _ in range(2)] if n_rs == 2 else [None, None]
 			for m in mains: m.wait_stream(torch.cuda.current_stream())
 			s_st.wait_stream(torch.cuda.current_stream())
-			state = [{} for _ in range(2)]
+			state = kept
 			tail_done = [torch.cuda.Event() for _ in range(2)]
 			# --fold-gather: C_q = A[:, anchors] out of the scan's own pass over A (anncur_rowwise_topk_gather: a2 folded into a8's first pass)
 			# instead of the separate gather, which re-reads one 64-byte sector per anchor and query (164 MB at cfg2, 0.065 ms).  The
@@ -545,14 +575,14 @@ def run_config(args, cfg_name, ctx, light=False):
 		# graph replay, with no copy-engine hop whose cross-queue dependency a busy host would have to resolve.
 		graphs = None
 		if not args.no_graph:
-			ops.copy_to_mapped_host(gpu_step(), pinned[0]); torch.cuda.synchronize()   # workspace / code objects loaded outside capture
+			ops.copy_to_mapped_host(gpu_step(0), pinned[0]); torch.cuda.synchronize()   # workspace / code objects loaded outside capture
 			try:
 				graphs = []
 				for slot in range(2):
 					g = torch.cuda.CUDAGraph()
 					# thread_local: other threads of the process (the RCCL watchdog of a multi-rank run) may touch the runtime meanwhile
 					with torch.cuda.graph(g, capture_error_mode="thread_local"):
-						ops.copy_to_mapped_host(gpu_step(), pinned[slot])
+						ops.copy_to_mapped_host(gpu_step(slot), pinned[slot])
 					graphs.append(g)
 			except Exception as exc:  # never lose the measurement to a capture problem: fall back to eager launches
 				print(f"[bench] HIP graph capture failed ({type(exc).__name__}: {exc}); launching eagerly", file=sys.stderr)
@@ -563,7 +593,7 @@ def run_config(args, cfg_name, ctx, light=False):
 			if graphs is not None:
 				graphs[slot].replay()
 			else:
-				ops.copy_to_mapped_host(gpu_step(), pinned[slot])
+				ops.copy_to_mapped_host(gpu_step(slot), pinned[slot])
 			events[slot].record()
 			return slot
 		return launch_one, graphs is not None
@@ -628,8 +658,11 @@ def run_config(args, cfg_name, ctx, light=False):
 	# the timed burst then starts on a chip that is out of its idle power state -- measured on one box, K = 20 steps after W = 5: 0.995 ms per step
 	# straight after the (host-heavy, GPU-idle) graph capture, 0.919 after 200 warm-up steps, 0.918 after 1000, 0.904 for K = 200: the first tens
 	# of milliseconds after idle run ~8 % slow, which is the box's clock ramp, not the step.  (--sustained-seconds 0: no such loop, the old order.)
+	# A plain run (no --full) keeps the loop only for that second reason: at most SETTLE_S seconds, and no "sustained" figure on the line.
 	sustained = None
 	sus_target = args.sustained_seconds if not light else min(args.sustained_seconds, 1.5)   # (the cfg4 sub-object of a multi-rank run: a short loop, same purpose, same field)
+	if not args.full:
+		sus_target = min(sus_target, SETTLE_S)
 	if sus_target > 0:
 		barrier()
 		t0 = time.perf_counter(); n_sus = 0
@@ -639,14 +672,15 @@ def run_config(args, cfg_name, ctx, light=False):
 			if time.perf_counter() - t0 >= sus_target:
 				break
 		sus_s = time.perf_counter() - t0
-		if use_dist:
-			t = torch.tensor([sus_s / n_sus], device=device if args.backend == "nccl" else "cpu", dtype=torch.float64)
-			torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-			sus_step = t.item()
-		else:
-			sus_step = sus_s / n_sus
-		sustained = {"value": world * Q / sus_step, "unit": "queries/s", "ms_per_step": 1e3 * sus_step, "seconds": sus_s, "steps": n_sus,
-					 "order": "runs BEFORE the W warm-up and K timed steps: the timed burst starts at the chip's settled clock, not in its ramp out of idle"}
+		if args.full:
+			if use_dist:
+				t = torch.tensor([sus_s / n_sus], device=device if args.backend == "nccl" else "cpu", dtype=torch.float64)
+				torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+				sus_step = t.item()
+			else:
+				sus_step = sus_s / n_sus
+			sustained = {"value": world * Q / sus_step, "unit": "queries/s", "ms_per_step": 1e3 * sus_step, "seconds": sus_s, "steps": n_sus,
+						 "order": "runs BEFORE the W warm-up and K timed steps: the timed burst starts at the chip's settled clock, not in its ramp out of idle"}
 	_mark("sustained section done")
 	res = run_steps(args.warmup)
 	barrier()
@@ -671,6 +705,10 @@ def run_config(args, cfg_name, ctx, light=False):
 		_mark("max-over-ranks of the step time done")
 	ms_per_step = 1e3 * elapsed / args.steps
 	value = world * Q * args.steps / elapsed
+	if args.dump_outputs and rank == 0 and not light:
+		last = (step_no[0] - 1) & 1   # the slot of the last timed step: nothing has been launched since
+		dump_outputs(args.dump_outputs, kept[last], pinned[last].numpy(), [res[t]["exact_vs_reranked_approx_retvr~common_frac_mean"] for t in top_k_vals])
+		_mark("outputs dumped")
 	if os.environ.get("ANNCUR_BENCH_NULL_PROBE"):
 		# the repro without RCCL: the NULL-stream work of one device-side reduction (8-byte H2D, D2H, a fill) between two batches of steps
 		with torch.cuda.stream(torch.cuda.default_stream(device)):
@@ -680,6 +718,30 @@ def run_config(args, cfg_name, ctx, light=False):
 		_mark("null-stream probe: copies done")
 		run_steps(args.steps); torch.cuda.synchronize()
 		_mark("null-stream probe: steps done")
+
+	out = None
+	if rank == 0:
+		recall = {f"recall@{t}": res[t]["exact_vs_reranked_approx_retvr~common_frac_mean"] for t in top_k_vals}
+		out = {
+			"metric": "queries/sec + Top-k-Recall@100 vs exact, CUR-256 on QxI score matrix",
+			"value": value, "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+			"ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+			"dtype": "bf16", "data": "synthetic",
+			"config": {"workload": f"{cfg_name}: Q={Q}/GPU x I={I} bf16 score matrix, {cfg['Ki']} anchor items, {cfg['Kq']} anchor queries, "
+								   f"k={k}, k_retvr={kr}; step = gather C_q + fused S_hat/top-k + exact top-k scan + overlap/recall",
+					   "Q_per_gpu": Q, "I": I, "anchors": cfg["Ki"], "anchor_queries": cfg["Kq"], "k": k, "k_retvr": kr,
+					   "parallelism": f"row-sharded x{world}, index replicated (one RCCL all-gather of anchor rows at build time)"},
+			"recall": recall,
+			"fused_plan": ops.fused_plan(Q, I, Kp, kr, leading_sample=True, staged=args.sweep_staged),
+			"launch_mode": "eager" if not graphed else "hipGraph replay (the step's launches captured once per result slot)",
+			"scan_mode": {"used": scan_mode_used, "requested": "partition" if os.environ.get("ANNCUR_BENCH_FALLBACK_REASON") else (args.scan_mode or "partition"),
+						  "fallback_reason": os.environ.get("ANNCUR_BENCH_FALLBACK_REASON"),   # set by the supervisor when a partition attempt died of a GPU fault and fresh workers re-ran with "side"
+						  "scan_cus": scan_cus if scan_mode_used == "partition" else None,
+						  "retrieval_streams": args.retr_streams if scan_mode_used == "partition" else 1, "gather_folded_into_scan": bool(scan_mode_used == "partition" and args.fold_gather and ops.rowwise_topk_gather_ok(A_test, k) and Kp == len(anc))},
+			"ranks_seen": ranks_seen, "allgather_ms": allgather_ms, "backend": (args.backend if use_dist else None), "full": args.full,
+		}
+	if not args.full:
+		return out
 
 	# the same K steps on rank 0 ALONE (the other ranks wait): the single-GPU rate of this very workload inside the same job, so that
 	# weak-scaling efficiency = value / (N x solo) can be read off one line
@@ -840,19 +902,8 @@ def run_config(args, cfg_name, ctx, light=False):
 		except Exception:
 			pass
 
-	out = None
 	if rank == 0:
-		recall = {f"recall@{t}": res[t]["exact_vs_reranked_approx_retvr~common_frac_mean"] for t in top_k_vals}
-		out = {
-			"metric": "queries/sec + Top-k-Recall@100 vs exact, CUR-256 on QxI score matrix",
-			"value": value, "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-			"ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-			"dtype": "bf16", "data": "synthetic",
-			"config": {"workload": f"{cfg_name}: Q={Q}/GPU x I={I} bf16 score matrix, {cfg['Ki']} anchor items, {cfg['Kq']} anchor queries, "
-								   f"k={k}, k_retvr={kr}; step = gather C_q + fused S_hat/top-k + exact top-k scan + overlap/recall",
-					   "Q_per_gpu": Q, "I": I, "anchors": cfg["Ki"], "anchor_queries": cfg["Kq"], "k": k, "k_retvr": kr,
-					   "parallelism": f"row-sharded x{world}, index replicated (one RCCL all-gather of anchor rows at build time)"},
-			"recall": recall,
+		out.update({
 			"roofline": {"bound": "mfma", "kernel": "sweep stages (fused S_hat GEMM + threshold filter): " + " + ".join(
 							 ({2: f"score16_kernel<{Kp}>", 3: f"scoreq1_kernel<{Kp}>", 4: f"scoreq16_kernel<{Kp}>", 5: f"score16r_kernel<{Kp}>"}.get(b, f"score_kernel<{Kp},sweep>")) for b in plan_now["stage_pred"]),
 						 "achieved": sweep_tflops, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": sweep_tflops / PEAK_BF16_TFLOPS,
@@ -883,15 +934,9 @@ def run_config(args, cfg_name, ctx, light=False):
 			"index_build_s": index_build_s, "index_build_numpy_pinv_s": index_build_numpy_s,
 			"index_build_what": "gather anchor columns + U = pinv(W) + E = U.R + bf16 packs; pinv 'auto' = fp64 Newton-Schulz on the GPU (host LAPACK only for ill-conditioned blocks); numpy = the reference's host call",
 			"value_with_index_build": world * Q / (ms_per_step * 1e-3 + index_build_s),
-			"fused_plan": plan_now,
-			"launch_mode": "eager" if not graphed else "hipGraph replay (the step's launches captured once per result slot)",
-			"scan_mode": {"used": scan_mode_used, "requested": "partition" if os.environ.get("ANNCUR_BENCH_FALLBACK_REASON") else (args.scan_mode or "partition"),
-						  "fallback_reason": os.environ.get("ANNCUR_BENCH_FALLBACK_REASON"),   # set by the supervisor when a partition attempt died of a GPU fault and fresh workers re-ran with "side"
-						  "scan_cus": scan_cus if scan_mode_used == "partition" else None,
-						  "retrieval_streams": args.retr_streams if scan_mode_used == "partition" else 1, "gather_folded_into_scan": bool(scan_mode_used == "partition" and args.fold_gather and ops.rowwise_topk_gather_ok(A_test, k) and Kp == len(anc))},
-			"sustained": sustained, "ranks_seen": ranks_seen, "allgather_ms": allgather_ms, "backend": (args.backend if use_dist else None),
+			"sustained": sustained,
 			"solo_rank0": ({"value": solo, "unit": "queries/s", "what": "the same K steps on rank 0 alone, other ranks idle: N x this is the ideal weak-scaling value"} if solo else None),
-		}
+		})
 
 	# ------------------------------------------------------------------ side-line: the IVF-flat branch at the hard-negative-mining size
 	if rank == 0 and world == 1 and not args.no_ivf and not light:
@@ -989,7 +1034,8 @@ def main():
 	ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: rehearsal of the multi-rank path with ranks sharing GPUs")
 	ap.add_argument("--share-gpu", action="store_true", help="rehearsal: rank r uses GPU r %% device_count (RCCL cannot; use --backend gloo)")
 	ap.add_argument("--no-k500", action="store_true", help="skip the retrieve_only_k500 side-line (profiling runs: its launches share the sweep kernel's name)")
-	ap.add_argument("--sustained-seconds", type=float, default=10.0, help="also loop the same step for this long and report it (DVFS-settled rate); 0 = skip")
+	ap.add_argument("--sustained-seconds", type=float, default=10.0, help="--full: also loop the same step for this long and report it (DVFS-settled rate); without --full the loop only settles the clock "
+					"for at most 2 s and is not reported; 0 = skip")
 	ap.add_argument("--cpu-sample-queries", type=int, default=4096, help="queries timed through the CPU oracle (0 = skip)")
 	ap.add_argument("--cpu-threads", type=int, default=8, help="torch CPU threads for the baseline (the per-query loop gets SLOWER with more)")
 	ap.add_argument("--no-ivf", action="store_true", help="skip the ivf_search side-line (the IVF-flat branch of build_flat_or_ivff_index at the hard-negative-mining size)")
@@ -1008,7 +1054,14 @@ def main():
 	ap.add_argument("--sweep-staged", action="store_true", help="A/B: the retrieval's sweep in stages with a refinement launch between them (ANNCUR_TOPK_STAGED, rounds 1-4) instead of one launch with the in-flight threshold ladder")
 	ap.add_argument("--no-ceiling", action="store_true", help="skip roofline.ceiling (the sweep on survivor-free operands); profiling runs: its launches share the sweep kernel's name")
 	ap.add_argument("--direct", action="store_true", help="measure in THIS process (no supervisor / worker split, no fallback attempt): what profiling scripts put behind `rocprofv3 --`")
+	ap.add_argument("--full", action="store_true", help="also run every side measurement: the --sustained-seconds loop, per-kernel roofline figures, retrieve-only, "
+					"entry A's cell, the sweep ceiling, the IVF side-line, the CPU baseline, solo_rank0 and (N > 1, no --config) the cfg4 sub-object; "
+					"without it a run sets up, warms up, times the K steps and prints the headline line")
+	ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (exact and retrieved top-k, "
+					"overlap counts, recall) as DIR/<name>.npy in float32 / float64 (rank 0's queries)")
 	args = ap.parse_args()
+	if args.steps < 1 or args.warmup < 0:
+		ap.error("--steps must be >= 1 and --warmup >= 0")
 	world = int(os.environ.get("WORLD_SIZE", "1"))
 	if args.gpus is None:
 		args.gpus = world if os.environ.get("RANK") is not None else 1
@@ -1072,7 +1125,7 @@ def main():
 
 def _run_all(args, ctx, world, rank):
 	out = run_config(args, args.config or "cfg2", ctx)
-	if world > 1 and args.config is None:
+	if world > 1 and args.config is None and args.full:
 		import gc
 		gc.collect(); torch.cuda.empty_cache()
 		sub = run_config(args, "cfg4_per_gpu", ctx, light=True)

@@ -2,8 +2,8 @@
 # round-4 artefacts, part A: the bench lines (N = 1 cfg2, cfg4 per-GPU shape, 2-rank rehearsal on one GPU) + rocprofv3 passes of cfg2
 O=gpurun_out/r04; mkdir -p $O
 export TMPDIR=/tmp
-echo "== bench cfg2"; timeout -k 10 400 python3 bench.py > $O/bench_cfg2_n1.json 2> $O/bench_cfg2.err; echo rc=$?
-echo "== bench cfg4 per gpu"; timeout -k 10 300 python3 bench.py --config cfg4_per_gpu --no-ivf > $O/bench_cfg4_per_gpu_n1.json 2> $O/bench_cfg4.err; echo rc=$?
+echo "== bench cfg2"; timeout -k 10 400 python3 bench.py --full > $O/bench_cfg2_n1.json 2> $O/bench_cfg2.err; echo rc=$?
+echo "== bench cfg4 per gpu"; timeout -k 10 300 python3 bench.py --full --config cfg4_per_gpu --no-ivf > $O/bench_cfg4_per_gpu_n1.json 2> $O/bench_cfg4.err; echo rc=$?
 echo "== profile cfg2"; timeout -k 10 500 bash scripts/profile_round.sh r04_cfg2 cfg2 > $O/profile_cfg2.log 2>&1; echo rc=$?
 tail -3 $O/profile_cfg2.log
 python3 - <<'P'

@@ -8,7 +8,7 @@ mkdir -p $out
 for r in $(seq 1 $rounds); do
   for v in staged ladder; do
     flag=""; [ $v = staged ] && flag="--sweep-staged"
-    python3 bench.py --direct --steps 30 --warmup 5 --no-ivf --cpu-sample-queries 0 --no-k500 --sustained-seconds 4 $flag "$@" > $out/${v}_$r.json 2> $out/${v}_$r.err || { echo "$v $r FAILED"; tail -5 $out/${v}_$r.err; exit 1; }
+    python3 bench.py --full --direct --steps 30 --warmup 5 --no-ivf --cpu-sample-queries 0 --no-k500 --sustained-seconds 4 $flag "$@" > $out/${v}_$r.json 2> $out/${v}_$r.err || { echo "$v $r FAILED"; tail -5 $out/${v}_$r.err; exit 1; }
     python3 - $out/${v}_$r.json $v $r <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

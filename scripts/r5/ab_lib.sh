@@ -19,7 +19,7 @@ for rep in 1 2 3; do
     for v in old new; do
       lib=anncur_amd/lib/libanncur_hip.so; [ $v = old ] && lib=$old
       flag=""; [ "$cus" != default ] && flag="--scan-cus $cus"
-      ANNCUR_LIB=$lib timeout -k 10 600 python3 bench.py --direct --steps 30 --warmup 5 --no-ivf --cpu-sample-queries 0 --no-k500 --no-ceiling --sustained-seconds 4 $flag 2>/dev/null | python3 -c "
+      ANNCUR_LIB=$lib timeout -k 10 600 python3 bench.py --full --direct --steps 30 --warmup 5 --no-ivf --cpu-sample-queries 0 --no-k500 --no-ceiling --sustained-seconds 4 $flag 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('$v', 'scan_cus', d['scan_mode']['scan_cus'], 'ms_per_step', round(d['ms_per_step'], 4), 'sustained', round(d['sustained']['ms_per_step'], 4), 'scan ms', round(d['stage_ms'].get('exact_scan'), 4))"

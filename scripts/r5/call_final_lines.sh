@@ -2,9 +2,9 @@
 set -e
 export TMPDIR=/tmp
 out=gpurun_out/r5_final; mkdir -p $out
-timeout -k 10 900 python3 bench.py > $out/bench_cfg2_n1.json 2> $out/bench_cfg2_n1.err
-timeout -k 10 900 python3 bench.py --config cfg4_per_gpu --no-ivf > $out/bench_cfg4_per_gpu_n1.json 2> $out/bench_cfg4.err
-timeout -k 10 900 python3 bench.py --gpus 2 --backend gloo --share-gpu --steps 10 --warmup 3 > $out/bench_default_2ranks_gloo_one_gpu_rehearsal.json 2> $out/bench_2ranks.err
+timeout -k 10 900 python3 bench.py --full > $out/bench_cfg2_n1.json 2> $out/bench_cfg2_n1.err
+timeout -k 10 900 python3 bench.py --full --config cfg4_per_gpu --no-ivf > $out/bench_cfg4_per_gpu_n1.json 2> $out/bench_cfg4.err
+timeout -k 10 900 python3 bench.py --full --gpus 2 --backend gloo --share-gpu --steps 10 --warmup 3 > $out/bench_default_2ranks_gloo_one_gpu_rehearsal.json 2> $out/bench_2ranks.err
 python3 - <<'P'
 import json
 for f in ("bench_cfg2_n1", "bench_cfg4_per_gpu_n1", "bench_default_2ranks_gloo_one_gpu_rehearsal"):

@@ -10,12 +10,12 @@ for v in ceiling normal; do
   find $out/$v -type f ! -name "*kernel_stats.csv" -delete
 done
 for cus in 64 96 128; do
-  python3 bench.py --direct --steps 30 --warmup 5 --no-ivf --cpu-sample-queries 0 --no-k500 --no-ceiling --sustained-seconds 3 --scan-cus $cus 2>/dev/null | python3 -c "
+  python3 bench.py --full --direct --steps 30 --warmup 5 --no-ivf --cpu-sample-queries 0 --no-k500 --no-ceiling --sustained-seconds 3 --scan-cus $cus 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('scan_cus', d['scan_mode']['scan_cus'], 'ms_per_step', round(d['ms_per_step'], 4), 'sustained', round(d['sustained']['ms_per_step'], 4))"
 done
-python3 bench.py --direct --steps 30 --warmup 5 --no-ivf --cpu-sample-queries 0 --no-k500 --no-ceiling --sustained-seconds 3 --scan-mode side 2>/dev/null | python3 -c "
+python3 bench.py --full --direct --steps 30 --warmup 5 --no-ivf --cpu-sample-queries 0 --no-k500 --no-ceiling --sustained-seconds 3 --scan-mode side 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('side', 'ms_per_step', round(d['ms_per_step'], 4), 'sustained', round(d['sustained']['ms_per_step'], 4))"

@@ -6,13 +6,14 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--gpus", "2", "--backend", "gloo", "--share-gpu", "--config", "small", "--steps", "3", "--warmup", "1", "--sustained-seconds", "0",
-		"--cpu-sample-queries", "0", "--no-k500"]
+		"--cpu-sample-queries", "0", "--no-k500", "--full"]
 
 
 def _run(extra_env=None, args=ARGS, timeout=600):
@@ -46,7 +47,7 @@ _N1_DEFAULT = {}
 def _n1_default_line(mode=None):
 	"""The N = 1 line with the driver's default config (cached: two tests read it)."""
 	if mode not in _N1_DEFAULT:
-		short = ["--steps", "3", "--warmup", "1", "--sustained-seconds", "0", "--cpu-sample-queries", "0", "--no-k500", "--no-ivf"]
+		short = ["--steps", "3", "--warmup", "1", "--sustained-seconds", "0", "--cpu-sample-queries", "0", "--no-k500", "--no-ivf", "--full"]
 		p = _run(args=short + (["--scan-mode", mode] if mode else []))
 		assert p.returncode == 0, p.stderr[-3000:]
 		assert "Memory access fault" not in p.stderr
@@ -57,11 +58,11 @@ def _n1_default_line(mode=None):
 
 
 def test_bench_default_config_is_one_workload_at_every_n():
-	"""What the driver runs: plain `bench.py --gpus N` for N = 1, 2, 4, 8.  The top-level value / config must name the SAME workload at
-	every N (the headline cfg2 shape per rank), so that value(N) / value(1) is a scaling curve; BASELINE cfg4's per-GPU shape rides along
-	at N > 1 as the "cfg4" sub-object with its own value, roofline, allgather_ms and solo_rank0."""
+	"""What the driver runs: `bench.py --gpus N` for N = 1, 2, 4, 8.  The top-level value / config must name the SAME workload at
+	every N (the headline cfg2 shape per rank), so that value(N) / value(1) is a scaling curve; with --full, BASELINE cfg4's per-GPU shape
+	rides along at N > 1 as the "cfg4" sub-object with its own value, roofline, allgather_ms and solo_rank0."""
 	one = _n1_default_line()
-	p = _run(args=["--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "2", "--warmup", "1", "--sustained-seconds", "0", "--no-k500", "--no-ivf"], timeout=1200)
+	p = _run(args=["--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "2", "--warmup", "1", "--sustained-seconds", "0", "--no-k500", "--no-ivf", "--full"], timeout=1200)
 	assert p.returncode == 0, p.stderr[-3000:]
 	lines = [l for l in p.stdout.splitlines() if l.strip()]
 	assert len(lines) == 1, p.stdout[-2000:]
@@ -93,7 +94,7 @@ def test_bench_rccl_code_path_with_one_rank():
 	env = {"RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "ANNCUR_BENCH_FORCE_DIST": "1",
 		   "HSA_ENABLE_IPC_MODE_LEGACY": "0"}
 	p = _run(env, args=["--gpus", "1", "--backend", "nccl", "--config", "small", "--steps", "3", "--warmup", "1", "--sustained-seconds", "0", "--cpu-sample-queries", "0",
-						"--no-k500", "--no-ivf"])
+						"--no-k500", "--no-ivf", "--full"])
 	assert p.returncode == 0, p.stderr[-3000:]
 	lines = [l for l in p.stdout.splitlines() if l.strip()]
 	assert len(lines) == 1, p.stdout[-2000:]
@@ -126,6 +127,36 @@ def test_bench_single_gpu_default_line_and_scan_placements():
 	assert d["roofline"]["bound"] == "mfma" and 0.2 < d["roofline"]["frac"] < 1.0 and d["roofline_scan"]["bound"] == "hbm"
 	assert all(b == 2 for b in d["fused_plan"]["stage_pred"])          # the 16x16x32 body
 	assert d["recall"] == outs["side"]["recall"] and d["recall"]["recall@1"] == 1.0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+	"""A plain run (no --full) prints the headline line without the side measurements, and --dump-outputs writes what its last timed step
+	computed: the overlap counts and the line's recall follow from the dumped top-k indices, and a second run with the same arguments dumps
+	the same arrays."""
+	runs = []
+	for i in range(2):
+		d = tmp_path / f"run{i}"
+		p = _run(args=["--config", "small", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+		assert p.returncode == 0, p.stderr[-3000:]
+		lines = [l for l in p.stdout.splitlines() if l.strip()]
+		assert len(lines) == 1, p.stdout[-2000:]
+		runs.append((json.loads(lines[0]), {f.stem: np.load(f) for f in d.glob("*.npy")}))
+	line, arr = runs[0]
+	assert line["full"] is False and line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "queries/s" and line["higher_is_better"] is True
+	assert line["value"] == pytest.approx(2000 * 3 / (line["ms_per_step"] * 3e-3), rel=1e-6)
+	assert not {"roofline", "roofline_scan", "stage_ms", "sustained", "retrieve_only", "cpu_baseline", "ivf_search", "solo_rank0"} & set(line)
+	Q, k, kr, tops = 2000, 10, 100, [1, 10]
+	assert sorted(arr) == ["exact_topk_indices", "exact_topk_values", "overlap_counts", "recall", "retrieved_topk_indices", "retrieved_topk_values"]
+	assert all(a.dtype in (np.float32, np.float64) for a in arr.values())
+	assert arr["exact_topk_values"].shape == arr["exact_topk_indices"].shape == (Q, k)
+	assert arr["retrieved_topk_values"].shape == arr["retrieved_topk_indices"].shape == (Q, kr)
+	assert np.all(np.diff(arr["exact_topk_values"], axis=1) <= 0) and np.all(np.diff(arr["retrieved_topk_values"], axis=1) <= 0)
+	ei, ai = arr["exact_topk_indices"].astype(np.int64), arr["retrieved_topk_indices"].astype(np.int64)
+	want = [[len(set(ei[q, :t]) & set(ai[q])) for q in range(Q)] for t in tops]
+	assert np.array_equal(arr["overlap_counts"], np.array(want, dtype=np.float64))
+	assert arr["recall"] == pytest.approx([line["recall"][f"recall@{t}"] for t in tops], abs=6e-5)
+	for name, a in arr.items():
+		assert np.array_equal(a, runs[1][1][name]), name
 
 
 def test_bench_partition_abort_falls_back_to_side_with_fresh_workers():

@@ -613,10 +613,10 @@ def test_entry_A_from_score_chunks_equals_combined_pickle(gpu, tmp_path):
 
 
 def test_bench_contract_small_config(gpu):
-	"""bench.py prints exactly one JSON line on stdout with the driver's keys plus `roofline` and `cpu_baseline` (small config)."""
+	"""bench.py --full prints exactly one JSON line on stdout with the driver's keys plus `roofline` and `cpu_baseline` (small config)."""
 	import subprocess, sys
 	root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-	out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "small", "--steps", "3", "--warmup", "1", "--cpu-sample-queries", "256"],
+	out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "small", "--steps", "3", "--warmup", "1", "--cpu-sample-queries", "256", "--full"],
 						 capture_output=True, text=True, timeout=600)
 	assert out.returncode == 0, out.stderr[-2000:]
 	lines = [l for l in out.stdout.splitlines() if l.strip()]

@@ -99,8 +99,16 @@ def test_entry_point_B_results(golden_dir, golden_meta):
 	S = cur.get_complete_row(A_test[:, anc])
 	_close(cur.U[:8, :8], g["U_sample"], rtol=1e-4, atol=1e-5)
 	_close(S[:16, :256], g["S_sample"], rtol=1e-4, atol=1e-4)
-	_, ti = torch.topk(S, 100, dim=1)
-	assert (np.sort(ti.numpy(), 1) == np.sort(g["approx_topk_idx"], 1)).mean() > 0.9999
+	# the top-100 sets are the reference's except where fp32 rounding, which differs between CPUs' GEMM kernels (a few 1e-6 relative
+	# here), reorders a near-tie at the boundary: every swapped item scores within 1e-5 relative of the row's 100th score, fewer than 20 swaps
+	tv, ti = torch.topk(S, 100, dim=1)
+	swapped = 0
+	for q, (got, want) in enumerate(zip(ti.tolist(), g["approx_topk_idx"].tolist())):
+		diff = set(got) ^ set(want)
+		kth = float(tv[q, -1])
+		assert all(abs(float(S[q, i]) - kth) <= 1e-5 * (1 + abs(kth)) for i in diff), (q, sorted(diff))
+		swapped += len(diff) // 2
+	assert swapped < 1e-4 * ti.numel(), swapped
 	_, ei = torch.topk(A_test, 100, dim=1)
 	assert (ei.numpy() == g["exact_topk_idx"]).all()
 	res = O.eval_approx_score_mat_for_all_topk(A_test, S, [1, 10, 50, 100], 100)
