@@ -636,16 +636,10 @@ __global__ __launch_bounds__(256, 2) void ivf_tile128_kernel(const uint16_t *__r
 		asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v_), "v"((OFF)[i]), "s"(BASE) : "memory", "m0"); \
 	} while (0)
 	// DMA of the next k-tile: two of the wave's eight 1 KiB pieces per k-step, between the fragment reads and the MFMAs of the step
-#ifdef ANNCUR_V_IVF_NODMA   // (ablation build, results wrong: scripts/r5/ivf_ablation.sh)
-#define T128_DEN(DEN) ((DEN) && false)
-#define T128_ROWS_WAIT 0
-#else
-#define T128_DEN(DEN) (DEN)
 #define T128_ROWS_WAIT 8   // the phase's DMA pieces, issued after the rows' loads
-#endif
 #define T128_DMA2(s, DA, AOFF, DB, BOFF, DD, DEN)                                                                 \
 	do {                                                                                                          \
-		if (T128_DEN(DEN)) {                                                                                              \
+		if (DEN) {                                                                                                \
 			if ((s) < 2) { T128_PIECE(DA, AOFF, DD, 2 * ((s) & 1)); T128_PIECE(DA, AOFF, DD, 2 * ((s) & 1) + 1); } \
 			else { T128_PIECE(DB, BOFF, (DD) + T128_TILE_BYTES, 2 * ((s) & 1)); T128_PIECE(DB, BOFF, (DD) + T128_TILE_BYTES, 2 * ((s) & 1) + 1); } \
 		}                                                                                                         \
@@ -777,11 +771,7 @@ __global__ __launch_bounds__(256, 2) void ivf_tile128_kernel(const uint16_t *__r
 #pragma unroll
 				for (int e = 0; e < 16; ++e) {
 					const int row = wm * 64 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-#ifdef ANNCUR_V_IVF_NOSTORE   // (ablation build)
-					if (row < d.p_rows && n < d.v_rows && acc[m][tt][e] == 1.2345e30f) col[ro[m][e >> 2][e & 3]] = acc[m][tt][e];
-#else
 					if (row < d.p_rows && n < d.v_rows) col[ro[m][e >> 2][e & 3]] = acc[m][tt][e];
-#endif
 				}
 			}
 		if (!has_next) break;
@@ -797,7 +787,6 @@ __global__ __launch_bounds__(256, 2) void ivf_tile128_kernel(const uint16_t *__r
 #undef T128_WAIT
 #undef T128_LOAD
 #undef T128_DMA2
-#undef T128_DEN
 #undef T128_ROWS_WAIT
 #undef T128_PIECE
 }

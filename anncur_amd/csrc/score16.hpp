@@ -126,7 +126,7 @@ __device__ __forceinline__ void filter16_one(float v, uint32_t code, float tau, 
 	if (__builtin_expect(m != 0ull, 0)) {
 		if (hit) {
 			const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-			lds_store_2x32(fill + rank * 8u, __float_as_uint(v), item0c + code);
+			lds_write_2x32(fill + rank * 8u, __float_as_uint(v), item0c + code);
 		}
 		fill += 8u * (uint32_t)__builtin_popcountll(m);
 	}
@@ -166,7 +166,7 @@ __device__ __forceinline__ void ladder_refresh(uint32_t lcnt_lane, uint32_t lvl_
 		jn = take ? (uint32_t)j : jn;
 		tn = take ? lv[j - 1] : tn;
 	}
-	if (jn > jc) lds_store_u32(jcur_lane, jn);
+	if (jn > jc) lds_write_u32(jcur_lane, jn);
 #pragma unroll
 	for (int t = 0; t < 4; ++t) {
 		const float o = __int_as_float(__builtin_amdgcn_ds_bpermute((16 * t + c16) * 4, __float_as_int(tn)));
@@ -237,22 +237,12 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const int c16 = lane & 15, g4 = lane >> 4;
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	unsigned long long st_entry = __builtin_amdgcn_s_memrealtime();
-	asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(st_entry)::"memory");
-#endif
-	// static priority (experiment, round 5): the two workgroups of a CU share each SIMD's matrix pipe; at equal priority their waves fall into
-	// step -- both in the MFMA section (each at half rate), then both in the tile's ~600 cycles of DMA issue / checks / barrier with the pipe idle.
-	// One of the two at a higher priority runs its MFMA section at full rate and does its bookkeeping while the other has the pipe.
-#ifdef ANNCUR_TIMING_EXPERIMENTS   // measured NULL (ANNCUR_DEBUG_PRIO = 1 / 2 / 3, by dispatch half or by parity: sweep 0.4511-0.4543 ms against 0.4517-0.4542 without; profiles/r05_static_priority_null.txt)
-	if (p.prio_mode) {   // (uniform)
-		const int sel = (p.prio_mode & 4) ? (int)(blockIdx.x & 1u) : (int)((blockIdx.x >> 8) & 1u);   // which co-resident workgroup: blocks b and b + 256 share a CU under round-robin dispatch (speed only)
-		if (sel) { if ((p.prio_mode & 3) == 1) __builtin_amdgcn_s_setprio(1); else if ((p.prio_mode & 3) == 2) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
-	}
-#endif
+	// (Round 5 measured a static wave priority for one of a CU's two workgroups -- they share each SIMD's matrix pipe and at equal priority
+	//  fall into step, both in the MFMA section, then both in the tile's DMA issue / checks / barrier: null, sweep 0.4511-0.4543 ms against
+	//  0.4517-0.4542 without; profiles/r05_static_priority_null.txt.)
 	const int wid = xcd_remap(blockIdx.x, p.n_wg);
 	const int n_rb = (int)((p.Q + C::BQ - 1) / C::BQ);
-	// work id -> (row block, split): split-major (p.rb_major = 1, row-block-major, is an experiments knob: measured worse, see launch_fused)
+	// work id -> (row block, split): split-major (p.rb_major = 1, row-block-major, measured worse: see launch_fused)
 	const int split = p.rb_major ? wid % p.S : wid / n_rb, rb = p.rb_major ? wid / p.S : wid - split * n_rb;
 
 	// ---- this lane's four queries: B operand fragments, resident for the whole kernel.  B[k = 8 (lane >> 4) + j][col = lane & 15]
@@ -295,8 +285,8 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 	uint32_t fill = w.base;
 	{
 		const int64_t q = q_wave0 + lane;
-		lds_store_u32(w.cnt + (uint32_t)lane * 4u, (p.carry && q < p.Q) ? p.seg_cnt[q * p.nseg + split] : 0u);
-		lds_store_u32(w.jcur + (uint32_t)lane * 4u, 0u);
+		lds_write_u32(w.cnt + (uint32_t)lane * 4u, (p.carry && q < p.Q) ? p.seg_cnt[q * p.nseg + split] : 0u);
+		lds_write_u32(w.jcur + (uint32_t)lane * 4u, 0u);
 	}
 	if (p.ladder_on) {   // (uniform) the wave's 64 level rows: 2 KB = two DMA pieces, waited for with the first tile
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -332,8 +322,8 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 				if (c0 < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c0] = (uint8_t)split;
 				if (c1 < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c1] = (uint8_t)split;
 			}
-			lds_store_u32(ticket_slot + 8u, c0);   // (the prologue's pair sits in the third and fourth ticket word)
-			lds_store_u32(ticket_slot + 12u, c1);
+			lds_write_u32(ticket_slot + 8u, c0);   // (the prologue's pair sits in the third and fourth ticket word)
+			lds_write_u32(ticket_slot + 12u, c1);
 			__builtin_amdgcn_s_waitcnt(0xC07F);
 		}
 		__syncthreads();
@@ -381,16 +371,6 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 	const uint32_t lane_code = (uint32_t)c16 << WQ_ITEM_BITS;
 	__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): stagger16_tile() counts LDS reads
 	float tau_hi[2] = {tau[2], tau[3]};
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	uint32_t ph_acc[5] = {0u, 0u, 0u, 0u, 0u};   // phase stamps of the diagnostic build: see score_kernel
-	uint32_t ph_t = (uint32_t)__builtin_amdgcn_s_memtime();
-	uint32_t ph_tiles = 0;
-#define PH16(i) do { const uint32_t now_ = (uint32_t)__builtin_amdgcn_s_memtime(); ph_acc[i] += now_ - ph_t; ph_t = now_; } while (0)
-#define PH16_TILE() do { ++ph_tiles; } while (0)
-#else
-#define PH16(i) do { } while (0)
-#define PH16_TILE() do { } while (0)
-#endif
 	// (Round 4 measured a SCHEDULED drain here -- all four waves of the workgroup draining in the same tile, by a uniform countdown planned for
 	//  ~160 entries, instead of each wave draining when ITS queue holds DRAIN_AT entries: sweep launches 0.4992 ms with it, 0.4893 without,
 	//  0.4888 at a period of 24 tiles; the per-tile barrier wait it was meant to remove is the waves' HIT imbalance, not their drains -- phase
@@ -430,20 +410,16 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 		if (nx >= 0) tile_dma_w(nx, lds_base + ((CUR) ^ 1) * C::TILE_BYTES);                                                    \
 		uint32_t ticket = 0;                                                                                                    \
 		if (crossed && tid == 0) ticket_draw(ticket, ctr_rb + slice);                                                           \
-		PH16(0);                                                                                                                \
 		LADDER_STEP();                                                                                                          \
 		R16_DRAIN_CHECK(J);                                                                                                     \
 		const uint32_t item0 = ((uint32_t)J * TILE_I + 4 * g4) | lane_code;                                                     \
-		PH16(1);                                                                                                                \
 		stagger16_tile<KP, CUR>(aoff, xb, accP, tau, tau_prev, item0, item0_prev, w, fill);                                        \
 		tau_prev[0] = tau_hi[0]; tau_prev[1] = tau_hi[1]; item0_prev = item0;                                                   \
-		PH16(2);                                                                                                                \
 		ticket_wait(ticket);                                                                                                    \
-		PH16(3);                                                                                                                \
 		if (crossed) {                                                                                                          \
 			if (tid == 0) {                                                                                                     \
 				if (S16_SLICED) ticket = slice_resolve(ticket, ctr_rb, p.n_chunks, p.chunks_per_slice, slice, tried);             \
-				lds_store_u32(ticket_slot, ticket);                                                                             \
+				lds_write_u32(ticket_slot, ticket);                                                                             \
 				if (p.chunk_owner && ticket < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + ticket] = (uint8_t)split; \
 				__builtin_amdgcn_s_waitcnt(0xC07F);                                                                             \
 			}                                                                                                                   \
@@ -451,14 +427,8 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 			t_cend = min(nx + p.chunk_tiles, p.tile_end);                                                                       \
 		}                                                                                                                       \
 		__syncthreads();                                                                                                        \
-		PH16(4);                                                                                                                \
-		PH16_TILE();                                                                                                            \
 		t_cur = nx;                                                                                                             \
 	} while (0)
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	unsigned long long st_c0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-	asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(st_c0), "+s"(st_r0)::"memory");
-#endif
 	ANNCUR_PAD_HERE();
 	while (t_cur >= 0) {
 		STAGGER16_STEP(0);
@@ -467,22 +437,6 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 	}
 #undef STAGGER16_STEP
 #undef LADDER_STEP
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	if (lane == 0 && d_sweep_stamps && p.debug_stamp && blockIdx.x * NW + wave < 8192) {
-		unsigned long long *ph = d_sweep_stamps + 5 * 8192 + (size_t)(blockIdx.x * NW + wave) * 8;
-		for (int i = 0; i < 5; ++i) ph[i] = ph_acc[i];
-		ph[5] = ph_tiles;
-	}
-	if (tid == 0 && d_sweep_stamps && p.debug_stamp && blockIdx.x < 8192) {
-		unsigned long long *stamps = d_sweep_stamps;
-		const unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
-		stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - st_c0;
-		stamps[2 * blockIdx.x + 1] = r1 - st_r0;
-		stamps[2 * 8192 + 3 * blockIdx.x] = st_entry; stamps[2 * 8192 + 3 * blockIdx.x + 1] = st_r0; stamps[2 * 8192 + 3 * blockIdx.x + 2] = r1;
-	}
-#endif
-#undef PH16
-#undef PH16_TILE
 	// drain: sub-tiles {2,3} of the last tile (16 pushes: at most the whole queue)
 	wq_drain<true>(w, fill);
 #define F16_LAST(e)                                                                                                             \

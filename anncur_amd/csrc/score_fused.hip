@@ -35,20 +35,6 @@
 #else
 #define ANNCUR_PAD_HERE() do { } while (0)
 #endif
-// Tuning knobs (ANNCUR_DEBUG_* environment variables) exist in the experiments library only (`make experiments`, -DANNCUR_TIMING_EXPERIMENTS):
-// the product library reads no environment -- knob() is the constant nullptr there and every `if (const char *dbg = knob(...))` folds away.
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-static inline const char *knob(const char *name) { return getenv(name); }
-#else
-static inline const char *knob(const char *) { return nullptr; }
-#endif
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-__device__ unsigned long long *d_sweep_stamps = nullptr;  // diagnostic build: {d s_memtime, d s_memrealtime} of the sweep's tile loop per workgroup
-__device__ unsigned long long *d_sel_stamps = nullptr;  // diagnostic build: phase stamps of the wave-level select kernels (4 per workgroup)
-#define SEL_STAMP(i) do { if (d_sel_stamps && wave == 0 && lane == 0) d_sel_stamps[8 * blockIdx.x + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define SEL_STAMP(i) do { } while (0)
-#endif
 #include "select.hpp"
 #include "wave_select.hpp"
 #include "select_stream.hpp"
@@ -104,11 +90,14 @@ struct FusedParams {
 	const float *tau; int tau_stride; // threshold per query: tau[q * tau_stride]
 	uint2 *cand; uint32_t *seg_cnt; int capg;
 	int nseg;                         // candidate segments per query (2 S: 32x32x16 body, lane halves; S: 16x16x32 body)
-	int rb_major;                     // work id -> (row block, split): 1 = row-block-major (dynamic tile schedule), 0 = split-major
+	int rb_major;                     // work id -> (row block, split): 0 = split-major (1 = row-block-major: see launch_fused)
 	int flush_tiles;                  // wave-cooperative queue flush period (tiles)
-	int debug_nostore;                // timing experiments only: candidates are counted but not stored
-	int debug_stamp;                  // timing experiments only: this launch writes the in-kernel clock stamps
-	float tau_bias;                   // 0 in production; ANNCUR_DEBUG_TAU_BIAS (timing experiments only: results become wrong)
+	// Left over from retired tuning experiments, always 0 / their defaults: tau_bias and rb_major are still read by the kernels;
+	// debug_nostore, debug_stamp, prio_mode, nfb, ring_stagger and ring_spin_sleep by none.  They stay while removing them would
+	// change the kernel argument layout.
+	int debug_nostore;
+	int debug_stamp;
+	float tau_bias;
 	int n_wg;                         // grid size (for the XCD remap)
 	// dynamic tile schedule of a sweep stage (chunk_tiles > 0): the workgroups of a query row block draw chunks of `chunk_tiles` consecutive
 	// tiles from the row block's ticket counter instead of sweeping a fixed share -- see score_kernel
@@ -118,11 +107,11 @@ struct FusedParams {
 	int sliced, chunks_per_slice;     // XCD-sliced tickets: chunk_ctr is [row block][N_SLICES], slice s = chunks [s * chunks_per_slice, + chunks_per_slice)
 	// threshold ladder of score16_kernel (score16.hpp): levels [n_rb x BQ][LADDER_LEVELS], counter words [n_rb x BQ][4] (zero at launch),
 	// the cell each wave raises to the threshold it ended with (initialised to tau0 by the threshold kernel), k
-	int prio_mode;                    // static wave priority of the sweep's workgroups (score16_kernel): see launch_fused
+	int prio_mode;
 	int ladder_on; uint32_t ladder_k, ladder_mask;   // ladder_mask = period - 1 (a power of two): tiles between two fetches of a wave's counter words
 	const float *ladder; uint32_t *ladder_cnt; float *tau_final;
-	uint32_t *nfb;                    // the call's fallback counter (workspace word 0): the ring kernel reports a spin timeout there
-	int ring_stagger, ring_spin_sleep; // ring kernel: start delay of waves 4..7 in units of 64 cycles; s_sleep between two polls of a waiting wave
+	uint32_t *nfb;                    // workspace word 0
+	int ring_stagger, ring_spin_sleep;
 };
 
 // Contiguous work ids per XCD (blocks b and b+8 share an XCD's L2): speed only, never correctness.
@@ -194,7 +183,7 @@ __device__ __forceinline__ void tile_dma_s(const uint16_t *__restrict__ Et, int 
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
 	return (uint32_t)(size_t)(__attribute__((address_space(3))) const char *)p;
 }
-__device__ __forceinline__ void lds_store_u64(uint32_t addr, uint32_t lo, uint32_t hi) {
+__device__ __forceinline__ void lds_write_u64(uint32_t addr, uint32_t lo, uint32_t hi) {
 #if defined(__HIP_DEVICE_COMPILE__)
 	const unsigned long long d = ((unsigned long long)hi << 32) | lo;
 	asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(d) : "memory");
@@ -208,7 +197,7 @@ __device__ __forceinline__ uint2 lds_load_u64(uint32_t addr) {
 	return make_uint2((uint32_t)d, (uint32_t)(d >> 32));
 }
 
-__device__ __forceinline__ void lds_store_u32(uint32_t addr, uint32_t v) {
+__device__ __forceinline__ void lds_write_u32(uint32_t addr, uint32_t v) {
 #if defined(__HIP_DEVICE_COMPILE__)
 	asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
 #endif
@@ -236,7 +225,7 @@ __device__ __forceinline__ void ticket_wait(uint32_t &ticket) {
 #endif
 }
 // Two dwords from two separate VGPRs (no 64-bit register pair has to be assembled in the hit path).
-__device__ __forceinline__ void lds_store_2x32(uint32_t addr, uint32_t lo, uint32_t hi) {
+__device__ __forceinline__ void lds_write_2x32(uint32_t addr, uint32_t lo, uint32_t hi) {
 #if defined(__HIP_DEVICE_COMPILE__)
 	asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" ::"v"(addr), "v"(lo), "v"(hi) : "memory");
 #endif
@@ -261,7 +250,7 @@ __device__ __forceinline__ void filter_one(float v, int e, float tau, uint32_t i
 		// compare INSIDE an inline-asm string, 0-6 wait states behind the MFMA whose result it read, and lost a survivor now and then
 		// (found by the randomised parity run; scripts/check_mfma_hazards.py flags exactly that string).
 		if (v >= tau) {
-			lds_store_2x32((qcnt & (uint32_t)((D - 1) << 11)) | lq, __float_as_uint(v), item0 + (uint32_t)((e & 3) + 8 * (e >> 2)));
+			lds_write_2x32((qcnt & (uint32_t)((D - 1) << 11)) | lq, __float_as_uint(v), item0 + (uint32_t)((e & 3) + 8 * (e >> 2)));
 			qcnt += 2048u;
 		}
 	} else if (INLINE_HIT) {
@@ -269,13 +258,13 @@ __device__ __forceinline__ void filter_one(float v, int e, float tau, uint32_t i
 		// branch out and back (taken when one does)
 		if (__builtin_expect(__ballot(v >= tau) != 0ull, 1)) {
 			if (v >= tau) {
-				lds_store_2x32((qcnt & (uint32_t)((D - 1) << 11)) | lq, __float_as_uint(v), item0 + (uint32_t)((e & 3) + 8 * (e >> 2)));
+				lds_write_2x32((qcnt & (uint32_t)((D - 1) << 11)) | lq, __float_as_uint(v), item0 + (uint32_t)((e & 3) + 8 * (e >> 2)));
 				qcnt += 2048u;
 			}
 		}
 	} else if (__builtin_expect(__ballot(v >= tau) != 0ull, 0)) {
 		if (v >= tau) {
-			lds_store_2x32((qcnt & (uint32_t)((D - 1) << 11)) | lq, __float_as_uint(v), item0 + (uint32_t)((e & 3) + 8 * (e >> 2)));
+			lds_write_2x32((qcnt & (uint32_t)((D - 1) << 11)) | lq, __float_as_uint(v), item0 + (uint32_t)((e & 3) + 8 * (e >> 2)));
 			qcnt += 2048u;
 		}
 	}
@@ -303,7 +292,7 @@ __device__ __forceinline__ void mark_wrapped_raw(const f32x16 &acc, uint32_t lq,
 	if (__builtin_expect(__ballot(wrapped) != 0ull, 0)) {
 		if (wrapped) {
 #pragma unroll
-			for (int i = 0; i < D; ++i) lds_store_2x32(lq + (uint32_t)i * 2048u, __float_as_uint(acc[2 * i]), __float_as_uint(acc[2 * i + 1]));
+			for (int i = 0; i < D; ++i) lds_write_2x32(lq + (uint32_t)i * 2048u, __float_as_uint(acc[2 * i]), __float_as_uint(acc[2 * i + 1]));
 			qcnt = RING_RAW;
 		}
 	}
@@ -338,12 +327,7 @@ __device__ __forceinline__ void flush_queue(uint32_t lq, uint32_t &qcnt, uint2 *
 		// kernel recomputes this query exactly
 		if (n > (uint32_t)D) { ncand = 0x80000000u; n = D; }
 	}
-#ifdef ANNCUR_V_SERIAL_FLUSH
-	constexpr bool BATCH_ = false;
-#else
-	constexpr bool BATCH_ = BATCH;
-#endif
-	if constexpr (!BATCH_) {  // (the three-workgroups-per-CU body of ANNCUR_TOPK_QT1 has no sixteen registers to spare: slot by slot)
+	if constexpr (!BATCH) {  // (the three-workgroups-per-CU body of ANNCUR_TOPK_QT1 has no sixteen registers to spare: slot by slot)
 		for (uint32_t i = 0; __ballot(i < n) != 0ull; ++i) {
 			if (i < n) {
 				const uint2 w = lds_load_u64(lq + i * 2048u);
@@ -380,7 +364,7 @@ __device__ __forceinline__ void flush_queue(uint32_t lq, uint32_t &qcnt, uint2 *
 		if ((uint32_t)i < n) {
 			const uint2 w = make_uint2((uint32_t)e[i], (uint32_t)(e[i] >> 32));
 			if (w.y < n_items) {               // (items past I exist only in the matrix' last, partial tile)
-				if (ncand < capg) seg[ncand] = w;  // (capg = 0 in the no-store timing experiment)
+				if (ncand < capg) seg[ncand] = w;
 				ncand++;                        // (a poisoned count stays > capg)
 			}
 		}
@@ -533,12 +517,8 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const int r = lane & 31, h = lane >> 5;
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	unsigned long long st_entry = 0;
-	if (MODE == 1) { st_entry = __builtin_amdgcn_s_memrealtime(); asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(st_entry)::"memory"); }
-#endif
 	const int wid = xcd_remap(blockIdx.x, p.n_wg);
-	const int nsplit = (MODE == 0) ? p.S0 : p.S;  // MODE 2 = MODE 1 without the filter (debug timing)
+	const int nsplit = (MODE == 0) ? p.S0 : p.S;
 	const int n_rb_ = (int)((p.Q + Cfg::BQ - 1) / Cfg::BQ);
 	const bool rbm = MODE == 1 && p.rb_major;   // (uniform) tickets: row-block-major work ids, see score16.hpp
 	const int split = rbm ? wid % p.S : wid / n_rb_;
@@ -618,7 +598,7 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 					if (c < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c] = (uint8_t)split;
 					if (c + 1 < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c + 1] = (uint8_t)split;
 				}
-				lds_store_u32(ticket_slot, c);
+				lds_write_u32(ticket_slot, c);
 				__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the word is in LDS before this wave reaches the barrier
 			}
 			__syncthreads();
@@ -634,26 +614,11 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 	uint32_t dma_off[STAG ? Cfg::TILE_BYTES / 4096 : 1];
 	if constexpr (STAG) {
 		tile_dma_offsets<KP>(dma_off, wave_u, lane);
-#ifdef ANNCUR_V_OLD_DMA
-		if (t_cur >= 0) tile_dma<KP>(p.Et, t_cur, smem, wave, lane);
-#else
 		if (t_cur >= 0) tile_dma_s<KP>(p.Et, t_cur, lds_base, wave_u, dma_off);
-#endif
 	} else if (j_begin < j_end) tile_dma<KP>(p.Et, tile_of(j_begin), smem, wave, lane);
 	__builtin_amdgcn_s_waitcnt(0x0F70);
 	__syncthreads();
 	ANNCUR_PAD_HERE();
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	// In-kernel clock (MI355X guide, 'DVFS give-back' (6)): shader cycles per 100 MHz reference tick around the tile loop.  The
-	// stamps go to a buffer nothing else reads; the shipped library contains none of this.
-	// (this diagnostic is how the MFMA -> v_mov hazard of the Kp = 512 loop was found: the extra instructions moved the loop by 8 bytes
-	//  and the scores changed -- see mfma_chain_done())
-	unsigned long long st_c0 = 0, st_r0 = 0;
-	if (MODE == 1) {
-		st_c0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime();
-		asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(st_c0), "+s"(st_r0)::"memory");
-	}
-#endif
 
 	if constexpr (MODE == 1 && QT == 2) {
 		// ---- staggered sweep (stagger_tile): tile loop unrolled by two so that the LDS buffer parity is a compile-time offset
@@ -670,22 +635,9 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 		// stagger_tile() counts LDS reads with lgkmcnt(n): no scalar load of the prologue may still be in flight (scalar loads share
 		// the counter and return out of order)
 		__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0) only
-#ifdef ANNCUR_V_OLD_DMA   /* A/B variant builds (make variant V=...): one feature of the round-3 sweep switched back */
-#define STAGGER_DMA(NX, CUR) tile_dma<KP>(p.Et, (NX), smem + ((CUR) ^ 1) * Cfg::TILE_BYTES, wave, lane)
-#else
 #define STAGGER_DMA(NX, CUR) tile_dma_s<KP>(p.Et, (NX), lds_base + ((CUR) ^ 1) * Cfg::TILE_BYTES, wave_u, dma_off)
-#endif
 // (Round 3 tried draining by occupancy as well -- a ballot "some lane's ring holds >= 3 / >= 4 entries" per step, beside or instead of the
 //  planned window: both cost 4 % of the sweep at cfg2, same box, alternating -- the check itself, not the drains.  The planned window stays.)
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-		// phase stamps (diagnostic build): shader cycles this WAVE spent per step in {ticket read + DMA issue, ring drain, the tile's MFMA / filter
-		// section, the vmcnt wait, the barrier}; summed over the loop, one record per wave (anncur_debug_sweep_phases, scripts/sweep_phases.py)
-		uint32_t ph_acc[5] = {0u, 0u, 0u, 0u, 0u};
-		uint32_t ph_t = (uint32_t)__builtin_amdgcn_s_memtime();
-#define PH(i) do { const uint32_t now_ = (uint32_t)__builtin_amdgcn_s_memtime(); ph_acc[i] += now_ - ph_t; ph_t = now_; } while (0)
-#else
-#define PH(i) do { } while (0)
-#endif
 #define STAGGER_STEP(CUR)                                                                                                       \
 		do {                                                                                                                    \
 			const int J = t_cur;                                                                                                \
@@ -701,7 +653,6 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 			if (nx >= 0) STAGGER_DMA(nx, CUR);                                                                                  \
 			uint32_t ticket = 0;                                                                                                \
 			if (crossed && tid == 0) ticket_draw(ticket, p.chunk_ctr + rb);  /* in flight until ticket_wait() below */          \
-			PH(0);                                                                                                              \
 			if (t_prev < dense_end || --flush_in2 <= 0) {                                                                       \
 				flush_in2 = p.flush_tiles;                                                                                      \
 				/* (a raw ring holds one tile: sub-tile 0 of the previous tile, sub-tile 1 of the one before) */                \
@@ -709,15 +660,12 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 				flush_queue<Cfg::QDEPTH>(lq1, qcnt[1], seg0 + seg_dt, ncand[1], (uint32_t)p.capg, (uint32_t)p.I, tau[1], item0_pp); \
 			}                                                                                                                   \
 			const uint32_t item0 = (uint32_t)J * TILE_I + 4 * h;                                                                \
-			PH(1);                                                                                                              \
 			stagger_tile<KP, CUR, PRED, INL>(aoff, xb, acc1, tau[0], tau1_prev, item0, item0_prev, lq0, lq1, qcnt[0], qcnt[1], J < dense_end || every_tile); \
 			tau1_prev = tau[1]; item0_pp = item0_prev; item0_prev = item0;                                                      \
-			PH(2);                                                                                                              \
 			ticket_wait(ticket);  /* vmcnt(0): the DMA of the next tile, the queue stores issued with it and the ticket have landed */ \
-			PH(3);                                                                                                              \
 			if (crossed) {                                                                                                      \
 				if (tid == 0) {                                                                                                 \
-					lds_store_u32(ticket_slot, ticket);                                                                         \
+					lds_write_u32(ticket_slot, ticket);                                                                         \
 					if (p.chunk_owner && ticket < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + ticket] = (uint8_t)split; \
 					__builtin_amdgcn_s_waitcnt(0xC07F);                                                                         \
 				}                                                                                                               \
@@ -725,7 +673,6 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 				t_cend = min(nx + p.chunk_tiles, p.tile_end);                                                                   \
 			}                                                                                                                   \
 			__syncthreads();                                                                                                    \
-			PH(4);                                                                                                              \
 			t_prev = J; t_cur = nx;                                                                                             \
 		} while (0)
 		while (t_cur >= 0) {
@@ -734,13 +681,6 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 			STAGGER_STEP(1);
 		}
 #undef STAGGER_STEP
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-		if (lane == 0 && d_sweep_stamps && p.debug_stamp && blockIdx.x * 4 + wave < 8192) {
-			unsigned long long *ph = d_sweep_stamps + 5 * 8192 + (size_t)(blockIdx.x * 4 + wave) * 8;
-			for (int i = 0; i < 5; ++i) ph[i] = ph_acc[i];
-		}
-#endif
-#undef PH
 		flush_queue<Cfg::QDEPTH>(lq1, qcnt[1], seg0 + seg_dt, ncand[1], (uint32_t)p.capg, (uint32_t)p.I, tau[1], item0_pp);  // keep one tile's hits per queue window
 #pragma unroll
 		for (int e = 0; e < 16; ++e)  // drain: sub-tile 1 of the last tile
@@ -785,7 +725,7 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 			ticket_wait(ticket);                                                                                                \
 			if (crossed) {                                                                                                      \
 				if (tid == 0) {                                                                                                 \
-					lds_store_u32(ticket_slot, ticket);                                                                         \
+					lds_write_u32(ticket_slot, ticket);                                                                         \
 					if (p.chunk_owner && ticket < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + ticket] = (uint8_t)split; \
 					__builtin_amdgcn_s_waitcnt(0xC07F);                                                                         \
 				}                                                                                                               \
@@ -816,7 +756,7 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 			mark_wrapped_raw<Cfg::QDEPTH>(accB, lq0, qcnt[0]);
 		}
 		last_item0 = item0_prev;
-	} else if constexpr (MODE == 1 && QT == 1 && KP >= 128 && !INL) {  // (INL = the plain loop, kept for A/B in the experiments build)
+	} else if constexpr (MODE == 1 && QT == 1 && KP >= 128 && !INL) {  // (INL: the plain loop below instead; no launch asks for it)
 		// ---- software-pipelined sweep for Kp = 512 (stagger1_tile): tile loop unrolled by two (buffer parity = immediate offset);
 		// even steps accumulate into accA and filter accB, odd steps the other way round
 		f32x16 accA, accB;
@@ -865,7 +805,7 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 	for (int j = j_begin; j < j_end; j += ts, cur ^= 1) {
 		const int tile = tile_of(j);
 		const bool more = j + ts < j_end;
-		if (more && MODE != 3) tile_dma<KP>(p.Et, tile_of(j + ts), smem + (cur ^ 1) * Cfg::TILE_BYTES, wave, lane);
+		if (more) tile_dma<KP>(p.Et, tile_of(j + ts), smem + (cur ^ 1) * Cfg::TILE_BYTES, wave, lane);
 		bool ring_fresh = false;  // (uniform) the rings were drained at the head of this step: they will hold nothing but this tile
 		if (MODE == 1) {
 			// drain the hit queues of the previous tiles right behind the DMA: the stores get the whole MFMA phase to retire
@@ -910,11 +850,6 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 					if (qv[t] < p.Q) *reinterpret_cast<float4 *>(p.gmax + qv[t] * p.n_groups + ((int64_t)j * 2 + h) * 4) = m;
 				}
 			}
-		} else if (MODE == 2 || MODE == 3) {
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-			for (int t = 0; t < QT; ++t) asm volatile("" ::"v"(acc[t]));  // timing experiment: GEMM + staging only
-#endif
 		} else {
 			const uint32_t item0 = (uint32_t)tile * TILE_I + 4 * h;
 #pragma unroll
@@ -926,25 +861,12 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 			}
 			last_item0 = item0;
 		}
-		if (MODE != 3) {
-			__builtin_amdgcn_s_waitcnt(0x0F70);  // the DMA of tile j+1 (and the queue stores issued with it) have landed
-			__syncthreads();
-		}
+		__builtin_amdgcn_s_waitcnt(0x0F70);  // the DMA of tile j+1 (and the queue stores issued with it) have landed
+		__syncthreads();
 	}
 	}  // plain loop
 
 #undef tile_of
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	if (MODE == 1 && tid == 0) {
-		unsigned long long *stamps = d_sweep_stamps;
-		if (stamps && p.debug_stamp && blockIdx.x < 8192) {
-			const unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
-			stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - st_c0;
-			stamps[2 * blockIdx.x + 1] = r1 - st_r0;
-			stamps[2 * 8192 + 3 * blockIdx.x] = st_entry; stamps[2 * 8192 + 3 * blockIdx.x + 1] = st_r0; stamps[2 * 8192 + 3 * blockIdx.x + 2] = r1;
-		}
-	}
-#endif
 	if (MODE == 1) {
 #pragma unroll
 		for (int t = 0; t < QT; ++t) {
@@ -986,8 +908,6 @@ __device__ __forceinline__ int xcc_id() {
 }
 
 #include "score16.hpp"
-#include "score16r.hpp"
-#include "score_q1.hpp"
 #include "score_q16.hpp"
 
 // ------------------------------------------------------------------ a11: approximation error on the same MFMA loop
@@ -1104,29 +1024,8 @@ __global__ __launch_bounds__(256, 2) void error_lds_kernel(const FusedParams p, 
 	uint32_t dma_off[Cfg::TILE_BYTES / 4096];
 	tile_dma_offsets<KP>(dma_off, wave_u, lane);
 	const int j_begin = split * p.tiles_per_split, j_end = min(j_begin + p.tiles_per_split, p.n_tiles);
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	// ANNCUR_DEBUG_ERR_MODE (p.ring_stagger here): 1 = every exact-tile DMA re-reads the split's first tile (L2-hot: no HBM latency, same
-	// instruction stream), 2 = no sums (DMAs and MFMAs only), 4 = the same bytes from CONTIGUOUS memory (wrong values, timing only)
-	const int dbg_mode = p.ring_stagger;
-	if (dbg_mode == 4) {
-#pragma unroll
-		for (int i = 0; i < PA; ++i) {
-			const int ch = (wave * PA + i) * 64 + lane, row = ch >> 2, pos = ch & 3;
-			asrc[i] = (uint32_t)(row * 64 + 16 * (pos ^ ((row >> 2) & 3)));
-		}
-	}
-#define ERRL_SUMS_ON (dbg_mode != 2)
-#else
-#define ERRL_SUMS_ON true
-#endif
 	auto adma = [&](int j, int buf) {
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-		if (dbg_mode == 1) j = j_begin;
-#endif
 		const unsigned char *src = abase + (int64_t)j * (TILE_I * 2);   // (uniform)
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-		if (dbg_mode == 4) src = reinterpret_cast<const unsigned char *>(Aex) + ((int64_t)rb * p.n_tiles + j) * ATILE;
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 		for (int i = 0; i < PA; ++i) {
@@ -1169,7 +1068,6 @@ __global__ __launch_bounds__(256, 2) void error_lds_kernel(const FusedParams p, 
 		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                      \
 		_Pragma("unroll") for (int t = 0; t < QT; ++t)                                                                          \
 			_Pragma("unroll") for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(ex[t][g].w));                                  \
-		if (ERRL_SUMS_ON)                                                                                                       \
 		_Pragma("unroll") for (int t = 0; t < QT; ++t)                                                                          \
 			_Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                                    \
 				const float x = ex[t][e >> 2].get(e & 3);                                                                       \
@@ -1177,7 +1075,6 @@ __global__ __launch_bounds__(256, 2) void error_lds_kernel(const FusedParams p, 
 				se[t] = fmaf(d, d, se[t]);                                                                                      \
 				sn[t] = fmaf(x, x, sn[t]);                                                                                      \
 			}                                                                                                                   \
-		else { _Pragma("unroll") for (int t = 0; t < QT; ++t) { se[t] += acc[t][0]; sn[t] += ex[t][0].get(0); } }              \
 		/* this wave's parts of the next item tile and of the next exact tile have landed; the barrier orders LDS only */        \
 		if (NAB == 3 && ahead) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA) : "memory");                                        \
 		else __builtin_amdgcn_s_waitcnt(0x0F70);                                                                                \
@@ -1190,7 +1087,6 @@ __global__ __launch_bounds__(256, 2) void error_lds_kernel(const FusedParams p, 
 		if (j + 1 < j_end) ERRL_STEP(1, 1, j + 1);
 	}
 #undef ERRL_STEP
-#undef ERRL_SUMS_ON
 #pragma unroll
 	for (int t = 0; t < QT; ++t)
 		if (qv[t] < p.Q) {
@@ -1517,7 +1413,6 @@ __global__ __launch_bounds__(256) void select_wave_kernel(const uint2 *__restric
 	const int lane = lane_id(), wave = threadIdx.x >> 6;
 	const int64_t q = (int64_t)blockIdx.x * 4 + wave;
 	if (q >= Q) return;
-	SEL_STAMP(0);
 	const uint32_t c = (lane < nseg) ? seg_cnt[q * nseg + lane] : 0u;
 	const uint32_t inc = wave_scan_incl<DppAdd>(c);
 	const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, WAVE - 1), pre = inc - c;
@@ -1536,7 +1431,6 @@ __global__ __launch_bounds__(256) void select_wave_kernel(const uint2 *__restric
 	// to back.  Written chunk by chunk hipcc emitted LOAD_U serial chains of seven LDS round trips and one exposed HBM latency per chunk.
 	// (A search without LDS -- the segment ends read into scalars with v_readlane, every lane counting the ends at or below its index --
 	//  was slower: 9.5 k instead of 5 k cycles per wave for the 23 ends x 8 chunks.)
-	SEL_STAMP(1);
 	constexpr int LOAD_U = 8;
 	for (uint32_t j0 = 0; j0 < total; j0 += LOAD_U * WAVE) {
 		int sg[LOAD_U];  // last segment whose exclusive prefix is <= j (skips empty segments)
@@ -1557,15 +1451,11 @@ __global__ __launch_bounds__(256) void select_wave_kernel(const uint2 *__restric
 #pragma unroll
 		for (int u = 0; u < LOAD_U; ++u) ps[u] = __shfl(pre, sg[u]);
 		uint2 e[LOAD_U];
-		if (j0 == 0) SEL_STAMP(4);
 #pragma unroll
 		for (int u = 0; u < LOAD_U; ++u) {
 			const uint32_t j = j0 + (uint32_t)(u * WAVE + lane);
 			e[u] = qc[j < total ? (int64_t)sg[u] * capg + (j - ps[u]) : 0];
 		}
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-		if (j0 == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); SEL_STAMP(5); }
-#endif
 #pragma unroll
 		for (int u = 0; u < LOAD_U; ++u) {
 			if (j0 + (uint32_t)(u * WAVE) < total) {  // (uniform)
@@ -1574,15 +1464,12 @@ __global__ __launch_bounds__(256) void select_wave_kernel(const uint2 *__restric
 			}
 		}
 	}
-	SEL_STAMP(2);
 	if (TAU_ONLY) {
 		if (w.cnt > k) wsel_compact<4, false, true>(w, k);
 		if (lane == 0 && w.cnt >= k) tau[q * tau_stride] = fmaxf(tau[q * tau_stride], w.tau);
-		SEL_STAMP(3);
 		return;
 	}
 	wsel_finish<0, 4, WqCfg<KW>::E, true>(w, k, out_val + q * (int64_t)k, out_idx + q * (int64_t)k, remap);
-	SEL_STAMP(3);
 }
 
 }  // namespace
@@ -1600,11 +1487,7 @@ struct FusedPlan {
 	int lg;   // candidate segments per query and item split: 2 (32x32x16 sweep: lane halves), 1 (16x16x32 sweep: wave-level queue)
 	bool body16;  // the sweep stages run score16_kernel
 	bool bodyef;  // the sweep stages run evalf_kernel (anncur_eval_fused: candidates + error sums in one pass; 32x32x16, wave queue, static shares)
-	bool wg8;     // ... score16_kernel<Kp, 8>: the same body in 8-wave workgroups of BQ_s = 512 queries, one per CU (half the DMA pieces per wave)
-	bool ring16;  // ... score16r_kernel: 8-wave workgroups of BQ_s = 512 queries, flag-synchronised tile ring (score16r.hpp)
-	int BQ_s, n_rb_s;   // query rows per sweep workgroup and the sweep's row blocks (the prepass keeps BQ / n_rb)
-	bool bodyq1;  // the sweep stages run scoreq1_kernel (Kp = 512)
-	bool bodyq16; // ... scoreq16_kernel: the same body on 16x16x32 MFMAs
+	bool bodyq16; // the sweep stages run scoreq16_kernel (Kp = 512: wave-level queue and tickets on 16x16x32 MFMAs)
 	int chunk;  // dynamic tile schedule of the sweep stages: tiles per ticket (0: static shares)
 	bool ladder;  // score16_kernel moves its thresholds up a ladder of levels inside ONE sweep launch (score16.hpp): no stages, no refinement launches
 	int ladder_k2; // rank (in the prepass sample's group maxima) of the ladder's top level
@@ -1653,20 +1536,10 @@ void plan_stages(FusedPlan &P, int64_t Q, int k, double exp_hits, bool staged, d
 	// loose one (higher clock on sparse tiles, costlier pushes on dense ones): cfg2 sweep launches 0.458 ms at 0.35, 0.455 at 0.30,
 	// 0.453 at 0.26, 0.450 at 0.22, 0.453 at 0.18, 0.461 at 0.14 -> 0.63 of the model's fraction.
 	if (P.n_stages == 2) {
-		double shrink = P.body16 ? 0.63 : (k <= WSEL_K ? 1.0 : 0.6);
-		if (const char *dbg = knob("ANNCUR_DEBUG_F1_SHRINK")) shrink = atof(dbg);
+		const double shrink = P.body16 ? 0.63 : (k <= WSEL_K ? 1.0 : 0.6);
 		const double f1 = frac[0] * shrink;
 		frac[0] = f1 > fmin ? f1 : (fmin < frac[0] ? fmin : frac[0]);
 	}
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	if (const char *dbg = getenv("ANNCUR_DEBUG_STAGES")) {  // tuning knob "f1,f2" or "f1" (>= 1: single stage)
-		double f1 = 0, f2 = 0;
-		const int n = sscanf(dbg, "%lf,%lf", &f1, &f2);
-		if (staged && n == 2 && f1 > 0 && f2 > f1 && f2 < 1) { frac[0] = f1; frac[1] = f2; P.n_stages = 3; }
-		else if (staged && n == 1 && f1 > 0 && f1 < 1) { frac[0] = f1; frac[1] = 1.0; P.n_stages = 2; }
-		else if (n == 1 && f1 >= 1) P.n_stages = 1;
-	}
-#endif
 	double rate = exp_hits / ((double)P.n_tiles * 2.0);  // expected hits per (query half, tile) in the first stage
 	int prev = 0;
 	for (int i = 0; i < P.n_stages; ++i) {
@@ -1686,14 +1559,13 @@ void plan_stages(FusedPlan &P, int64_t Q, int k, double exp_hits, bool staged, d
 		// 0.84 vs 0.88; I = 10^6, Kp = 256 (P ~ 0.2 over most of the sweep) 2.80 vs 2.76 -> exec above P = 0.25.
 		// (staggered Kp <= 256 loop only: launch_fused ignores it elsewhere)
 		P.stage_pred[i] = (1.0 - exp(-4.0 * rate)) > 0.25 ? 1 : 0;
-		if (const char *dbg = knob("ANNCUR_DEBUG_ALL_PRED")) P.stage_pred[i] = atoi(dbg) != 0;
 		// next stage: threshold = k-th best of the fraction seen so far
 		rate = (double)k / ((double)end * unit_items) * 16.0 * 1.2;
 		prev = end;
 	}
 }
 
-FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, bool mfma16 = false, bool qt1 = false, bool mfma32 = false, bool ring = false, bool evalf = false,
+FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, bool mfma16 = false, bool qt1 = false, bool mfma32 = false, bool evalf = false,
 					 bool no_ladder = false) {
 	FusedPlan P{};
 	P.ok = false;
@@ -1703,7 +1575,7 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	// qt1 (ANNCUR_TOPK_QT1, Kp = 128 / 256): one 32-query sub-tile per wave with the cross-tile pipeline of the Kp = 512 sweep,
 	// 3 workgroups per CU (<= 168 VGPRs) instead of two sub-tiles staggered inside a wave at 2 workgroups per CU
 	if (evalf && !(KP <= 256 && I < (int64_t)(1 << 26))) return P;   // anncur_eval_fused: Kp <= 256 (two workgroups per CU), queue entries carry the query
-	if (evalf) { qt1 = false; mfma16 = false; mfma32 = false; ring = false; leading = false; P.leading = 0; }
+	if (evalf) { qt1 = false; mfma16 = false; mfma32 = false; leading = false; P.leading = 0; }
 	P.bodyef = evalf;
 	P.QT = (KP <= 256 && !(qt1 && KP >= 128)) ? 2 : 1;
 	P.BQ = 128 * P.QT;
@@ -1712,7 +1584,6 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	P.n_full = (int)(I / TILE_I);
 	// prepass sample: enough groups that the k-th largest group maximum is a tight bound
 	int target = (4 * k > 512) ? 4 * k : 512;
-	if (const char *dbg = knob("ANNCUR_DEBUG_SAMPLE_GROUPS")) target = atoi(dbg);   // prepass sample size in groups (tuning knob)
 	int n_st16 = (target + 1) / 2;
 	if ((int64_t)n_st16 * 8 <= P.n_full) { P.group = 16; P.n_st = n_st16; }
 	else { P.group = 4; P.n_st = (target + 7) / 8; }
@@ -1720,20 +1591,16 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	P.n_groups = P.n_st * (P.group == 16 ? 2 : 8);
 	if (P.n_groups < k) return P;
 	int slots = ((P.QT == 1 && KP <= 256) ? 3 : 2) * num_cu();
-	if (knob("ANNCUR_DEBUG_ONE_WG")) slots = num_cu();  // one sweep workgroup per CU (co-residence experiment)
 	// Dynamic tile schedule (staggered 32x32x16 sweep, Kp <= 256): tickets of CHUNK_TILES tiles per query row block instead of fixed shares
 	// (score_kernel).  Workgroups per row block: enough to fill every slot (rounded UP -- a workgroup that finds no ticket left ends at
 	// once), at most 32 so that the 2 S segments of a query fit the wave-level select.
-	// Kp = 512: the body with the wave-level queue (score_q1.hpp: queue + counters + ticket words fit the 16 KB the rings took) unless
-	// ANNCUR_TOPK_MFMA32 asks for the per-lane-ring body (static shares: no LDS left for its ticket words) or I >= 2^26
-	P.bodyq1 = KP == 512 && !mfma32 && I < (int64_t)(1 << 26);
-	if (knob("ANNCUR_DEBUG_NO_Q1")) P.bodyq1 = false;
-	P.bodyq16 = P.bodyq1;   // (16x16x32 MFMAs: cfg4 per-GPU shape, one box, alternating: sweep launches 5.21 -> 5.02 ms, step 7.19 -> 7.00; scoreq1_kernel stays for A/B)
-	if (const char *dbg = knob("ANNCUR_DEBUG_Q16")) P.bodyq16 = P.bodyq1 && atoi(dbg) != 0;
-	const bool ticketed = (P.QT == 2 || P.bodyq1) && !evalf;   // the bodies with the ticket schedule
+	// Kp = 512: the body with the wave-level queue (score_q16.hpp: queue + counters + ticket words fit the 16 KB the rings took) unless
+	// ANNCUR_TOPK_MFMA32 asks for the per-lane-ring body (static shares: no LDS left for its ticket words) or I >= 2^26.  (16x16x32 MFMAs
+	// against the same body on 32x32x16, cfg4 per-GPU shape, one box, alternating: sweep launches 5.21 -> 5.02 ms, step 7.19 -> 7.00)
+	P.bodyq16 = KP == 512 && !mfma32 && I < (int64_t)(1 << 26);
+	const bool ticketed = (P.QT == 2 || P.bodyq16) && !evalf;   // the bodies with the ticket schedule
 	P.chunk = ticketed ? CHUNK_TILES : 0;
-	if (const char *dbg = knob("ANNCUR_DEBUG_CHUNK")) P.chunk = ticketed ? atoi(dbg) : 0;
-	// Body of the sweep stages, decided here because the ring body changes the decomposition (512-query workgroups, one per CU)
+	// Body of the sweep stages
 	const bool can16 = KP <= 256 && P.QT == 2 && I < (int64_t)(1 << 26);
 	// (default up to k = 384 since late round 4: same process, warm, round robin at cfg2 size -- k = 150: 0.733 vs 0.738 ms for the 32x32x16 body,
 	//  200: 0.779 vs 0.827, 256: 0.829 vs 0.878, 300: 0.909 vs 0.942, 384: 0.951 vs 0.968; level from 500 on: 1.04 / 1.04, 1000: 1.50 / 1.50)
@@ -1744,20 +1611,7 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	constexpr int BODY16_MAX_K = 384, BODY16_MAX_K_LADDER = 1024;
 	const bool ladder_possible = !no_ladder && ticketed && P.n_groups <= 4096;
 	P.body16 = can16 && !mfma32 && !evalf && (mfma16 || k <= (ladder_possible ? BODY16_MAX_K_LADDER : BODY16_MAX_K));
-	if (knob("ANNCUR_DEBUG_MFMA16") && !evalf) P.body16 = can16 && atoi(knob("ANNCUR_DEBUG_MFMA16")) != 0;
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	P.ring16 = P.body16 && k <= WSEL_K && KP >= 128 && P.chunk == CHUNK_TILES && ring;   // opt-in (ANNCUR_TOPK_RING): measured slower than the barrier body, see score16r.hpp
-#else
-	P.ring16 = false;   // (the tile-ring body is compiled into the experiments library only; the product refuses the flag: score_topk_impl)
-	(void)ring;
-#endif
-	if (const char *dbg = knob("ANNCUR_DEBUG_RING16")) P.ring16 = P.body16 && KP >= 128 && P.chunk == CHUNK_TILES && atoi(dbg) != 0;
-	P.wg8 = false;
-	if (const char *dbg = knob("ANNCUR_DEBUG_WG8")) P.wg8 = P.body16 && !P.ring16 && KP >= 128 && atoi(dbg) != 0;
-	P.BQ_s = (P.ring16 || P.wg8) ? 512 : P.BQ;
-	P.n_rb_s = (int)ceil_div64(Q, P.BQ_s);
-	const int slots_s = (P.ring16 || P.wg8) ? num_cu() : slots;   // sweep workgroups resident at once
-	int S = P.chunk > 0 ? (slots_s + P.n_rb_s - 1) / P.n_rb_s : slots_s / P.n_rb_s;
+	int S = P.chunk > 0 ? (slots + P.n_rb - 1) / P.n_rb : slots / P.n_rb;
 	if (P.chunk > 0 && k <= WQ_K2 && S > WAVE / 2) S = WAVE / 2;
 	if (S < 1) S = 1;
 	if (S > 255) S = P.chunk > 0 ? 255 : (S > 256 ? 256 : S);   // (the owner map holds a split in a byte, 255 = none)
@@ -1775,7 +1629,7 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	P.st_per_split = (P.n_st + S0 - 1) / S0;
 	P.S0 = (P.n_st + P.st_per_split - 1) / P.st_per_split;
 	// candidate segments per (query, item split): two (lane halves) in the 32x32x16 sweep, ONE in the 16x16x32 sweep (wave-level queue)
-	P.lg = (P.body16 || P.bodyq1 || P.bodyef) ? 1 : 2;
+	P.lg = (P.body16 || P.bodyq16 || P.bodyef) ? 1 : 2;
 	// expected survivors per query ~ 1.3 k * (tiles / sample tiles), spread over lg S lane segments
 	// (segment capacity -- hence the workspace size -- is planned for the strided sample whatever the hint; with item rows ordered
 	//  by descending norm the leading sample's threshold lets ~40 % fewer elements through: measured on the synthetic protocol)
@@ -1785,7 +1639,6 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	int capg = next_pow2((int)(4.0 * per_seg) + 32);
 	if (capg < 64) capg = 64;
 	if (capg > 16384) capg = 16384;
-	if (const char *dbg = knob("ANNCUR_DEBUG_CAPG")) capg = atoi(dbg);
 	P.capg = capg;
 	// queue window: keep the expected hits per (lane, sub-tile) window near 0.5 so that 8 slots overflow with p ~ 1e-9
 	const double per_lane_tile = exp_hits / ((double)P.n_tiles * 2.0);  // hits per query-half per tile
@@ -1794,11 +1647,9 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	// Threshold ladder (score16.hpp, round 5): the default 16x16x32 body raises its thresholds inside ONE launch from counts of what it keeps, so it
 	// runs unstaged.  The ladder's top level = the sample's group maximum of rank k2 ~ where the k-th best of ALL items is expected to fall among
 	// the sample's (k x sample items / I; the norm-ordered leading sample holds about twice its share of the high scorers), at least 3, at most k / 2.
-	P.ladder = P.body16 && !P.ring16 && !P.wg8 && !no_ladder && P.n_groups <= 4096 && P.chunk > 0;
-	if (const char *dbg = knob("ANNCUR_DEBUG_LADDER")) P.ladder = P.ladder && atoi(dbg) != 0;
+	P.ladder = P.body16 && !no_ladder && P.n_groups <= 4096 && P.chunk > 0;
 	{
 		double r = (double)k * ((double)P.n_st * TILE_I / (double)I) * (leading ? 2.0 : 1.25);
-		if (const char *dbg = knob("ANNCUR_DEBUG_LADDER_K2")) r = atof(dbg);
 		int k2 = (int)(r + 0.5);
 		if (k2 > k / 2) k2 = k / 2;
 		if (k2 < 3) k2 = 3;
@@ -1809,7 +1660,7 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	P.kmax = k <= 128 ? 128 : (k <= 512 ? 512 : 2048);
 	size_t off = 256;
 	P.off_ctr = off;    off = align256(off + (size_t)P.n_rb * 3 * 4 * N_SLICES);   // ticket counters [stage][row block][slice]: zeroed with the header, one memset
-	P.off_lcnt = off;   off = align256(off + (P.ladder ? (size_t)P.n_rb_s * P.BQ_s * 16 : 0));   // ladder counter words: zeroed with the header too
+	P.off_lcnt = off;   off = align256(off + (P.ladder ? (size_t)P.n_rb * P.BQ * 16 : 0));   // ladder counter words: zeroed with the header too
 	P.off_gmax = off;   off = align256(off + (size_t)Q * P.n_groups * 4);
 	P.off_tval = off;   off = align256(off + (size_t)Q * k * 4);
 	P.off_tidx = off;   off = align256(off + (size_t)Q * k * 4);
@@ -1817,7 +1668,7 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	P.off_tau = off;    off = align256(off + (size_t)Q * 4);
 	P.off_hard = off;   off = align256(off + (size_t)Q * 4);
 	P.off_owner = off;  off = align256(off + (size_t)3 * P.n_rb * (size_t)(P.n_tiles / (P.chunk > 0 ? P.chunk : P.n_tiles) + 2));   // chunk owners
-	P.off_lvl = off;    off = align256(off + (P.ladder ? (size_t)P.n_rb_s * P.BQ_s * 4 * LADDER_LEVELS : 0));
+	P.off_lvl = off;    off = align256(off + (P.ladder ? (size_t)P.n_rb * P.BQ * 4 * LADDER_LEVELS : 0));
 	P.off_tau2 = off;   off = align256(off + (P.ladder ? (size_t)Q * 4 : 0));
 	P.off_cand = off;   off = align256(off + (size_t)Q * P.lg * P.S * (size_t)P.capg * 8);
 	P.total = off;
@@ -1827,17 +1678,8 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 
 #define EV(i) do { if (ev) ANNCUR_HIP_OK(hipEventRecord(ev[i], st)); } while (0)
 
-// contiguous item ranges per split instead of interleaved tiles (timing experiment)
-bool contiguous_splits() {
-	if (const char *dbg = knob("ANNCUR_DEBUG_CONTIG")) return atoi(dbg) != 0;
-	return false;
-}
-
-// k <= 128: which wave-level candidate select runs (the buffer-and-compact one or the streaming one)
-bool stream_select_small() {
-	if (const char *dbg = knob("ANNCUR_DEBUG_STREAM128")) return atoi(dbg) != 0;
-	return false;
-}
+// k <= 128: the buffer-and-compact wave-level select runs; the streaming one (select_stream_kernel<false, 2>) stays compiled, never chosen
+constexpr bool STREAM_SELECT_SMALL = false;
 
 // Threshold refinement between two sweep stages: tau[q] = max(tau[q], k-th best candidate collected so far).
 int launch_tau_refine(const uint2 *cand, const uint32_t *seg_cnt, int nseg, int capg, int64_t Q, int k, int kmax, float *tau, int tau_stride,
@@ -1851,7 +1693,7 @@ int launch_tau_refine(const uint2 *cand, const uint32_t *seg_cnt, int nseg, int 
 			hipLaunchKernelGGL((select_wave_kernel<true, KW>), dim3((unsigned)ceil_div64(Q, 4)), dim3(256), lds, st, cand, seg_cnt, nseg, capg, Q, \
 							   (uint32_t)k, (float *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, tau, tau_stride, prefilter, (const int32_t *)nullptr); \
 		} while (0)
-		if (k <= WSEL_K && !stream_select_small()) LAUNCH_WTAU(128);
+		if (k <= WSEL_K) LAUNCH_WTAU(128);
 		else {  // streaming radix select (select_stream.hpp): 1 KB of LDS per wave
 			constexpr int lds = 4 * StreamSelLayout::BYTES;
 			hipLaunchKernelGGL((select_stream_kernel<true, 2>), dim3((unsigned)ceil_div64(Q, 4)), dim3(256), lds, st, cand, seg_cnt, nseg, capg, Q,
@@ -1905,7 +1747,7 @@ int launch_select(const FusedPlan &P, int nseg, const SweepStages &stages, const
 			hipLaunchKernelGGL((select_stream_kernel<false, EE>), dim3((unsigned)ceil_div64(Q, 4)), dim3(256), lds, st, cand, seg_cnt, nseg, P.capg, Q, \
 							   (uint32_t)k, out_val, out_idx, hc, hl, const_cast<float *>(tau), tau_stride, (P.n_stages > 1 || P.ladder) ? 1 : 0, remap); \
 		} while (0)
-		if (k <= WSEL_K) { if (stream_select_small()) LAUNCH_SSEL(2); else LAUNCH_WSEL(128); }
+		if (k <= WSEL_K) { if (STREAM_SELECT_SMALL) LAUNCH_SSEL(2); else LAUNCH_WSEL(128); }
 		else if (k <= 256) LAUNCH_SSEL(4);
 		else if (k <= 512) LAUNCH_SSEL(8);
 		else LAUNCH_SSEL(16);
@@ -1935,9 +1777,6 @@ int launch_threshold(const FusedPlan &P, const float *gmax, int64_t Q, int k, un
 	return anncur_rowwise_topk(gmax, ANNCUR_F32, Q, P.n_groups, P.n_groups, k, tval, (int32_t *)(ws + P.off_tidx), st);
 }
 
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-unsigned long long *g_stamps = nullptr;  // diagnostic build: the last sweep launch's per-workgroup {cycles, 100 MHz ticks}
-#endif
 
 // ------------------------------------------------------------------ a8: the exact scan co-scheduled with the retrieval (anncur_eval_topk)
 // The retrieval is a chain of MFMA-bound sweep launches with latency-bound launches in between (threshold, refinement, select): one
@@ -2037,31 +1876,12 @@ int launch_fused(const FusedPlan &P, const void *X, int64_t ldx, const void *Et,
 	p.chunk_tiles = 0; p.n_chunks = 0; p.chunk_ctr = nullptr; p.chunk_owner = nullptr;
 	p.nfb = (uint32_t *)ws;
 	p.ring_stagger = 0; p.ring_spin_sleep = 1;
-	if (const char *dbg = knob("ANNCUR_DEBUG_RING_STAGGER")) p.ring_stagger = atoi(dbg);
-	if (const char *dbg = knob("ANNCUR_DEBUG_RING_SLEEP")) p.ring_spin_sleep = atoi(dbg);
 	p.nseg = P.lg * P.S;
 	p.prio_mode = 0;
-	if (const char *dbg = knob("ANNCUR_DEBUG_PRIO")) p.prio_mode = atoi(dbg);
 	p.ladder_on = P.ladder ? 1 : 0; p.ladder_k = (uint32_t)k; p.ladder_mask = (uint32_t)(LADDER_PERIOD - 1);
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	if (const char *dbg = getenv("ANNCUR_DEBUG_LADDER_PERIOD")) { int v = atoi(dbg); if (v >= 1 && (v & (v - 1)) == 0) p.ladder_mask = (uint32_t)(v - 1); }
-#endif
 	p.ladder = (const float *)(ws + P.off_lvl); p.ladder_cnt = (uint32_t *)(ws + P.off_lcnt); p.tau_final = (float *)(ws + P.off_tau2);
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	if (getenv("ANNCUR_DEBUG_STAMPS")) {
-		if (!g_stamps) {
-			ANNCUR_HIP_OK(hipMalloc((void **)&g_stamps, 13 * 8192 * sizeof(unsigned long long)));
-			ANNCUR_HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(d_sweep_stamps), &g_stamps, sizeof(g_stamps)));
-		}
-		ANNCUR_HIP_OK(hipMemsetAsync(g_stamps, 0, 13 * 8192 * sizeof(unsigned long long), st));
-	}
-#endif
-#ifdef ANNCUR_TIMING_EXPERIMENTS  // (the -DANNCUR_TIMING_EXPERIMENTS build of scripts/fused_microbench.py only: results become wrong)
-	{ const char *dbg = getenv("ANNCUR_DEBUG_TAU_BIAS"); p.tau_bias = dbg ? (float)atof(dbg) : 0.f; }
-	if (getenv("ANNCUR_DEBUG_NOSTORE")) { p.capg = 0; item_ids = nullptr; }  // every candidate is dropped at the store (the select then reads slots nobody wrote: no id map through them)
-#endif
 
-	const int chunk = (P.chunk > 0 && (Cfg::QT == 2 || P.bodyq1)) ? P.chunk : 0;   // (the one-sub-tile bodies with per-lane rings keep static shares)
+	const int chunk = (P.chunk > 0 && (Cfg::QT == 2 || P.bodyq16)) ? P.chunk : 0;   // (the one-sub-tile bodies with per-lane rings keep static shares)
 	const int owner_stride = P.n_rb * (P.n_tiles / (chunk > 0 ? chunk : P.n_tiles) + 2);
 	ANNCUR_HIP_OK(hipMemsetAsync(ws, 0, (chunk > 0 || P.ladder) ? P.off_gmax : 256, st));   // header (+ the stages' ticket counters, the ladder's counter words)
 	EV(0);
@@ -2091,8 +1911,8 @@ int launch_fused(const FusedPlan &P, const void *X, int64_t ldx, const void *Et,
 	// the survivors crowd into the leading tiles, all the workgroups of a stage run at once, and with contiguous ranges the stage took
 	// as long as its FIRST split (cfg2: the first stage, 22 % of the tiles, 0.236 ms against 0.306 ms for the other 78 %).
 	// (score16_kernel keeps contiguous ranges)
-	const int tile_step = (!P.body16 && !P.bodyq1 && !P.bodyef && P.S > 1 && chunk == 0 && !contiguous_splits()) ? P.S : 1;
-	p.n_wg = P.n_rb_s * P.S;
+	const int tile_step = (!P.body16 && !P.bodyq16 && !P.bodyef && P.S > 1 && chunk == 0) ? P.S : 1;
+	p.n_wg = P.n_rb * P.S;
 	if ((rc = anncur_ensure_dyn_lds((const void *)score_kernel<KP, 1, 16, false, false, QTV>, Cfg::LDS_BYTES)) != ANNCUR_OK) return rc;
 	for (int stg = 0, prev = 0; stg < P.n_stages; prev = P.stage_end[stg], ++stg) {
 		EV(5 + 2 * stg);
@@ -2103,32 +1923,17 @@ int launch_fused(const FusedPlan &P, const void *X, int64_t ldx, const void *Et,
 			// (row-block-major work ids -- the workgroups of a row block on ONE XCD -- were measured for the ticket schedule, round 3, one box:
 			//  cfg4 shape sweep 5.13 -> 6.28 ms and L2-miss traffic 9.0 -> 13.0 GB per launch, cfg2 0.451 -> 0.480 ms: split-major stays)
 			p.rb_major = 0;
-			if (const char *dbg = knob("ANNCUR_DEBUG_RB_MAJOR")) p.rb_major = atoi(dbg);
 			p.chunk_tiles = chunk; p.n_chunks = (p.tile_end - p.tile_begin + chunk - 1) / chunk;
 			// XCD-sliced tickets: the wave-queue bodies (Kp = 512: the shape whose sweep was close to the fabric's bandwidth; Kp <= 256: traffic only); [row block][slice] counters
 			// (Kp <= 256: measured at cfg2, one process, interleaved -- sweep launches 0.5030 ms sliced vs 0.4914 unsliced, bare loops level:
 			//  there the fabric is nowhere near its limit and the steals' blocking atomics cost more than the traffic they save (328 -> 180 MB
-			//  per launch); the score16 body keeps the code path (ANNCUR_DEBUG_SLICED=2 in the experiments build) but runs unsliced)
-			p.sliced = (P.bodyq1 || P.bodyq16) ? 1 : 0;
-			if (const char *dbg = knob("ANNCUR_DEBUG_SLICED")) p.sliced = (atoi(dbg) == 2 && P.body16 && !P.ring16) ? 1 : (p.sliced && atoi(dbg) != 0);
+			//  per launch); the score16 body keeps the code path but runs unsliced)
+			p.sliced = P.bodyq16 ? 1 : 0;
 			p.chunks_per_slice = (p.n_chunks + N_SLICES - 1) / N_SLICES;
 			p.chunk_ctr = (uint32_t *)(ws + P.off_ctr) + (size_t)stg * P.n_rb * N_SLICES;
 			p.chunk_owner = (uint8_t *)(ws + P.off_owner) + (size_t)stg * owner_stride;
 		}
 		bool launched = false;
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-		{ const char *dbg = getenv("ANNCUR_DEBUG_STAMP_STAGE"); p.debug_stamp = dbg ? (atoi(dbg) == stg) : (stg == P.n_stages - 1); }  // which launch leaves its stamps
-		{ const char *dbg = getenv("ANNCUR_DEBUG_FLUSH_TILES"); if (dbg) p.flush_tiles = atoi(dbg); }
-		if (getenv("ANNCUR_DEBUG_GEMM_NOSYNC")) {  // MFMA + LDS fragment reads, no staging, no barriers
-			if ((rc = anncur_ensure_dyn_lds((const void *)score_kernel<KP, 3, 16, false, false, QTV>, Cfg::LDS_BYTES)) != ANNCUR_OK) return rc;
-			hipLaunchKernelGGL((score_kernel<KP, 3, 16, false, false, QTV>), dim3(p.n_wg), dim3(256), Cfg::LDS_BYTES, st, p);
-			launched = true;
-		} else if (getenv("ANNCUR_DEBUG_GEMM_ONLY")) {  // no candidates are produced
-			if ((rc = anncur_ensure_dyn_lds((const void *)score_kernel<KP, 2, 16, false, false, QTV>, Cfg::LDS_BYTES)) != ANNCUR_OK) return rc;
-			hipLaunchKernelGGL((score_kernel<KP, 2, 16, false, false, QTV>), dim3(p.n_wg), dim3(256), Cfg::LDS_BYTES, st, p);
-			launched = true;
-		}
-#endif
 		if constexpr (KP <= 256 && QTV == 2) {  // anncur_eval_fused: candidates + error sums in one pass (score_evalf.hpp)
 			if (!launched && P.bodyef) {
 				if (!ea) { anncur_set_error("launch_fused: evalf plan without the exact matrix"); return ANNCUR_E_INVALID; }
@@ -2137,42 +1942,13 @@ int launch_fused(const FusedPlan &P, const void *X, int64_t ldx, const void *Et,
 				launched = true;
 			}
 		}
-		if constexpr (KP == 512) {  // Kp = 512 with the wave-level queue and tickets (score_q1.hpp)
+		if constexpr (KP == 512) {  // Kp = 512 with the wave-level queue and tickets (score_q16.hpp)
 			if (!launched && P.bodyq16) {
-				if ((rc = anncur_ensure_dyn_lds((const void *)scoreq16_kernel<KP>, FusedQ1Cfg<KP>::LDS_BYTES)) != ANNCUR_OK) return rc;
-				hipLaunchKernelGGL((scoreq16_kernel<KP>), dim3(p.n_wg), dim3(256), FusedQ1Cfg<KP>::LDS_BYTES, st, p);
-				launched = true;
-			}
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-			if (!launched && P.bodyq1) {
-				if ((rc = anncur_ensure_dyn_lds((const void *)scoreq1_kernel<KP>, FusedQ1Cfg<KP>::LDS_BYTES)) != ANNCUR_OK) return rc;
-				hipLaunchKernelGGL((scoreq1_kernel<KP>), dim3(p.n_wg), dim3(256), FusedQ1Cfg<KP>::LDS_BYTES, st, p);
-				launched = true;
-			}
-#endif
-		}
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-		if constexpr (KP >= 128 && KP <= 256 && QTV == 2) {  // 16x16x32 sweep, 8-wave workgroups with the flag-synchronised tile ring (score16r.hpp)
-			if (!launched && P.ring16) {
-				if ((rc = anncur_ensure_dyn_lds((const void *)score16r_kernel<KP>, Ring16Cfg<KP>::LDS_BYTES)) != ANNCUR_OK) return rc;
-				hipLaunchKernelGGL((score16r_kernel<KP>), dim3(p.n_wg), dim3(512), Ring16Cfg<KP>::LDS_BYTES, st, p);
+				if ((rc = anncur_ensure_dyn_lds((const void *)scoreq16_kernel<KP>, FusedQ16Cfg<KP>::LDS_BYTES)) != ANNCUR_OK) return rc;
+				hipLaunchKernelGGL((scoreq16_kernel<KP>), dim3(p.n_wg), dim3(256), FusedQ16Cfg<KP>::LDS_BYTES, st, p);
 				launched = true;
 			}
 		}
-#endif
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-		// score16_kernel<Kp, 8>: the barrier body in 8-wave workgroups (512 queries, one per CU: half the DMA pieces per wave).  Measured (round 4,
-		// one process): sweep launches 0.5125 vs 0.4874 ms, bare 0.436 vs 0.395 -- with both waves of a SIMD in ONE workgroup the partners run in
-		// lockstep through DMA issue, barrier and MFMA section; two independent 4-wave workgroups per CU are 10 % faster.  Experiments build only.
-		if constexpr (KP >= 128 && KP <= 256 && QTV == 2) {
-			if (!launched && P.body16 && P.wg8) {
-				constexpr int lds8 = Fused16Cfg<KP, 8>::LDS_BYTES;
-				if ((rc = anncur_ensure_dyn_lds((const void *)score16_kernel<KP, 8>, lds8)) != ANNCUR_OK) return rc;
-				hipLaunchKernelGGL((score16_kernel<KP, 8>), dim3(p.n_wg), dim3(512), lds8, st, p);
-				launched = true;
-			}
-		}
-#endif
 		if constexpr (KP <= 256 && QTV == 2) {  // 16x16x32 sweep (score16.hpp): one segment per (query, item split)
 			if (!launched && P.body16) {
 				if ((rc = anncur_ensure_dyn_lds((const void *)score16_kernel<KP>, Fused16Cfg<KP>::LDS_BYTES)) != ANNCUR_OK) return rc;
@@ -2187,27 +1963,6 @@ int launch_fused(const FusedPlan &P, const void *X, int64_t ldx, const void *Et,
 				launched = true;
 			}
 		}
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-		if constexpr (KP == 512) {
-			if (!launched && getenv("ANNCUR_DEBUG_PLAIN512")) {  // the sweep without the cross-tile software pipeline
-				if ((rc = anncur_ensure_dyn_lds((const void *)score_kernel<KP, 1, 16, false, true, QTV>, Cfg::LDS_BYTES)) != ANNCUR_OK) return rc;
-				hipLaunchKernelGGL((score_kernel<KP, 1, 16, false, true, QTV>), dim3(p.n_wg), dim3(256), Cfg::LDS_BYTES, st, p);
-				launched = true;
-			}
-		}
-		if constexpr (Cfg::QT == 2) {
-			if (!launched && getenv("ANNCUR_DEBUG_INLINE_HIT")) {
-				if ((rc = anncur_ensure_dyn_lds((const void *)score_kernel<KP, 1, 16, false, true, QTV>, Cfg::LDS_BYTES)) != ANNCUR_OK) return rc;
-				hipLaunchKernelGGL((score_kernel<KP, 1, 16, false, true, QTV>), dim3(p.n_wg), dim3(256), Cfg::LDS_BYTES, st, p);
-				launched = true;
-			}
-		}
-		if (!launched && getenv("ANNCUR_DEBUG_ONE_WG")) {  // padded LDS request: a second workgroup does not fit on the CU
-			if ((rc = anncur_ensure_dyn_lds((const void *)score_kernel<KP, 1, 16, false, false, QTV>, 84 * 1024)) != ANNCUR_OK) return rc;
-			hipLaunchKernelGGL((score_kernel<KP, 1, 16, false, false, QTV>), dim3(p.n_wg), dim3(256), 84 * 1024, st, p);
-			launched = true;
-		}
-#endif
 		if (!launched) hipLaunchKernelGGL((score_kernel<KP, 1, 16, false, false, QTV>), dim3(p.n_wg), dim3(256), Cfg::LDS_BYTES, st, p);
 		ANNCUR_LAUNCH_OK();
 		EV(6 + 2 * stg);
@@ -2224,7 +1979,7 @@ int launch_fused(const FusedPlan &P, const void *X, int64_t ldx, const void *Et,
 	SweepStages stages{};
 	stages.n = P.n_stages;
 	stages.stride = tile_step;
-	stages.chunk = chunk; stages.bq = P.BQ_s;
+	stages.chunk = chunk; stages.bq = P.BQ;
 	for (int g = 0, prev = 0; g < P.n_stages; prev = P.stage_end[g], ++g) {
 		stages.begin[g] = prev; stages.end[g] = P.stage_end[g]; stages.tps[g] = P.stage_tps[g];
 		stages.n_chunks[g] = chunk > 0 ? (P.stage_end[g] - prev + chunk - 1) / chunk : 0;
@@ -2307,9 +2062,6 @@ int launch_wide(const FusedPlan &P, const void *X, int64_t ldx, const void *Et, 
 	p.gmax = (float *)(ws + P.off_gmax); p.n_groups = P.n_groups;
 	p.cand = (uint2 *)(ws + P.off_cand); p.seg_cnt = (uint32_t *)(ws + P.off_segcnt); p.capg = P.capg;
 	p.tau_bias = 0.f;
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	{ const char *dbg = getenv("ANNCUR_DEBUG_TAU_BIAS"); p.tau_bias = dbg ? (float)atof(dbg) : 0.f; }
-#endif
 	int rc;
 	ANNCUR_HIP_OK(hipMemsetAsync(ws, 0, 256, st));
 	EV(0);
@@ -2356,12 +2108,7 @@ int launch_wide(const FusedPlan &P, const void *X, int64_t ldx, const void *Et, 
 		stages.end[g] = P.stage_end[g] * u < n_tiles32 ? P.stage_end[g] * u : n_tiles32;
 		stages.tps[g] = P.stage_tps[g] * u;
 	}
-#if defined(ANNCUR_V_WIDE_NOREAD) || defined(ANNCUR_V_WIDE_MFMAONLY) || defined(ANNCUR_V_WIDE_NODMA_NOREAD) || defined(ANNCUR_V_WIDE_NODMA) || defined(ANNCUR_V_WIDE_NOBAR) || defined(ANNCUR_V_WIDE_NOFILTER) || defined(ANNCUR_V_WIDE_BASE)
-	// (ablation builds of wide_kernel: the candidates are garbage, the select -- which would repair every query from scratch -- is skipped)
-	(void)item_ids; (void)out_val; (void)out_idx;
-#else
 	if ((rc = launch_select(P, 4 * P.S, stages, p.cand, p.seg_cnt, p.X, ldx, p.Et, Q, I, KP, k, out_val, out_idx, ws, p.tau, p.tau_stride, st, item_ids)) != ANNCUR_OK) return rc;
-#endif
 	EV(4);
 	return ANNCUR_OK;
 }
@@ -2369,15 +2116,11 @@ int launch_wide(const FusedPlan &P, const void *X, int64_t ldx, const void *Et, 
 
 FusedPlan plan_any(int64_t Q, int64_t I, int KP, int k, int flags = 0) {
 	const bool leading = (flags & ANNCUR_TOPK_LEADING_SAMPLE) != 0, mfma16 = (flags & ANNCUR_TOPK_MFMA16) != 0, qt1 = (flags & ANNCUR_TOPK_QT1) != 0;
-	return wide_kp(KP) ? plan_wide(Q, I, KP, k, leading) : plan_fused(Q, I, KP, k, leading, mfma16 && !qt1, qt1, (flags & ANNCUR_TOPK_MFMA32) != 0, (flags & ANNCUR_TOPK_RING) != 0,
-																	  false, (flags & ANNCUR_TOPK_STAGED) != 0);
+	return wide_kp(KP) ? plan_wide(Q, I, KP, k, leading) : plan_fused(Q, I, KP, k, leading, mfma16 && !qt1, qt1, (flags & ANNCUR_TOPK_MFMA32) != 0, false,
+																	  (flags & ANNCUR_TOPK_STAGED) != 0);
 }
 bool ring_flag_ok(int flags) {
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	(void)flags; return true;
-#else
 	return (flags & ANNCUR_TOPK_RING) == 0;
-#endif
 }
 constexpr int TOPK_FLAGS = ANNCUR_TOPK_LEADING_SAMPLE | ANNCUR_TOPK_MFMA16 | ANNCUR_TOPK_QT1 | ANNCUR_TOPK_MFMA32 | ANNCUR_TOPK_RING | ANNCUR_TOPK_STAGED;
 
@@ -2404,9 +2147,8 @@ static int score_topk_impl(const void *X, int64_t ldx, const void *Et, int64_t l
 						   int32_t k, float *out_val, int32_t *out_idx, void *workspace, size_t workspace_bytes,
 						   void *stream, hipEvent_t *ev, int32_t flags = 0, const int32_t *item_ids = nullptr, CoScan *co = nullptr, const EvalArgs *ea = nullptr) {
 	ANNCUR_REQUIRE((flags & ~TOPK_FLAGS) == 0, ANNCUR_E_INVALID, "score_topk: unknown flags 0x%x", flags);
-	ANNCUR_REQUIRE(ring_flag_ok(flags), ANNCUR_E_UNSUPPORTED, "score_topk: ANNCUR_TOPK_RING (the tile-ring sweep body) is compiled into the experiments library only "
-				   "(make -C anncur_amd/csrc experiments; ANNCUR_LIB=.../libanncur_hip_exp.so): measured slower than the default body");
-	const FusedPlan P = ea ? plan_fused(Q, I, Kp, k, false, false, false, false, false, true) : plan_any(Q, I, Kp, k, flags);
+	ANNCUR_REQUIRE(ring_flag_ok(flags), ANNCUR_E_UNSUPPORTED, "score_topk: ANNCUR_TOPK_RING (the tile-ring sweep body) is retired: measured slower than the default body");
+	const FusedPlan P = ea ? plan_fused(Q, I, Kp, k, false, false, false, false, true) : plan_any(Q, I, Kp, k, flags);
 	ANNCUR_REQUIRE(P.ok, ANNCUR_E_UNSUPPORTED,
 				   "score_topk: (Q=%lld, I=%lld, Kp=%d, k=%d) is outside the fused path (Kp in {64,128,256,512} or a multiple of 128 up to %d, "
 				   "1<=k<=%d, I large enough for a sampled threshold); use anncur_gemm + anncur_rowwise_topk",
@@ -2471,7 +2213,7 @@ extern "C" int anncur_eval_topk(const void *A, int a_dtype, int64_t lda, int32_t
  * norm_sq[q] = sum_i A^2 (score_evalf.hpp).  Operands as anncur_score_topk (Et in ITEM order) + the exact matrix as
  * anncur_approx_error_packed's lds route takes it (bf16, 16-byte aligned rows). */
 extern "C" size_t anncur_eval_fused_workspace_bytes(int64_t Q, int64_t I, int32_t Kp, int32_t k) {
-	const FusedPlan P = plan_fused(Q, I, Kp, k, false, false, false, false, false, true);
+	const FusedPlan P = plan_fused(Q, I, Kp, k, false, false, false, false, true);
 	return P.ok ? P.total : 0;
 }
 
@@ -2537,19 +2279,6 @@ extern "C" int anncur_score_topk_timed(const void *X, int64_t ldx, const void *E
 	return rc;
 }
 
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-/* experiments build only (scripts/r4/timeline_probe.py): the same launches with the CALLER's 11 events recorded at the stage boundaries
- * (0 start, 1 after the prepass, 2 after the threshold, 5 + 2 g / 6 + 2 g around sweep launch g, 3 after the last stage, 4 after the
- * select) and no synchronisation -- for a timeline of several calls in flight on several streams against one base event */
-extern "C" int anncur_score_topk_events(const void *X, int64_t ldx, const void *Et, int64_t lde, int64_t Q, int64_t I, int32_t Kp,
-										int32_t k, float *out_val, int32_t *out_idx, void *workspace, size_t workspace_bytes,
-										int32_t flags, const int32_t *item_ids, void *stream, void *const *events11) {
-	ANNCUR_REQUIRE(events11, ANNCUR_E_INVALID, "score_topk_events: events is null");
-	hipEvent_t ev[11];
-	for (int i = 0; i < 11; ++i) ev[i] = (hipEvent_t)events11[i];
-	return score_topk_impl(X, ldx, Et, lde, Q, I, Kp, k, out_val, out_idx, workspace, workspace_bytes, stream, ev, flags, item_ids);
-}
-#endif
 
 /* plan introspection for benchmarks / DESIGN.md: n_sample_tiles, n_tiles, S, capg, group (tiles of 32 items, or of 256 for Kp > 512) */
 extern "C" int anncur_score_topk_plan(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t *out5) {
@@ -2561,13 +2290,13 @@ extern "C" int anncur_score_topk_plan(int64_t Q, int64_t I, int32_t Kp, int32_t 
 
 /* the same for the flags of anncur_score_topk_ex: out[0 .. n_out) = {sample tiles, item tiles, S, segment capacity, group, segments per
  * query and item split (2: 32x32x16 sweep, 1: 16x16x32 sweep, 4: wide kernel), 32-query sub-tiles per wave, sweep stages,
- * stage_end[3], stage body[3] (0: 32x32x16 with the ballot filter, 1: with the exec-mask filter, 2: 16x16x32, 3 / 4: Kp = 512 with the
- * wave-level queue on 32x32x16 / 16x16x32 MFMAs, 5: 16x16x32 in 8-wave workgroups with the flag-synchronised tile ring), ring drain period[3],
+ * stage_end[3], stage body[3] (0: 32x32x16 with the ballot filter, 1: with the exec-mask filter, 2: 16x16x32, 4: Kp = 512 with the
+ * wave-level queue on 16x16x32 MFMAs), ring drain period[3],
  * threshold ladder (1: the sweep raises its thresholds in-launch, score16.hpp; 0: staged), rank of the ladder's top level} --
  * what a test needs to see that a variant flag was honoured */
 extern "C" int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, int32_t *out, int32_t n_out) {
 	ANNCUR_REQUIRE((flags & ~TOPK_FLAGS) == 0, ANNCUR_E_INVALID, "score_topk_plan_ex: unknown flags 0x%x", flags);
-	ANNCUR_REQUIRE(ring_flag_ok(flags), ANNCUR_E_UNSUPPORTED, "score_topk_plan_ex: ANNCUR_TOPK_RING is compiled into the experiments library only");
+	ANNCUR_REQUIRE(ring_flag_ok(flags), ANNCUR_E_UNSUPPORTED, "score_topk_plan_ex: ANNCUR_TOPK_RING (the tile-ring sweep body) is retired");
 	const FusedPlan P = plan_any(Q, I, Kp, k, flags);
 	ANNCUR_REQUIRE(P.ok && out && n_out >= 0, ANNCUR_E_UNSUPPORTED, "score_topk_plan_ex: unsupported shape");
 	const bool wide = wide_kp(Kp);
@@ -2575,7 +2304,7 @@ extern "C" int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32
 	v[17] = (!wide && P.ladder) ? 1 : 0; v[18] = (!wide && P.ladder) ? P.ladder_k2 : 0;
 	for (int g = 0; g < 3; ++g) {
 		const bool on = g < P.n_stages;
-		v[8 + g] = on ? P.stage_end[g] : 0; v[11 + g] = on ? (!wide && P.bodyef ? 6 : !wide && P.ring16 ? 5 : !wide && P.body16 ? 2 : (!wide && P.bodyq16 ? 4 : (!wide && P.bodyq1 ? 3 : P.stage_pred[g]))) : 0; v[14 + g] = on ? P.stage_flush[g] : 0;
+		v[8 + g] = on ? P.stage_end[g] : 0; v[11 + g] = on ? (wide ? P.stage_pred[g] : P.bodyef ? 6 : P.body16 ? 2 : P.bodyq16 ? 4 : P.stage_pred[g]) : 0; v[14 + g] = on ? P.stage_flush[g] : 0;
 	}
 	for (int i = 0; i < n_out && i < 19; ++i) out[i] = v[i];
 	return ANNCUR_OK;
@@ -2632,7 +2361,6 @@ extern "C" int anncur_approx_error_packed(const void *X, int64_t ldx, const void
 	p.tiles_per_split = (p.n_tiles + S - 1) / S;
 	S = (p.n_tiles + p.tiles_per_split - 1) / p.tiles_per_split;
 	p.n_wg = n_rb * S;
-	if (const char *dbg = knob("ANNCUR_DEBUG_ERR_MODE")) p.ring_stagger = atoi(dbg);
 #define LAUNCH_ERR(KPV, TA)                                                                                                   \
 	hipLaunchKernelGGL((error_kernel<KPV, TA>), dim3(p.n_wg), dim3(256), 2 * FusedCfg<KPV>::TILE_BYTES, st, p, (const TA *)A, lda, err_sq, norm_sq)
 #define LAUNCH_ERR_K(TA)                                                                                                      \
@@ -2668,86 +2396,7 @@ extern "C" int anncur_approx_error_packed(const void *X, int64_t ldx, const void
 	return ANNCUR_OK;
 }
 
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-/* diagnostic build only (not in include/anncur_hip.h): median in-kernel clock in GHz over the workgroups of the last sweep launch
- * that ran with ANNCUR_DEBUG_STAMPS set (s_memtime ticks per s_memrealtime tick x 100 MHz), and the median loop duration in us. */
-extern "C" int anncur_debug_read_stamps(double *clock_ghz, double *loop_us, int *n_wg) {
-	if (!g_stamps) return ANNCUR_E_INVALID;
-	static unsigned long long h[2 * 8192];
-	if (hipMemcpy(h, g_stamps, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return ANNCUR_E_HIP;
-	double r[8192], u[8192];
-	int n = 0;
-	for (int i = 0; i < 8192; ++i)
-		if (h[2 * i + 1] > 0) { r[n] = (double)h[2 * i] / (double)h[2 * i + 1] * 0.1; u[n] = (double)h[2 * i + 1] / 100.0; ++n; }
-	if (n == 0) return ANNCUR_E_INVALID;
-	for (int i = 1; i < n; ++i) { double x = r[i], y = u[i]; int j = i - 1; while (j >= 0 && r[j] > x) { r[j + 1] = r[j]; --j; } r[j + 1] = x; j = i - 1; while (j >= 0 && u[j] > y) { u[j + 1] = u[j]; --j; } u[j + 1] = y; }
-	*clock_ghz = r[n / 2]; *loop_us = u[n / 2]; *n_wg = n;
-	return ANNCUR_OK;
-}
-#endif
 
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-/* diagnostic build only: arm (n_wg > 0) or read the phase stamps of select_wave_kernel.  out[3] = median cycles of the phases
- * (prologue, candidate load loop, final compaction / sort) over the workgroups' first waves. */
-extern "C" int anncur_debug_sel_stamps(int arm, double *out) {
-	static unsigned long long *buf = nullptr;
-	const int N = 4096;
-	if (!buf) { if (hipMalloc((void **)&buf, 8 * N * sizeof(unsigned long long)) != hipSuccess) return ANNCUR_E_HIP; }
-	if (arm) {
-		if (hipMemset(buf, 0, 8 * N * sizeof(unsigned long long)) != hipSuccess) return ANNCUR_E_HIP;
-		unsigned long long *v = arm > 0 ? buf : nullptr;
-		return hipMemcpyToSymbol(HIP_SYMBOL(d_sel_stamps), &v, sizeof(v)) == hipSuccess ? ANNCUR_OK : ANNCUR_E_HIP;
-	}
-	static unsigned long long h[8 * 4096];
-	if (hipMemcpy(h, buf, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return ANNCUR_E_HIP;
-	// out[0..2]: prologue, load loop, finish; out[3..4] (select_wave_kernel only): first batch's segment search, its loads' latency
-	static const int from[5] = {0, 1, 2, 1, 4}, to[5] = {1, 2, 3, 4, 5};
-	static double ph[4096];
-	for (int j = 0; j < 5; ++j) {
-		int n = 0;
-		for (int i = 0; i < N; ++i)
-			if (h[8 * i + 3] > h[8 * i] && h[8 * i + to[j]] > h[8 * i + from[j]]) ph[n++] = (double)(h[8 * i + to[j]] - h[8 * i + from[j]]);
-		for (int i = 1; i < n; ++i) { double x = ph[i]; int t = i - 1; while (t >= 0 && ph[t] > x) { ph[t + 1] = ph[t]; --t; } ph[t + 1] = x; }
-		out[j] = n ? ph[n / 2] : 0.0;
-	}
-	return ANNCUR_OK;
-}
-#endif
 
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-/* diagnostic build only: timeline of the last sweep launch in us relative to the first workgroup's entry: out = {entry p50, entry max,
- * loop start p50, loop start max, loop end p50, loop end max} */
-extern "C" int anncur_debug_sweep_timeline(double *out) {
-	if (!g_stamps) return ANNCUR_E_INVALID;
-	static unsigned long long h[5 * 8192];
-	if (hipMemcpy(h, g_stamps, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return ANNCUR_E_HIP;
-	static double v[3][8192];
-	int n = 0; unsigned long long t0 = ~0ull;
-	for (int i = 0; i < 8192; ++i) if (h[2 * 8192 + 3 * i + 2] > 0 && h[2 * 8192 + 3 * i] < t0) t0 = h[2 * 8192 + 3 * i];
-	for (int i = 0; i < 8192; ++i)
-		if (h[2 * 8192 + 3 * i + 2] > 0) { for (int j = 0; j < 3; ++j) v[j][n] = (double)(h[2 * 8192 + 3 * i + j] - t0) / 100.0; ++n; }
-	if (!n) return ANNCUR_E_INVALID;
-	for (int j = 0; j < 3; ++j) {
-		for (int i = 1; i < n; ++i) { double x = v[j][i]; int t = i - 1; while (t >= 0 && v[j][t] > x) { v[j][t + 1] = v[j][t]; --t; } v[j][t + 1] = x; }
-		out[2 * j] = v[j][n / 2]; out[2 * j + 1] = v[j][n - 1];
-	}
-	return ANNCUR_OK;
-}
-#endif
 
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-/* diagnostic build only: per-wave phase cycles of the stamped sweep launch (staggered Kp <= 256 body): out[8192 x 8], words 0..4 = cycles in
- * {ticket + DMA issue, ring drain, MFMA / filter section, vmcnt wait, barrier} */
-extern "C" int anncur_debug_sweep_phases(unsigned long long *out) {
-	if (!g_stamps) return ANNCUR_E_INVALID;
-	return hipMemcpy(out, g_stamps + 5 * 8192, 8 * 8192 * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess ? ANNCUR_OK : ANNCUR_E_HIP;
-}
-#endif
 
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-/* diagnostic build only: raw stamps of the last sweep launch, 5 x 8192 words ({cycles, ticks} x 8192, then {entry, loop start, loop end} x 8192) */
-extern "C" int anncur_debug_sweep_raw(unsigned long long *out) {
-	if (!g_stamps) return ANNCUR_E_INVALID;
-	return hipMemcpy(out, g_stamps, 5 * 8192 * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess ? ANNCUR_OK : ANNCUR_E_HIP;
-}
-#endif

@@ -1,17 +1,39 @@
-// Kp = 512 sweep on v_mfma_f32_16x16x32_bf16 (round 3): the body of score_q1.hpp (one candidate queue per wave, tickets, cross-tile
-// pipeline, 32 queries per wave, 80 KB of LDS) with the MFMA shape of score16.hpp -- the chip holds a higher clock on it at equal
-// cycles per flop.  A wave's 32 queries are two 16-query sub-tiles (qs), a 32-item tile two 16-item halves (ih); step s = 2 ks + ih of
-// a tile (32 steps) reads one A fragment (16 item rows x 32 k) and issues two MFMAs (qs = 0, 1); the previous tile's accumulator
-// (2 halves x 2 sub-tiles x 4 registers = 16 elements per lane) is filtered in the shadow, one element every second step.
+// Sweep kernel for Kp = 512 with the wave-level candidate queue and the dynamic tile schedule (round 3).  The Kp = 512 body of
+// score_kernel (one 32-query sub-tile per wave -- the query operand alone takes 128 VGPRs --, cross-tile software pipeline: while the
+// MFMA chain of tile j runs, the filter of tile j-1's accumulator is issued in its shadow) uses exactly 80 KB of LDS per workgroup, 64 KB
+// of tile buffers and 16 KB of per-lane candidate rings: no room for the two ticket words of the dynamic schedule (16 bytes more halved
+// the occupancy: -20 %).  With the candidates in ONE queue per wave (score16.hpp: WaveQueue, wq_drain, filter16_one) the queues take
+// 14 KB, the per-query counters 0.5 KB, and the tickets fit.
+// MFMA shape: v_mfma_f32_16x16x32_bf16, as in score16.hpp -- the chip holds a higher clock on it at equal cycles per flop (the same body
+// on 32x32x16 MFMAs was retired in round 5).  A wave's 32 queries are two 16-query sub-tiles (qs), a 32-item tile two 16-item halves
+// (ih); step s = 2 ks + ih of a tile (32 steps) reads one A fragment (16 item rows x 32 k) and issues two MFMAs (qs = 0, 1); the
+// previous tile's accumulator (2 halves x 2 sub-tiles x 4 registers = 16 elements per lane) is filtered in the shadow, one element
+// every second step.
 // C/D layout: col = lane & 15 = query of the sub-tile, row = 4 (lane >> 4) + reg = item of the half.
 // Fragment address of step s: row = 16 ih + (lane & 15), chunk = 4 ks + (lane >> 4); the swizzle XORs the chunk's low four bits with
 // lane & 15, and chunk = 16 (ks >> 2) + 4 (ks & 3) + (lane >> 4): address = aoff8[s & 7] + (s >> 3) * 256.
 #pragma once
 
+template <int KP>
+struct FusedQ16Cfg {
+	static constexpr int KSTEPS = KP / 16;
+	static constexpr int CPR = KP / 8;
+	static constexpr int TILE_BYTES = TILE_I * KP * 2;
+	static constexpr int QCAP = 448;                 // entries of a wave's queue
+	static constexpr int DRAIN_AT = 128;             // a step drains at its head from this fill on
+	static constexpr int CHECK_PUSHES = 4;           // the tile function checks the fill every 4 pushes (64 entries each at most)
+	static constexpr int QUEUE_OFF = 2 * TILE_BYTES;
+	static constexpr int CNT_OFF = QUEUE_OFF + 4 * QCAP * 8;   // 128 per-query candidate counts of this item split
+	static constexpr int TICKET_OFF = CNT_OFF + 128 * 4;
+	static constexpr int LDS_BYTES = TICKET_OFF + 16;
+	static constexpr int BQ = 128;
+	static_assert(LDS_BYTES <= 80 * 1024, "two workgroups per CU");
+};
+
 template <int KP, int CUR>
 __device__ __forceinline__ void staggerq16_tile(const uint32_t (&aoff8)[8], const bf16x8 (&xb)[2][KP / 32], f32x4 (&acc)[2][2], const f32x4 (&accP)[2][2],
 												 float tau0, float tau1, uint32_t item0_prev, const WaveQueue &w, uint32_t &fill) {
-	using C = FusedQ1Cfg<KP>;
+	using C = FusedQ16Cfg<KP>;
 	constexpr int K = KP / 16, AR = 5, DIST = 3, OFF = CUR * C::TILE_BYTES;   // K steps = (k-step of 32, item half) pairs
 	static_assert(K == 32, "Kp = 512");
 	u32x4 ring[AR];
@@ -48,15 +70,11 @@ __device__ __forceinline__ void staggerq16_tile(const uint32_t (&aoff8)[8], cons
 
 template <int KP>
 __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
-	using C = FusedQ1Cfg<KP>;
+	using C = FusedQ16Cfg<KP>;
 	constexpr int KS32 = KP / 32, CPR = KP / 8;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const int c16 = lane & 15, g4 = lane >> 4;
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	unsigned long long st_entry = __builtin_amdgcn_s_memrealtime();   // (diagnostic build: scripts/inkernel_clock.py)
-	asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(st_entry)::"memory");
-#endif
 	const int wid = xcd_remap(blockIdx.x, p.n_wg);
 	const int n_rb = (int)((p.Q + C::BQ - 1) / C::BQ);
 	const int split = p.rb_major ? wid % p.S : wid / n_rb, rb = p.rb_major ? wid / p.S : wid - split * n_rb;
@@ -94,7 +112,7 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 	uint32_t fill = w.base;
 	if (lane < 32) {
 		const int64_t q = q_wave0 + lane;
-		lds_store_u32(w.cnt + (uint32_t)lane * 4u, (p.carry && q < p.Q) ? p.seg_cnt[q * p.nseg + split] : 0u);
+		lds_write_u32(w.cnt + (uint32_t)lane * 4u, (p.carry && q < p.Q) ? p.seg_cnt[q * p.nseg + split] : 0u);
 	}
 
 	// ---- tile schedule: tickets (see score_kernel), or a static contiguous share
@@ -119,8 +137,8 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 				if (c0 < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c0] = (uint8_t)split;
 				if (c1 < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c1] = (uint8_t)split;
 			}
-			lds_store_u32(ticket_slot + 8u, c0);   // (the prologue's pair sits in the third and fourth ticket word)
-			lds_store_u32(ticket_slot + 12u, c1);
+			lds_write_u32(ticket_slot + 8u, c0);   // (the prologue's pair sits in the third and fourth ticket word)
+			lds_write_u32(ticket_slot + 12u, c1);
 			__builtin_amdgcn_s_waitcnt(0xC07F);
 		}
 		__syncthreads();
@@ -172,7 +190,7 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 		if (crossed) {                                                                                                          \
 			if (tid == 0) {                                                                                                     \
 				if (p.sliced) ticket = slice_resolve(ticket, ctr_rb, p.n_chunks, p.chunks_per_slice, slice, tried);             \
-				lds_store_u32(ticket_slot, ticket);                                                                             \
+				lds_write_u32(ticket_slot, ticket);                                                                             \
 				if (p.chunk_owner && ticket < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + ticket] = (uint8_t)split; \
 				__builtin_amdgcn_s_waitcnt(0xC07F);                                                                             \
 			}                                                                                                                   \
@@ -182,10 +200,6 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 		__syncthreads();                                                                                                        \
 		t_cur = nx;                                                                                                             \
 	} while (0)
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	unsigned long long st_c0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-	asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(st_c0), "+s"(st_r0)::"memory");
-#endif
 	ANNCUR_PAD_HERE();
 	bool last_in_a = false;  // (uniform) which accumulator set holds the last tile
 	while (t_cur >= 0) {
@@ -196,15 +210,6 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 		last_in_a = false;
 	}
 #undef Q16_STEP
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	if (tid == 0 && d_sweep_stamps && p.debug_stamp && blockIdx.x < 8192) {
-		unsigned long long *stamps = d_sweep_stamps;
-		const unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
-		stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - st_c0;
-		stamps[2 * blockIdx.x + 1] = r1 - st_r0;
-		stamps[2 * 8192 + 3 * blockIdx.x] = st_entry; stamps[2 * 8192 + 3 * blockIdx.x + 1] = st_r0; stamps[2 * 8192 + 3 * blockIdx.x + 2] = r1;
-	}
-#endif
 	// drain: the last tile's accumulators (16 pushes, the fill checked every CHECK_PUSHES)
 	wq_drain(w, fill);
 #define Q16_LAST(ACC)                                                                                                           \

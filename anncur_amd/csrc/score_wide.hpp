@@ -35,7 +35,7 @@ struct WideParams {
 	const float *tau; int tau_stride;
 	uint2 *cand; uint32_t *seg_cnt; int capg;
 	int n_wg;
-	float tau_bias;  // 0 in production (ANNCUR_DEBUG_TAU_BIAS of the timing-experiment build: results become wrong)
+	float tau_bias;  // always 0 (read by wide_kernel: a tuning offset of the threshold, no longer set)
 };
 
 // work id -> (query block, item split).  Consecutive ids (= one XCD after xcd_remap) cover a compact rectangle of
@@ -159,13 +159,7 @@ __global__ __launch_bounds__(512, 2) void wide_kernel(const WideParams p) {
 
 		// One 64-wide k-tile = 4 k-steps of 6 fragment reads + 8 MFMAs.  The fragments of step s + 1 are requested before the MFMAs of step s
 		// (two register sets) and the MFMAs wait with lgkmcnt(6): the six reads just issued stay in flight.
-		// (ablation builds, `make variant V=WIDE_<what>`: results become wrong; scripts/r5/wide_ablation.sh)
-#if defined(ANNCUR_V_WIDE_NOREAD) || defined(ANNCUR_V_WIDE_MFMAONLY) || defined(ANNCUR_V_WIDE_NODMA_NOREAD)
-#define WIDE_LOAD(F, STAGE, s) do { if (kt == 0 && j == j_begin) { WIDE_LOAD_(F, STAGE, s); } } while (0)
-#else
-#define WIDE_LOAD(F, STAGE, s) WIDE_LOAD_(F, STAGE, s)
-#endif
-#define WIDE_LOAD_(F, STAGE, s)                                                                                   \
+#define WIDE_LOAD(F, STAGE, s)                                                                                    \
 		do {                                                                                                      \
 			_Pragma("unroll") for (int m = 0; m < 4; ++m) lds_read_frag_at(F.a[m], fa[STAGE][s], m * 4096);        \
 			_Pragma("unroll") for (int t = 0; t < 2; ++t) lds_read_frag_at(F.b[t], fb[STAGE][s], t * 4096);        \
@@ -181,25 +175,16 @@ __global__ __launch_bounds__(512, 2) void wide_kernel(const WideParams p) {
 		// The wave's DMA pieces of the next k-tile have landed, its fragment reads are done: raw barrier.
 		// (Tried and dropped: warming the XCD's L2 two k-tiles ahead with one 4-byte load per 128-byte line and thread, excluded
 		//  from the wait by a counted vmcnt: 907 vs 960 TFLOP/s at 10k x 100k x 1024 -- the loop is not waiting on misses.)
-#if defined(ANNCUR_V_WIDE_NOBAR) || defined(ANNCUR_V_WIDE_MFMAONLY)
-#define WIDE_SYNC() do { } while (0)
-#else
 #define WIDE_SYNC()                                                                                               \
 		do {                                                                                                      \
 			asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                           \
 			__builtin_amdgcn_s_barrier();                                                                         \
 			asm volatile("" ::: "memory");                                                                        \
 		} while (0)
-#endif
 		// DMA of the next k-tile: two of the wave's eight 1 KiB pieces per k-step, issued between the fragment reads and the MFMAs
 		// of the step (eight back-to-back issues at the head of the k-tile kept both waves of a SIMD off the matrix pipe together).
 		// Hand-placed (round 5): uniform 64-bit base in SGPRs + the lane's 32-bit offset, M0 from a scalar -- the builtin cost two 64-bit
 		// VALU adds and two v_readfirstlane per piece.
-#if defined(ANNCUR_V_WIDE_NODMA) || defined(ANNCUR_V_WIDE_MFMAONLY) || defined(ANNCUR_V_WIDE_NODMA_NOREAD)
-#define WIDE_NODMA_COND && false
-#else
-#define WIDE_NODMA_COND
-#endif
 #define WIDE_PIECE(BASE, OFF, TILE_OFF, i)                                                                        \
 		do {                                                                                                      \
 			const uint32_t m0v_ = lds0_u + (uint32_t)(TILE_OFF) + (uint32_t)(wave_u * 4 + (i)) * 1024u;            \
@@ -207,7 +192,7 @@ __global__ __launch_bounds__(512, 2) void wide_kernel(const WideParams p) {
 		} while (0)
 #define WIDE_DMA2(s)                                                                                              \
 		do {                                                                                                      \
-			if (den WIDE_NODMA_COND) {                                                                                            \
+			if (den) {                                                                                                            \
 				if ((s) < 2) { WIDE_PIECE(da, aoff, dd, 2 * ((s) & 1)); WIDE_PIECE(da, aoff, dd, 2 * ((s) & 1) + 1); } \
 				else { WIDE_PIECE(db, boff, dd + W_TILE_BYTES, 2 * ((s) & 1)); WIDE_PIECE(db, boff, dd + W_TILE_BYTES, 2 * ((s) & 1) + 1); } \
 			}                                                                                                     \
@@ -242,12 +227,7 @@ __global__ __launch_bounds__(512, 2) void wide_kernel(const WideParams p) {
 				den = false;
 			}
 			WIDE_COMPUTE(1);
-#if defined(ANNCUR_V_WIDE_NOFILTER) || defined(ANNCUR_V_WIDE_MFMAONLY)
-			if (last) { asm volatile("" :: "v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]), "v"(acc[3][0]), "v"(acc[0][1]), "v"(acc[1][1]), "v"(acc[2][1]), "v"(acc[3][1])); }
-			if (false) {
-#else
 			if (last) {
-#endif
 				// ---- epilogue of the block tile (the next tile's DMA is in flight).  C/D layout: query = lane & 31,
 				// item row = (e & 3) + 8 (e >> 2) + 4 h within the 32-item sub-tile m of the wave's item half wi
 				if (MODE == 0) {
@@ -307,8 +287,6 @@ __global__ __launch_bounds__(512, 2) void wide_kernel(const WideParams p) {
 #undef WIDE_PIECE
 #undef WIDE_DMA2
 #undef WIDE_WAIT
-#undef WIDE_NODMA_COND
-#undef WIDE_LOAD_
 	}
 #undef bt_of
 	if (MODE == 1) {

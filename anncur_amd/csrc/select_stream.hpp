@@ -18,9 +18,6 @@
 // LDS per wave: 9 KB whatever k (the old buffer: 10 KB for k <= 128, 18 KB for k <= 512).
 #pragma once
 #include "wave_select.hpp"
-#ifndef SEL_STAMP
-#define SEL_STAMP(i) do { } while (0)
-#endif
 
 namespace anncur {
 
@@ -117,7 +114,6 @@ __global__ __launch_bounds__(256) void select_stream_kernel(const uint2 *__restr
 	const uint32_t floor_key = (tau && prefilter) ? f32_sortable(tau[q * tau_stride]) : 0u;
 	const uint2 *qc = cand + q * nseg * (int64_t)capg;
 
-	SEL_STAMP(0);
 	// ---- pass A: the keys at or above the floor go to the LDS key buffer (as many as fit); their range and count
 	uint32_t mn = 0xffffffffu, mx = 0u, n_in = 0;
 	walk_candidates<false>(qc, c, nseg, capg, lane, [&](const uint2 &e, bool valid) {
@@ -133,7 +129,6 @@ __global__ __launch_bounds__(256) void select_stream_kernel(const uint2 *__restr
 	});
 	mn = wave_reduce<DppMin>(mn); mx = wave_reduce<DppMax>(mx);
 	__builtin_amdgcn_wave_barrier();
-	SEL_STAMP(1);
 	if (n_in < k) { defer(); return; }
 
 	// ---- levels: 8-bit digits of (key - mn), most significant first; from the key buffer, or (more keys than it holds) from HBM again
@@ -159,11 +154,9 @@ __global__ __launch_bounds__(256) void select_stream_kernel(const uint2 *__restr
 				});
 			});
 	}
-	SEL_STAMP(2);
 	const uint32_t T = mn + prefix;  // key of the k-th best score; `need` of the n_eq candidates that carry it belong to the top-k
 	if (TAU_ONLY) {
 		if (lane == 0) tau[q * tau_stride] = fmaxf(tau[q * tau_stride], f32_unsortable(T));
-		SEL_STAMP(3);
 		return;
 	}
 
@@ -218,7 +211,6 @@ __global__ __launch_bounds__(256) void select_stream_kernel(const uint2 *__restr
 				oi[i] = real ? (remap ? remap[id] : id) : -1;
 			}
 		}
-		SEL_STAMP(3);
 	}
 }
 

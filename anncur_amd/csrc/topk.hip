@@ -196,9 +196,6 @@ template <> struct ScanPre<uint16_t> {  // bf16 rows: packed 16-bit integer comp
 		const uint32_t p16 = t16 ^ m16;
 		pre_pk = p16 | (p16 << 16);
 		pos = !neg && !all;
-#ifdef ANNCUR_V_SCANPTR
-		pos = false;
-#endif
 		pre_s = t16 | (t16 << 16);
 	}
 	__device__ __forceinline__ bool any_pos(const u32x4 &c) const {
@@ -845,9 +842,6 @@ extern "C" int anncur_rowwise_topk(const void *A, int dtype, int64_t Q, int64_t 
 	} while (0)
 	ANNCUR_REQUIRE(Q < (int64_t)0x7fffffff, ANNCUR_E_INVALID, "rowwise_topk: Q too large");
 	bool wave_scan = k <= WSEL_K;  // barrier-free path: one wave per row
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-	if (getenv("ANNCUR_DEBUG_BLOCK_SCAN")) wave_scan = false;
-#endif
 	if (wave_scan && I <= (int64_t)WS_CAP) {   // short rows: the whole row into the wave's buffer, then the final select + sort
 		const size_t lds = 4 * (size_t)WaveSelLayout<WS_CAP>::BYTES;
 		const unsigned grid = (unsigned)ceil_div64(Q, 4);
@@ -863,21 +857,9 @@ extern "C" int anncur_rowwise_topk(const void *A, int dtype, int64_t Q, int64_t 
 	}
 	if (wave_scan) {
 		size_t lds = 4 * (size_t)WaveSelLayout<WS_CAP>::BYTES;
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-		if (const char *dbg = getenv("ANNCUR_DEBUG_SCAN_LDS")) lds = (size_t)atoi(dbg);  // occupancy experiment: larger request = fewer waves per SIMD
-#endif
 		const unsigned grid = (unsigned)ceil_div64(Q, 4);
 		uint32_t trig = ws_trigger((uint32_t)k);
-#ifdef ANNCUR_TIMING_EXPERIMENTS
-		if (const char *dbg = getenv("ANNCUR_DEBUG_SCAN_TRIGGER")) {  // tuning knob: any value in (k, 512] is exact
-			const int t = atoi(dbg);
-			if (t > k && t <= 512) trig = (uint32_t)t;
-		}
-#endif
 		bool buf = I * (int64_t)dtype_size(dtype) < ((int64_t)1 << 31);   // the stream's loads through a buffer resource (32-bit offsets)
-#ifdef ANNCUR_V_SCANPTR   // (A/B variant build: round 3's stream loop -- pointer loads, xor prefilter)
-		buf = false;
-#endif
 		if (dtype == ANNCUR_F32) {
 			if (buf) hipLaunchKernelGGL((rowwise_topk_wave_kernel<float, false, true>), dim3(grid), dim3(256), lds, st, (const float *)A, Q, I, lda, (uint32_t)k, trig, out_val, out_idx);
 			else hipLaunchKernelGGL((rowwise_topk_wave_kernel<float, false, false>), dim3(grid), dim3(256), lds, st, (const float *)A, Q, I, lda, (uint32_t)k, trig, out_val, out_idx);

@@ -533,11 +533,6 @@ def score_topk_fused(Xp, Etp, I, k, return_fallbacks=False, workspace=None, lead
 	ids = _item_ids_arg(item_ids, I, Xp.device)
 	check(lib.anncur_score_topk_ex(_p(Xp), _ld(Xp), _p(Etp), Kp, Q, I, Kp, k, _p(val), _p(idx), _p(ws), nbytes,
 								   _topk_flags(leading_sample, mfma16, qt1, mfma32, ring, staged), _p(ids) if ids is not None else None, _stream()), "score_topk")
-	if ring and not torch.cuda.is_current_stream_capturing():
-		# ANNCUR_TOPK_RING (opt-in): a wave whose bounded spin on the tile ring's flags ran out stopped waiting and added 2^30 to the call's
-		# fallback counter (csrc/score16r.hpp); its candidates are then not to be trusted.  Fatal here (one host sync, the variant is opt-in).
-		if int(ws[:4].view(torch.int32).item()) >= 1 << 30:
-			raise _lib.AnncurHipError("score_topk (ring body): a wave gave up waiting on the tile ring; the result of this call is invalid")
 	if return_fallbacks:
 		return TopK(val, idx), ws[:4].view(torch.int32)
 	return TopK(val, idx)
@@ -560,7 +555,7 @@ _cu_streams = {}
 def cu_partition_streams(device, n_scan):
 	"""Two streams that split the chip's compute units: (retrieval stream on the CUs the scan leaves, scan stream on `n_scan` CUs), by
 	hipExtStreamCreateWithCUMask.  On MI355X the first n bits of the mask stand for n / 8 CUs on each of the 8 XCDs, in steps of 32
-	bits (scripts/cumask_map.py; sparse masks are ignored by the driver), so n_scan is rounded down to a multiple of 32.  For an
+	bits (mapped in round 4 by reading XCC_ID / HW_ID per workgroup; sparse masks are ignored by the driver), so n_scan is rounded down to a multiple of 32.  For an
 	HBM-bound kernel (the exact scan) beside an MFMA-bound one (the fused retrieval) whose workgroups fill the register file: sharing a
 	CU means time-slicing it, a partition lets both run for the whole step.  Created once per (device, n_scan); fails loudly if the
 	runtime lacks the call."""
@@ -667,7 +662,7 @@ def fused_plan(Q, I, Kp, k, leading_sample=False, mfma16=False, qt1=False, mfma3
 	rings; the default above k = 1024 -- above 384 under staged=True --, and for Kp = 512), 1 = the 16x16x32 body (one queue per wave; the default for Kp <= 256, k <= 1024),
 	4 = the wide kernel (Kp > 512); "QT": 32-query sub-tiles per wave (1 = qt1 honoured, or Kp = 512);
 	"stage_pred": body of each sweep stage -- 0 / 1 = 32x32x16 with the ballot / exec-mask filter, 2 = 16x16x32 (4-wave workgroups, barrier per
-	tile), 3 / 4 = Kp = 512 with the wave queue on 32x32x16 / 16x16x32, 5 = 16x16x32 in 8-wave workgroups with the tile ring (ring=True)."""
+	tile), 4 = Kp = 512 with the wave queue on 16x16x32.  ring=True (the retired tile-ring body) raises."""
 	out = (ctypes.c_int32 * 19)()
 	check(_lib.load().anncur_score_topk_plan_ex(Q, I, Kp, k, _topk_flags(leading_sample, mfma16, qt1, mfma32, ring, staged), out, 19), "score_topk_plan_ex")
 	v = [int(x) for x in out]

@@ -211,13 +211,10 @@ int anncur_score_topk(const void *X, int64_t ldx, const void *Et, int64_t lde,
  *    pipeline of the Kp = 512 sweep, instead of two sub-tiles staggered inside a wave at two workgroups per CU (A/B variant). */
 #define ANNCUR_TOPK_QT1 4
 #define ANNCUR_TOPK_MFMA32 8
-/*  ANNCUR_TOPK_RING (Kp = 128 / 256, k <= 128): the 16x16x32 body in 8-wave workgroups of 512 queries whose item tiles stream through a
- *    ring of four LDS slots synchronised by per-wave landed / done counters in LDS instead of a workgroup barrier per tile (round 4,
- *    csrc/score16r.hpp: half the L2 -> LDS traffic, half the DMA pieces per wave).  Same result bit for bit; measured slower than the
- *    default (4-wave workgroups, two tile buffers, one barrier per tile) at every size tried -- an A/B variant, not the default.
- *    Callers that set it MUST read workspace word 0 (uint32) after the call has completed: every spin of that body is bounded, and a
- *    wave whose spin ran out adds 2^30 to that word and stops waiting -- the call still returns ANNCUR_OK, its result is invalid
- *    (anncur_amd/ops.py::score_topk_fused(ring=True) raises on it). */
+/*  ANNCUR_TOPK_RING: retired.  It selected a tile-ring sweep body (round 4: the 16x16x32 body in 8-wave workgroups of 512 queries whose
+ *    item tiles stream through a ring of four LDS slots synchronised by per-wave counters instead of a workgroup barrier per tile),
+ *    which measured 3-4 % slower than the default at every size tried.  The body is gone; a call that sets the flag fails with
+ *    ANNCUR_E_UNSUPPORTED. */
 #define ANNCUR_TOPK_RING 16
 /*  ANNCUR_TOPK_STAGED: the default 16x16x32 body (Kp <= 256, k <= 384) WITHOUT its threshold ladder -- the sweep in stages with a refinement
  *    launch between them, as rounds 1-4 ran it (A/B and parity reference; the default since round 5 is ONE sweep launch whose waves move

@@ -47,7 +47,7 @@ retr = lambda: ops.score_topk_fused(Xp, Etp, I, k, leading_sample=True, item_ids
 s0, s1 = torch.cuda.Stream(), torch.cuda.Stream()
 print("unmasked: scan %.3f ms, retrieval %.3f ms, both on two streams %.3f ms" % (timed([scan], [s0]), timed([retr], [s0]), timed([retr, scan], [s0, s1])), flush=True)
 
-# (scripts/cumask_map.py: the first n bits of the mask, n a multiple of 8, are n / 8 CUs on each of the 8 XCDs; sparse masks are ignored)
+# (the CU-mask map of round 4: the first n bits of the mask, n a multiple of 8, are n / 8 CUs on each of the 8 XCDs; sparse masks are ignored)
 for n_scan in (64, 80, 88, 96, 104, 112, 120, 128):
 	bs = np.zeros(256, dtype=bool); bs[:n_scan] = True
 	ss, sr = masked_stream(bs), masked_stream(~bs)

@@ -4,7 +4,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "scripts", "r4"))
 from anncur_amd import ops   # noqa: E402
-from timeline_probe import masked_stream   # noqa: E402
+from cumask import masked_stream   # noqa: E402
 
 def main():
 	dev = torch.device("cuda", 0)

@@ -7,7 +7,7 @@ sys.path.insert(0, ROOT)
 from anncur_amd import ops   # noqa: E402
 import bench   # noqa: E402
 sys.path.insert(0, os.path.join(ROOT, "scripts", "r4"))
-from timeline_probe import masked_stream   # noqa: E402
+from cumask import masked_stream   # noqa: E402
 
 def main():
 	dev = torch.device("cuda", 0)

@@ -50,9 +50,10 @@ def test_no_compute_without_gpu_and_plan_queries_work():
 	assert lib.anncur_score_topk_workspace_bytes(1200, 15603, 1024, 100) > 0
 
 
-def test_sweep_variant_flags_reach_the_plan():
+def test_sweep_variant_flags_reach_the_plan_and_ring_is_refused():
 	"""ops.score_topk_fused accepted mfma16= / qt1= and dropped them.  The plan query takes the same flags word the launch
-	does (ops._topk_flags), so a dropped flag shows here without a GPU."""
+	does (ops._topk_flags), so a dropped flag shows here without a GPU.  The retired ring body's flag still reaches the library, which
+	refuses it."""
 	from anncur_amd import _lib, ops
 	assert ops._topk_flags() == 0 and ops._topk_flags(True, True, True, True) == (_lib.TOPK_LEADING_SAMPLE | _lib.TOPK_MFMA16 | _lib.TOPK_QT1 | _lib.TOPK_MFMA32)
 	base = ops.fused_plan(10000, 100000, 256, 100)
@@ -79,14 +80,10 @@ def test_sweep_variant_flags_reach_the_plan():
 	assert p512["lg"] == 1 and p512["QT"] == 1 and all(b == 4 for b in p512["stage_pred"])            # ... on 16x16x32 MFMAs
 	assert ops.fused_plan(6250, 1000000, 512, 100, mfma32=True)["lg"] == 2           # the per-lane-ring body on request
 	assert ops.fused_plan(64, (1 << 26) + 64, 64, 10)["lg"] == 2                      # queue entries carry the query beside the item: I < 2^26
-	# ANNCUR_TOPK_RING (round 4: the 16x16x32 body in 8-wave workgroups with a flag-synchronised tile ring) measured slower than the default and lives
-	# in the experiments library only since round 5: the product refuses the flag instead of silently running something else
-	if _lib.IS_EXPERIMENTS_LIB:
-		ring = ops.fused_plan(10000, 100000, 256, 100, ring=True)
-		assert all(b == 5 for b in ring["stage_pred"]) and ring["lg"] == 1 and ring["splits"] == 13 and not ring["ladder"]
-	else:
-		with pytest.raises(_lib.AnncurHipError, match="experiments library"):
-			ops.fused_plan(10000, 100000, 256, 100, ring=True)
+	# ANNCUR_TOPK_RING (round 4: the 16x16x32 body in 8-wave workgroups with a flag-synchronised tile ring) measured slower than the default and is
+	# retired: the library refuses the flag instead of silently running something else
+	with pytest.raises(_lib.AnncurHipError, match=r"\(code -4\).*ANNCUR_TOPK_RING.*retired"):   # ANNCUR_E_UNSUPPORTED
+		ops.fused_plan(10000, 100000, 256, 100, ring=True)
 	assert ops._topk_flags(ring=True) == _lib.TOPK_RING
 	import inspect
 	src = inspect.getsource(ops.score_topk_fused.__wrapped__) + inspect.getsource(ops.score_topk_fused_timed.__wrapped__)

@@ -316,35 +316,6 @@ def test_error_kernels_with_a_row_pitch_beyond_the_32_bit_tile_offsets(ops):
 	del buf
 
 
-@pytest.mark.parametrize("Q,I,K,k", [(1000, 40000, 256, 10), (777, 50001, 200, 64), (513, 30000, 128, 32), (5, 20000, 256, 7), (2049, 123457, 256, 128), (4100, 200000, 128, 100)])
-def test_fused_ring_body_equals_the_barrier_body(ops, Q, I, K, k):
-	"""ANNCUR_TOPK_RING (round 4, csrc/score16r.hpp): 8-wave workgroups of 512 queries, the item tiles through a ring of four LDS slots
-	synchronised by per-wave landed / done counters (no barrier in the tile loop), the tile sequence published by wave 0.  The tile
-	arithmetic is the barrier body's instruction for instruction: values bit for bit, index sets identical, no repaired query, no spin
-	timeout (a timeout adds 2^30 to the fallback counter).  Ragged row blocks (Q not a multiple of 512), a partial last tile, both
-	item orders, one- and two-stage plans."""
-	from anncur_amd import _lib
-	if not _lib.IS_EXPERIMENTS_LIB:
-		pytest.skip("the tile-ring body is compiled into the experiments library only since round 5 (ANNCUR_LIB=anncur_amd/lib/libanncur_hip_exp.so)")
-	X, E, Xp, Etp = _fused_case(ops, Q, I, K, k, seed=Q + I + K + k)
-	Kp = Xp.shape[1]
-	plan = ops.fused_plan(Q, I, Kp, k, ring=True)
-	assert all(b == 5 for b in plan["stage_pred"]) and all(b == 2 for b in ops.fused_plan(Q, I, Kp, k)["stage_pred"])
-	(v0, i0), nfb0 = ops.score_topk_fused(Xp, Etp, I, k, return_fallbacks=True)
-	for _ in range(3):   # (a protocol race would come and go)
-		(v, i), nfb = ops.score_topk_fused(Xp, Etp, I, k, return_fallbacks=True, ring=True)
-		torch.cuda.synchronize()
-		assert nfb.item() == 0 and nfb0.item() == 0
-		assert torch.equal(v, v0)
-		assert torch.equal(torch.sort(i, 1).values, torch.sort(i0, 1).values)
-	# with the index builder's hints (norm-ordered rows, leading sample, id map)
-	from anncur_amd.cur import _norm_sorted_pack
-	Ets, ids = _norm_sorted_pack(E.t().contiguous().float().cuda(), Kp)
-	a = ops.score_topk_fused(Xp, Ets, I, k, leading_sample=True, item_ids=ids, ring=True)
-	b = ops.score_topk_fused(Xp, Ets, I, k, leading_sample=True, item_ids=ids)
-	assert torch.equal(a.values, b.values) and torch.equal(torch.sort(a.indices, 1).values, torch.sort(b.indices, 1).values)
-
-
 @pytest.mark.parametrize("Q,I,K,k", [(300, 40000, 64, 10), (257, 65536, 128, 100), (1000, 50007, 256, 100), (64, 70000, 256, 1), (50, 131072, 200, 500)])
 def test_fused_mfma16_sweep_gives_the_same_topk(ops, Q, I, K, k):
 	"""The 16x16x32 sweep (ANNCUR_TOPK_MFMA16, score16.hpp): other lane <-> (query, item) map, survivors through one queue per wave
@@ -376,8 +347,8 @@ def test_fused_mfma16_sweep_gives_the_same_topk(ops, Q, I, K, k):
 
 @pytest.mark.parametrize("Q,I,K,k", [(257, 70000, 512, 100), (1000, 60007, 400, 10), (130, 131072, 512, 500)])
 def test_fused_kp512_queue_body_equals_the_ring_body(ops, Q, I, K, k):
-	"""Kp = 512 has two candidate paths: one queue per wave with the dynamic tile schedule (score_q16.hpp: 16x16x32 MFMAs, the default;
-	score_q1.hpp: the same on 32x32x16 MFMAs, experiments build) and per-lane rings with static shares on 32x32x16 MFMAs
+	"""Kp = 512 has two candidate paths: one queue per wave with the dynamic tile schedule (score_q16.hpp: 16x16x32 MFMAs, the default)
+	and per-lane rings with static shares on 32x32x16 MFMAs
 	(ANNCUR_TOPK_MFMA32).  Same products, fp32 sums that may associate differently between the MFMA shapes: values to 1e-6, sets identical."""
 	X, E, Xp, Etp = _fused_case(ops, Q, I, K, k, seed=Q + I + K + k)
 	assert Xp.shape[1] == 512
