@@ -26,11 +26,14 @@
 // threshold kernel also leaves eight LEVELS per query above tau0 (value-linear between the sample's k-th and a higher order statistic:
 // roughly geometric in rank), and the sweep counts what it keeps: the drain adds every candidate at or above a level the wave has not
 // reached yet to that level's 16-bit field of the query's four counter words (one no-return global_atomic_add per candidate, device scope).
-// Every fourth tile a wave fetches its 64 queries' counter words (one LDS-DMA piece, sc1) and, a tile later, moves each query's threshold up
-// to the highest level at or above which k candidates have been counted by ANY workgroup -- k distinct items score >= that level, so it is a
-// valid lower bound on the k-th best, whatever the timing (a stale count only means a later move).  One launch sweeps all the tiles: no
-// stage boundary, no refinement launch.  cfg2 (model: scripts/r5/survivor_model.py): 442 -> ~340 candidates per query; a field cannot
-// overflow (a wave stops counting a level once its own threshold is there; between two refreshes it adds <= 128 per query).
+// Every LADDER_PERIOD (16) tiles a wave fetches its 64 queries' counter words (one LDS-DMA piece, sc1) and, a tile later, moves each query's
+// threshold up to the highest level at or above which k candidates have been counted by ANY workgroup -- k distinct items score >= that level,
+// so it is a valid lower bound on the k-th best, whatever the timing (a stale count only means a later move).  One launch sweeps all the
+// tiles: no stage boundary, no refinement launch.  cfg2 (model: scripts/r5/survivor_model.py): 442 -> ~340 candidates per query.
+// A field must not wrap: a wrap in a low half (levels 1, 3, 5, 7) carries +1 into the next level's count.  A wave stops counting a level once
+// its own threshold is there; after the k-th count of a level each of the S waves of the query adds at most one fetch period, the lag tile,
+// the last tile's tail and what its queue still holds ahead of a drain: (LADDER_PERIOD + 2) * TILE_I + DRAIN_AT per query.  plan_fused
+// (score_fused.hip) runs the ladder only while k + S * that stays <= 32768, half a field (or I < 65536), and derives the bound in full.
 #pragma once
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;

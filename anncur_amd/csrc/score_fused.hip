@@ -1609,20 +1609,35 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	// (1970 against 2606 candidates per query, select 0.144 against 0.19), k = 1000 1.38 against 1.53; without the ladder (ANNCUR_TOPK_STAGED) the
 	// round-4 limit stands
 	constexpr int BODY16_MAX_K = 384, BODY16_MAX_K_LADDER = 1024;
-	const bool ladder_possible = !no_ladder && ticketed && P.n_groups <= 4096;
-	P.body16 = can16 && !mfma32 && !evalf && (mfma16 || k <= (ladder_possible ? BODY16_MAX_K_LADDER : BODY16_MAX_K));
 	int S = P.chunk > 0 ? (slots + P.n_rb - 1) / P.n_rb : slots / P.n_rb;
 	if (P.chunk > 0 && k <= WQ_K2 && S > WAVE / 2) S = WAVE / 2;
 	if (S < 1) S = 1;
 	if (S > 255) S = P.chunk > 0 ? 255 : (S > 256 ? 256 : S);   // (the owner map holds a split in a byte, 255 = none)
+	if (S > P.n_tiles) S = P.n_tiles;
+	P.tiles_per_split = (P.n_tiles + S - 1) / S;
+	P.S = (P.n_tiles + P.tiles_per_split - 1) / P.tiles_per_split;
+	// The ladder's counters are 16-bit fields, two per word: a wrap in a low half (levels 1, 3, 5, 7) would carry +1 into the next level's count,
+	// and a move on that count could drop the true k-th item.  Bound on a field (score16.hpp): the S waves that serve a query (one per item split)
+	// add to level j's field only while their own threshold is below level j.  Once k candidates at or above level j have been counted (time T:
+	// the field holds <= k then), a wave adds to it only what it drains before its next refresh, which raises its threshold to j:
+	//   - one fetch period: the first fetch issued after T comes at most LADDER_PERIOD tiles later;
+	//   - the lag tile: its words are consumed at the head of the NEXT tile (and T may fall inside a tile whose pushes are drained later), and
+	//     the last tile's sub-tiles {2,3} are filtered and drained after the tile loop: one tile each, <= TILE_I candidates per query and tile;
+	//   - the entries still queued ahead of a drain: a head drain waits for DRAIN_AT entries, so fewer than DRAIN_AT of the query's candidates
+	//     may sit in the queue at T.
+	// (The cold drains inside a tile do not count.)  So a field never exceeds k + S ((LADDER_PERIOD + 2) TILE_I + DRAIN_AT), and the ladder runs
+	// only while that stays below half a field (or while I itself is below a field's range: a field counts distinct items).  With S <= WAVE / 2
+	// (k <= WQ_K2) and LADDER_PERIOD = 16 this is 1024 + 32 x 768 = 25 600 <= 32 768: the gate does not bind today; it keeps a later change of
+	// WQ_K2, the cap on S, LADDER_PERIOD or the tile size from bringing the carry back unnoticed (tests/test_cpu_host.py checks it on a grid).
+	constexpr int64_t LADDER_WAVE_SLACK = (int64_t)(LADDER_PERIOD + 2) * TILE_I + Fused16Cfg<256>::DRAIN_AT;   // (DRAIN_AT: the same for every Kp)
+	const bool ladder_fits = I < 65536 || (int64_t)k + (int64_t)P.S * LADDER_WAVE_SLACK <= 32768;
+	const bool ladder_possible = !no_ladder && ticketed && P.n_groups <= 4096 && ladder_fits;
+	P.body16 = can16 && !mfma32 && !evalf && (mfma16 || k <= (ladder_possible ? BODY16_MAX_K_LADDER : BODY16_MAX_K));
 	// Body of the sweep stages (Kp <= 256, two sub-tiles per wave): 16x16x32 MFMAs with one candidate queue per wave (score16.hpp; its queue
 	// entries carry the query beside the item: I < 2^26) for k <= 128, 32x32x16 with per-lane rings above (at k = 500 half of the leading
 	// tiles' elements pass the first threshold: the rings' raw-tile hand-over is built for that).  ANNCUR_TOPK_MFMA16 / _MFMA32 force one.
 	// Measured at cfg2, MI355X, same box, alternating (round 3): sweep launches 0.457 ms (16x16x32) vs 0.479 (32x32x16) at equal stage
 	// split, 0.450 with the split below; a mixed plan (first stage 32x32x16, later stages 16x16x32) was level with 16x16x32 throughout.
-	if (S > P.n_tiles) S = P.n_tiles;
-	P.tiles_per_split = (P.n_tiles + S - 1) / S;
-	P.S = (P.n_tiles + P.tiles_per_split - 1) / P.tiles_per_split;
 	int S0 = slots / P.n_rb;
 	if (S0 < 1) S0 = 1;
 	if (S0 > P.n_st) S0 = P.n_st;
@@ -1647,7 +1662,7 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	// Threshold ladder (score16.hpp, round 5): the default 16x16x32 body raises its thresholds inside ONE launch from counts of what it keeps, so it
 	// runs unstaged.  The ladder's top level = the sample's group maximum of rank k2 ~ where the k-th best of ALL items is expected to fall among
 	// the sample's (k x sample items / I; the norm-ordered leading sample holds about twice its share of the high scorers), at least 3, at most k / 2.
-	P.ladder = P.body16 && !no_ladder && P.n_groups <= 4096 && P.chunk > 0;
+	P.ladder = P.body16 && ladder_possible;
 	{
 		double r = (double)k * ((double)P.n_st * TILE_I / (double)I) * (leading ? 2.0 : 1.25);
 		int k2 = (int)(r + 0.5);
@@ -2292,7 +2307,8 @@ extern "C" int anncur_score_topk_plan(int64_t Q, int64_t I, int32_t Kp, int32_t 
  * query and item split (2: 32x32x16 sweep, 1: 16x16x32 sweep, 4: wide kernel), 32-query sub-tiles per wave, sweep stages,
  * stage_end[3], stage body[3] (0: 32x32x16 with the ballot filter, 1: with the exec-mask filter, 2: 16x16x32, 4: Kp = 512 with the
  * wave-level queue on 16x16x32 MFMAs), ring drain period[3],
- * threshold ladder (1: the sweep raises its thresholds in-launch, score16.hpp; 0: staged), rank of the ladder's top level} --
+ * threshold ladder (1: the sweep raises its thresholds in-launch, score16.hpp; 0: staged), rank of the ladder's top level,
+ * tiles between two fetches of a wave's ladder counters (LADDER_PERIOD)} --
  * what a test needs to see that a variant flag was honoured */
 extern "C" int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, int32_t *out, int32_t n_out) {
 	ANNCUR_REQUIRE((flags & ~TOPK_FLAGS) == 0, ANNCUR_E_INVALID, "score_topk_plan_ex: unknown flags 0x%x", flags);
@@ -2300,13 +2316,13 @@ extern "C" int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32
 	const FusedPlan P = plan_any(Q, I, Kp, k, flags);
 	ANNCUR_REQUIRE(P.ok && out && n_out >= 0, ANNCUR_E_UNSUPPORTED, "score_topk_plan_ex: unsupported shape");
 	const bool wide = wide_kp(Kp);
-	int32_t v[19] = {P.n_st, P.n_tiles, P.S, P.capg, P.group, wide ? 4 : P.lg, P.QT, P.n_stages};
-	v[17] = (!wide && P.ladder) ? 1 : 0; v[18] = (!wide && P.ladder) ? P.ladder_k2 : 0;
+	int32_t v[20] = {P.n_st, P.n_tiles, P.S, P.capg, P.group, wide ? 4 : P.lg, P.QT, P.n_stages};
+	v[17] = (!wide && P.ladder) ? 1 : 0; v[18] = (!wide && P.ladder) ? P.ladder_k2 : 0; v[19] = LADDER_PERIOD;
 	for (int g = 0; g < 3; ++g) {
 		const bool on = g < P.n_stages;
 		v[8 + g] = on ? P.stage_end[g] : 0; v[11 + g] = on ? (wide ? P.stage_pred[g] : P.bodyef ? 6 : P.body16 ? 2 : P.bodyq16 ? 4 : P.stage_pred[g]) : 0; v[14 + g] = on ? P.stage_flush[g] : 0;
 	}
-	for (int i = 0; i < n_out && i < 19; ++i) out[i] = v[i];
+	for (int i = 0; i < n_out && i < 20; ++i) out[i] = v[i];
 	return ANNCUR_OK;
 }
 
@@ -2324,6 +2340,30 @@ extern "C" int anncur_score_topk_survivors(const void *workspace, int64_t Q, int
 	double tot = 0.0;
 	for (size_t i = 0; i < n; ++i) tot += (h[i] & 0x80000000u) ? 0.0 : (double)h[i];   // (a poisoned count marks a repaired split)
 	*mean_per_query = tot / (double)Q;
+	return ANNCUR_OK;
+}
+
+/* diagnostics: the threshold ladder the sweep of the LAST call on this workspace left behind (synchronises the stream).  The plan's arrays
+ * are laid out per row block (n_rb x BQ rows); the first Q rows are returned, the counter words decoded into one count per level
+ * (levels[q][j - 1] <-> counts[q][j - 1]: the candidates counted with level j as the highest they reach). */
+extern "C" int anncur_score_topk_ladder_state(const void *workspace, int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, float *levels,
+											  uint32_t *counts, float *tau_final, float *tau0, void *stream) {
+	ANNCUR_REQUIRE((flags & ~TOPK_FLAGS) == 0 && workspace && levels && counts && tau_final, ANNCUR_E_INVALID, "score_topk_ladder_state: bad arguments");
+	ANNCUR_REQUIRE(ring_flag_ok(flags), ANNCUR_E_UNSUPPORTED, "score_topk_ladder_state: ANNCUR_TOPK_RING (the tile-ring sweep body) is retired");
+	const FusedPlan P = plan_any(Q, I, Kp, k, flags);
+	ANNCUR_REQUIRE(P.ok, ANNCUR_E_UNSUPPORTED, "score_topk_ladder_state: unsupported shape");
+	ANNCUR_REQUIRE(!wide_kp(Kp) && P.ladder, ANNCUR_E_UNSUPPORTED, "score_topk_ladder_state: the plan of (Q=%lld, I=%lld, Kp=%d, k=%d, flags 0x%x) has no threshold ladder",
+				   (long long)Q, (long long)I, Kp, k, flags);
+	const unsigned char *ws = (const unsigned char *)workspace;
+	hipStream_t st = (hipStream_t)stream;
+	std::vector<uint32_t> words((size_t)Q * 4);
+	ANNCUR_HIP_OK(hipMemcpyAsync(levels, ws + P.off_lvl, (size_t)Q * LADDER_LEVELS * 4, hipMemcpyDeviceToHost, st));
+	ANNCUR_HIP_OK(hipMemcpyAsync(words.data(), ws + P.off_lcnt, (size_t)Q * 16, hipMemcpyDeviceToHost, st));
+	ANNCUR_HIP_OK(hipMemcpyAsync(tau_final, ws + P.off_tau2, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
+	if (tau0) ANNCUR_HIP_OK(hipMemcpyAsync(tau0, ws + P.off_tau, (size_t)Q * 4, hipMemcpyDeviceToHost, st));   // (ladder plans: <= 4096 group maxima, tau_stride 1)
+	ANNCUR_HIP_OK(hipStreamSynchronize(st));
+	for (int64_t q = 0; q < Q; ++q)
+		for (int j = 0; j < LADDER_LEVELS; ++j) counts[q * LADDER_LEVELS + j] = (words[(size_t)q * 4 + (j >> 1)] >> (16 * (j & 1))) & 0xffffu;
 	return ANNCUR_OK;
 }
 

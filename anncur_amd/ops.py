@@ -499,7 +499,8 @@ def score_topk_fused(Xp, Etp, I, k, return_fallbacks=False, workspace=None, lead
 	leading_sample / item_ids: the index builder's hints of anncur_score_topk_ex (rows of Etp ordered by descending norm, and the
 	map from rows back to item ids); the result is the exact top-k either way.
 	mfma16 / mfma32 / qt1: the sweep variants ANNCUR_TOPK_MFMA16 / _MFMA32 / _QT1 (fused_plan(..., mfma16=, ...) tells whether the shape
-	takes them: "lg" == 1 / "lg" == 2 / "QT" == 1; the default for Kp <= 256 is the 16x16x32 body up to k = 128, 32x32x16 above)."""
+	takes them: "lg" == 1 / "lg" == 2 / "QT" == 1; the default for Kp <= 256 is the 16x16x32 body with its threshold ladder up to k = 1024,
+	32x32x16 above; staged=True runs the sweep in stages without the ladder, on the 16x16x32 body up to k = 384 and on 32x32x16 above)."""
 	_dev(Xp, Etp)
 	if Xp.dtype != torch.bfloat16 or Etp.dtype != torch.bfloat16:
 		raise TypeError("score_topk_fused takes bf16 operands")
@@ -657,19 +658,36 @@ def fused_survivors(workspace, Q, I, Kp, k, leading_sample=False, mfma16=False, 
 	return out.value
 
 
+@_on_device
+def fused_ladder_state(workspace, Q, I, Kp, k, leading_sample=False, mfma16=False, qt1=False, mfma32=False, ring=False, staged=False):
+	"""The threshold ladder the sweep of the last score_topk_fused call on `workspace` (same shape and flags) left behind, as numpy arrays
+	(diagnostics; synchronises): "levels" [Q x 8] float32 (ascending, above "tau0"), "counts" [Q x 8] uint32 (candidates counted with level
+	j as the highest they reach: counts[:, j - 1]), "tau_final" [Q] float32 (the select's prefilter), "tau0" [Q] float32 (the prepass
+	threshold).  Raises when the plan has no ladder (fused_plan(...)["ladder"] is False)."""
+	levels = np.zeros((Q, 8), dtype=np.float32)
+	counts = np.zeros((Q, 8), dtype=np.uint32)
+	tau_final = np.zeros(Q, dtype=np.float32)
+	tau0 = np.zeros(Q, dtype=np.float32)
+	check(_lib.load().anncur_score_topk_ladder_state(_p(workspace), Q, I, Kp, k, _topk_flags(leading_sample, mfma16, qt1, mfma32, ring, staged),
+													  levels.ctypes.data, counts.ctypes.data, tau_final.ctypes.data, tau0.ctypes.data, _stream()),
+		  "score_topk_ladder_state")
+	return {"levels": levels, "counts": counts, "tau_final": tau_final, "tau0": tau0}
+
+
 def fused_plan(Q, I, Kp, k, leading_sample=False, mfma16=False, qt1=False, mfma32=False, ring=False, staged=False):
 	"""The plan a fused call with these flags runs.  "lg": candidate segments per (query, item split) -- 2 = the 32x32x16 body (per-lane
 	rings; the default above k = 1024 -- above 384 under staged=True --, and for Kp = 512), 1 = the 16x16x32 body (one queue per wave; the default for Kp <= 256, k <= 1024),
 	4 = the wide kernel (Kp > 512); "QT": 32-query sub-tiles per wave (1 = qt1 honoured, or Kp = 512);
 	"stage_pred": body of each sweep stage -- 0 / 1 = 32x32x16 with the ballot / exec-mask filter, 2 = 16x16x32 (4-wave workgroups, barrier per
 	tile), 4 = Kp = 512 with the wave queue on 16x16x32.  ring=True (the retired tile-ring body) raises."""
-	out = (ctypes.c_int32 * 19)()
-	check(_lib.load().anncur_score_topk_plan_ex(Q, I, Kp, k, _topk_flags(leading_sample, mfma16, qt1, mfma32, ring, staged), out, 19), "score_topk_plan_ex")
+	out = (ctypes.c_int32 * 20)()
+	check(_lib.load().anncur_score_topk_plan_ex(Q, I, Kp, k, _topk_flags(leading_sample, mfma16, qt1, mfma32, ring, staged), out, 20), "score_topk_plan_ex")
 	v = [int(x) for x in out]
 	plan = dict(zip(("n_sample_tiles", "n_tiles", "splits", "segment_capacity", "group", "lg", "QT", "n_stages"), v[:8]))
 	n = plan["n_stages"]
 	plan["stage_end"], plan["stage_pred"], plan["stage_flush"] = v[8:8 + n], v[11:11 + n], v[14:14 + n]
 	plan["ladder"], plan["ladder_top_rank"] = bool(v[17]), v[18]   # the sweep raises its thresholds in-launch (csrc/score16.hpp; staged=True switches it off)
+	plan["ladder_period"] = v[19]   # tiles between two fetches of a wave's ladder counters (LADDER_PERIOD)
 	return plan
 
 

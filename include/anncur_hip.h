@@ -202,7 +202,8 @@ int anncur_score_topk(const void *X, int64_t ldx, const void *Et, int64_t lde,
 #define ANNCUR_TOPK_LEADING_SAMPLE 1
 /*  The sweep has two bodies for Kp <= 256: v_mfma_f32_32x32x16_bf16 with per-lane candidate rings, and v_mfma_f32_16x16x32_bf16 with one
  *    candidate queue per wave (I < 2^26; the chip holds a higher clock on that shape).  Same products and fp32 sums: the result is the
- *    same bit for bit up to the order of exact score ties.  Default: the 16x16x32 body for k <= 384, the 32x32x16 body above.
+ *    same bit for bit up to the order of exact score ties.  Default: the 16x16x32 body for k <= 1024, where its threshold ladder runs
+ *    (k <= 384 in a plan without the ladder), the 32x32x16 body above.
  *  ANNCUR_TOPK_MFMA16 / ANNCUR_TOPK_MFMA32: force the 16x16x32 / the 32x32x16 body (A/B variants).  Kp = 512 has one MFMA shape and two
  *    candidate paths: one queue per wave with the dynamic tile schedule on 16x16x32 MFMAs (default, I < 2^26), per-lane rings with
  *    static shares on 32x32x16 MFMAs (ANNCUR_TOPK_MFMA32). */
@@ -216,9 +217,10 @@ int anncur_score_topk(const void *X, int64_t ldx, const void *Et, int64_t lde,
  *    which measured 3-4 % slower than the default at every size tried.  The body is gone; a call that sets the flag fails with
  *    ANNCUR_E_UNSUPPORTED. */
 #define ANNCUR_TOPK_RING 16
-/*  ANNCUR_TOPK_STAGED: the default 16x16x32 body (Kp <= 256, k <= 384) WITHOUT its threshold ladder -- the sweep in stages with a refinement
- *    launch between them, as rounds 1-4 ran it (A/B and parity reference; the default since round 5 is ONE sweep launch whose waves move
- *    their thresholds up a ladder of levels from device-wide counts of the candidates kept so far: csrc/score16.hpp).  Same result. */
+/*  ANNCUR_TOPK_STAGED: the default sweep WITHOUT its threshold ladder -- the sweep in stages with a refinement launch between them, as
+ *    rounds 1-4 ran it (A/B and parity reference; the default since round 5 is ONE sweep launch whose waves move their thresholds up a
+ *    ladder of levels from device-wide counts of the candidates kept so far: csrc/score16.hpp).  For Kp <= 256 and k <= 384 the same
+ *    16x16x32 body runs staged; for k in 385..1024 the flag also switches the body, to the staged 32x32x16 one.  Same result. */
 #define ANNCUR_TOPK_STAGED 32
 int anncur_score_topk_ex(const void *X, int64_t ldx, const void *Et, int64_t lde,
                          int64_t Q, int64_t I, int32_t Kp, int32_t k,
@@ -252,16 +254,24 @@ int anncur_score_topk_timed(const void *X, int64_t ldx, const void *Et, int64_t 
                             int32_t flags, const int32_t *item_ids, void *stream, float *stage_ms);
 /* Plan introspection: out5 = {sample tiles, item tiles, item splits S, segment capacity, group size}. */
 int anncur_score_topk_plan(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t *out5);
-/* The plan a call with `flags` (ANNCUR_TOPK_*) would run: out[0 .. n_out), n_out <= 17 = {sample tiles, item tiles, item splits S,
+/* The plan a call with `flags` (ANNCUR_TOPK_*) would run: out[0 .. n_out), n_out <= 20 = {sample tiles, item tiles, item splits S,
  * segment capacity, group size, candidate segments per (query, item split) -- 2: 32x32x16 sweep, 1: 16x16x32 sweep, 4: wide
  * kernel --, 32-query sub-tiles per wave, number of sweep stages, stage_end[3] (tiles), body per stage[3] (0: 32x32x16 with the ballot
  * filter, 1: 32x32x16 with the exec-mask filter, 2: 16x16x32, 3 / 4: the Kp = 512 body with the wave-level queue on 32x32x16 / 16x16x32 MFMAs), ring
- * drain period per stage[3]}.  Lets a caller (and the parity tests) see that a variant flag was honoured for the shape. */
+ * drain period per stage[3], threshold ladder (1: in-launch ladder, 0: none), rank of the ladder's top level among the sampled group
+ * maxima, tiles between two fetches of a wave's ladder counters}.  Lets a caller (and the parity tests) see that a variant flag was
+ * honoured for the shape. */
 int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, int32_t *out, int32_t n_out);
 /* Diagnostics: mean number of candidates per query the sweep of the last call on `workspace` kept (reads the segment counts it left
  * behind; synchronises `stream`).  k ln(I / k) is what a sequential threshold can reach. */
 int anncur_score_topk_survivors(const void *workspace, int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, double *mean_per_query,
                                 void *stream);
+/* Diagnostics: the threshold ladder the sweep of the last call on `workspace` (same Q, I, Kp, k, flags) left behind; synchronises `stream`.
+ * Host arrays: levels[Q x 8] (the levels above tau0, ascending), counts[Q x 8] (candidates counted with level j as the highest they
+ * reach, one count per level: counts[q][j - 1]), tau_final[Q] (the select's prefilter: the highest threshold a workgroup ended with),
+ * tau0[Q] (the prepass threshold; may be NULL).  ANNCUR_E_UNSUPPORTED when the plan has no ladder. */
+int anncur_score_topk_ladder_state(const void *workspace, int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, float *levels,
+                                   uint32_t *counts, float *tau_final, float *tau0, void *stream);
 
 /* a8: exact re-rank of the approximately retrieved items + a10 overlap counts --------
  *   temp[approx_idx] = exact[approx_idx]; temp.topk(k)      ...crossenc.py:108-113 ; ..._splits.py:93-96

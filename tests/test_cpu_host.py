@@ -90,6 +90,55 @@ def test_sweep_variant_flags_reach_the_plan_and_ring_is_refused():
 	assert src.count("_topk_flags(leading_sample, mfma16, qt1, mfma32, ring, staged)") == 2 and "mfma16=mfma16, qt1=qt1, mfma32=mfma32, ring=ring, staged=staged" in src
 
 
+def _score16_constant(name):
+	src = open(os.path.join(ROOT, "anncur_amd", "csrc", "score16.hpp")).read()
+	return int(re.search(r"\b" + name + r"\s*=\s*(\d+)\s*;", src).group(1))
+
+
+def test_fused_plan_ladder_counters_cannot_wrap():
+	"""The threshold ladder (csrc/score16.hpp) counts candidates per level in 16-bit fields, two per word: a wrap in a low half would carry
+	into the next level's count and could move a threshold past the true k-th score.  plan_fused runs the ladder only while
+	k + S ((LADDER_PERIOD + 2) TILE_I + DRAIN_AT) <= 32768 (half a field; the derivation is at the gate) or I < 65536.  Over a grid of
+	shapes: every ladder plan keeps that bound, and today's constants never make the gate bind (the ladder runs wherever it ran before)."""
+	from anncur_amd import _lib, ops
+	lib = _lib.load()
+	tile_i, drain_at = 32, _score16_constant("DRAIN_AT")
+	n_ladder = 0
+	for Q in (1, 63, 64, 65, 255, 256, 257, 700, 2560, 10000):
+		for I in (40000, 65535, 65536, 1 << 18, 1 << 20, (1 << 26) - 1, 1 << 26):
+			for Kp in (64, 128, 256):
+				for k in (1, 100, 128, 129, 384, 385, 1000, 1024, 1025):
+					if not lib.anncur_score_topk_supported(Q, I, Kp, k):
+						continue
+					for leading in (False, True):
+						p = ops.fused_plan(Q, I, Kp, k, leading_sample=leading)
+						case = (Q, I, Kp, k, leading, p)
+						assert p["ladder_period"] >= 1 and p["ladder_period"] & (p["ladder_period"] - 1) == 0, case
+						if I >= 1 << 26:
+							assert p["lg"] == 2 and not p["ladder"], case        # queue entries carry the query beside the item: I < 2^26
+						if k > 1024:
+							assert not p["ladder"], case                          # > 4096 group maxima: no wave-level threshold kernel
+						elif I < 1 << 26:
+							assert p["ladder"], case                              # the gate does not bind with today's constants
+						if not p["ladder"]:
+							continue
+						n_ladder += 1
+						assert p["lg"] == 1 and p["n_stages"] == 1, case
+						assert I < 65536 or k + p["splits"] * ((p["ladder_period"] + 2) * tile_i + drain_at) <= 32768, case
+						if k >= 6:
+							assert 3 <= p["ladder_top_rank"] <= k // 2, case
+	assert n_ladder > 500
+
+
+def test_fused_plan_cfg2_is_unchanged_by_the_ladder_gate():
+	"""The bench headline shape (10 000 queries x 100 000 items, Kp 256, k 100): the plan the 16-bit counter gate leaves is exactly the one
+	the sweep ran before it -- 13 item splits, the ladder, one sweep launch on the 16x16x32 body, segments of 1024."""
+	from anncur_amd import ops
+	assert ops.fused_plan(10000, 100000, 256, 100) == {
+		"n_sample_tiles": 256, "n_tiles": 3125, "splits": 13, "segment_capacity": 1024, "group": 16, "lg": 1, "QT": 2, "n_stages": 1,
+		"stage_end": [3125], "stage_pred": [2], "stage_flush": [1], "ladder": True, "ladder_top_rank": 10, "ladder_period": 16}
+
+
 def test_product_never_imports_the_oracle():
 	pkg = os.path.join(ROOT, "anncur_amd")
 	offenders = []

@@ -267,13 +267,26 @@ def test_fused_threshold_ladder_equals_the_staged_sweep(ops, kind):
 	Xp = ops.pack_bf16(X.cuda(), Kp); Etp = ops.pack_bf16(E.t().contiguous().cuda(), Kp, row_multiple=32)
 	plan, plan_s = ops.fused_plan(Q, I, Kp, k), ops.fused_plan(Q, I, Kp, k, staged=True)
 	assert plan["ladder"] and plan["n_stages"] == 1 and not plan_s["ladder"] and plan_s["n_stages"] >= 2
+	S = X.double() @ E.double()
+	# the ladder's own state (tests/test_gpu_fused_exact.py): (a) no level counts more items than score at or above it, (b) tau0 <= the final
+	# threshold <= the true k-th score, (c) ascending levels from tau0 up.  The select's repair would hide a threshold that moved too far.
+	# (fp32 sums against the fp64 scores: a tolerance of 1e-4 of the largest score, the same as the value checks below; 0 for the exact kinds)
+	tol = 0.0 if kind in ("integer_ties", "flat") else 1e-4 * float(S.abs().max())
+	kth = torch.topk(S, k, dim=1).values[:, -1].numpy()
+	ws = ops.fused_workspace(Q, I, Kp, k, Xp.device)
 	for _ in range(3):   # (a dependence on the timing of the counts would come and go)
-		a = ops.score_topk_fused(Xp, Etp, I, k)
+		a = ops.score_topk_fused(Xp, Etp, I, k, workspace=ws)
+		st = ops.fused_ladder_state(ws, Q, I, Kp, k)
 		torch.cuda.synchronize()
 		b = ops.score_topk_fused(Xp, Etp, I, k, staged=True)
 		torch.cuda.synchronize()
 		assert torch.equal(a.values, b.values) and torch.equal(a.indices, b.indices), kind
-	S = X.double() @ E.double()
+		lv, t0, tf = st["levels"].astype(np.float64), st["tau0"].astype(np.float64), st["tau_final"].astype(np.float64)
+		assert (np.diff(lv, axis=1) >= 0).all() and (lv[:, 0] >= t0).all(), kind                      # (c)
+		assert (t0 <= tf).all() and (tf <= kth + tol).all(), kind                                      # (b)
+		counted_ge = np.cumsum(st["counts"].astype(np.int64)[:, ::-1], axis=1)[:, ::-1]
+		true_ge = np.stack([(S >= torch.from_numpy(lv[:, j] - tol)[:, None]).sum(1).numpy() for j in range(8)], axis=1)
+		assert (counted_ge <= true_ge).all(), kind                                                     # (a)
 	order = torch.argsort(S, dim=1, descending=True, stable=True)[:, :k]
 	if kind in ("integer_ties", "flat"):    # exactly representable: THE top-k under the defined order
 		assert torch.equal(a.indices.cpu().long(), order) and torch.equal(a.values.cpu().double(), torch.gather(S, 1, order))
