@@ -112,12 +112,25 @@ struct FusedParams {
 	const float *ladder; uint32_t *ladder_cnt; float *tau_final;
 	uint32_t *nfb;                    // workspace word 0
 	int ring_stagger, ring_spin_sleep;
+	uint32_t zero_bytes;              // prepass kernels: workspace bytes [0, zero_bytes) to clear (a multiple of 16; 0: none) -- see zero_ws_header
 };
 
 // Contiguous work ids per XCD (blocks b and b+8 share an XCD's L2): speed only, never correctness.
 __device__ __forceinline__ int xcd_remap(int b, int n) {
 	const int q = n >> 3, r = n & 7, x = b & 7, l = b >> 3;
 	return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + l;
+}
+
+// The workspace header -- fallback and hard-list counts (bytes 0..255), the sweep stages' ticket counters, the ladder's counter words: everything
+// in front of gmax -- must be zero when the sweep starts.  It used to be a hipMemsetAsync in front of the prepass (a fill kernel and a graph node
+// of its own, every call); the prepass workgroups clear it instead, grid-strided, 16 bytes per lane (at cfg2 165 KB over 480 x 256 lanes: at most
+// one store each).  Nothing reads the range before the threshold kernel's successors: the prepass writes only gmax, the threshold kernel tau and
+// the ladder levels; the counts are first touched by the sweep and the select, all behind the prepass on the same stream.
+__device__ __forceinline__ void zero_ws_header(const FusedParams &p) {
+	typedef __attribute__((ext_vector_type(4))) unsigned int zvec;
+	zvec *const dst = reinterpret_cast<zvec *>(p.nfb);   // (the workspace is 256-byte aligned)
+	const uint32_t n = p.zero_bytes >> 4;
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = (zvec){0u, 0u, 0u, 0u};
 }
 
 
@@ -517,6 +530,7 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const int r = lane & 31, h = lane >> 5;
+	if (MODE == 0) zero_ws_header(p);
 	const int wid = xcd_remap(blockIdx.x, p.n_wg);
 	const int nsplit = (MODE == 0) ? p.S0 : p.S;
 	const int n_rb_ = (int)((p.Q + Cfg::BQ - 1) / Cfg::BQ);
@@ -908,6 +922,7 @@ __device__ __forceinline__ int xcc_id() {
 }
 
 #include "score16.hpp"
+#include "prepass16.hpp"
 #include "score_q16.hpp"
 
 // ------------------------------------------------------------------ a11: approximation error on the same MFMA loop
@@ -1674,7 +1689,7 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	plan_stages(P, Q, k, exp_hits, !P.ladder && (k <= WQ_K2 ? P.lg * P.S <= WAVE : true) && P.n_tiles >= 24 * P.S, 4.0 * P.S / P.n_tiles, TILE_I);
 	P.kmax = k <= 128 ? 128 : (k <= 512 ? 512 : 2048);
 	size_t off = 256;
-	P.off_ctr = off;    off = align256(off + (size_t)P.n_rb * 3 * 4 * N_SLICES);   // ticket counters [stage][row block][slice]: zeroed with the header, one memset
+	P.off_ctr = off;    off = align256(off + (size_t)P.n_rb * 3 * 4 * N_SLICES);   // ticket counters [stage][row block][slice]: zeroed with the header by the prepass (zero_ws_header)
 	P.off_lcnt = off;   off = align256(off + (P.ladder ? (size_t)P.n_rb * P.BQ * 16 : 0));   // ladder counter words: zeroed with the header too
 	P.off_gmax = off;   off = align256(off + (size_t)Q * P.n_groups * 4);
 	P.off_tval = off;   off = align256(off + (size_t)Q * k * 4);
@@ -1898,24 +1913,32 @@ int launch_fused(const FusedPlan &P, const void *X, int64_t ldx, const void *Et,
 
 	const int chunk = (P.chunk > 0 && (Cfg::QT == 2 || P.bodyq16)) ? P.chunk : 0;   // (the one-sub-tile bodies with per-lane rings keep static shares)
 	const int owner_stride = P.n_rb * (P.n_tiles / (chunk > 0 ? chunk : P.n_tiles) + 2);
-	ANNCUR_HIP_OK(hipMemsetAsync(ws, 0, (chunk > 0 || P.ladder) ? P.off_gmax : 256, st));   // header (+ the stages' ticket counters, the ladder's counter words)
+	int rc;
 	EV(0);
-	// 1. prepass
+	// 1. prepass; its workgroups also clear the header (+ the stages' ticket counters, the ladder's counter words): zero_ws_header -- no memset launch
 	p.n_wg = P.n_rb * P.S0;
 	{
 		// anncur_eval_fused_ex's hint: the prepass samples the LEADING tiles of the norm-ordered copy (the likeliest high scorers: a tighter first
 		// threshold), the sweep keeps the item order the exact tiles need.  Any subset of the items gives a valid threshold.
 		FusedParams pp = p;
+		pp.zero_bytes = (uint32_t)((chunk > 0 || P.ladder) ? P.off_gmax : 256);
 		if (ea && ea->Et_hint) { pp.Et = ea->Et_hint; pp.sample_leading = 1; }
-		if (P.group == 16)
+		bool pre16 = false;
+		if constexpr (KP <= 256 && QTV == 2) {   // the plans that sweep with score16_kernel: the prepass on the same body (prepass16.hpp)
+			if (P.body16 && P.group == 16) {
+				if ((rc = anncur_ensure_dyn_lds((const void *)prepass16_kernel<KP>, Prepass16Cfg<KP>::LDS_BYTES)) != ANNCUR_OK) return rc;
+				hipLaunchKernelGGL((prepass16_kernel<KP>), dim3(p.n_wg), dim3(256), Prepass16Cfg<KP>::LDS_BYTES, st, pp);
+				pre16 = true;
+			}
+		}
+		if (!pre16 && P.group == 16)
 			hipLaunchKernelGGL((score_kernel<KP, 0, 16, false, false, QTV>), dim3(p.n_wg), dim3(256), 2 * Cfg::TILE_BYTES, st, pp);
-		else
+		else if (!pre16)
 			hipLaunchKernelGGL((score_kernel<KP, 0, 4, false, false, QTV>), dim3(p.n_wg), dim3(256), 2 * Cfg::TILE_BYTES, st, pp);
 	}
 	ANNCUR_LAUNCH_OK();
 	EV(1);
 	// 2. tau = k-th largest group maximum (beside it: the first chunk of the exact scan, anncur_eval_topk only)
-	int rc;
 	if ((rc = co_fork(co, st)) != ANNCUR_OK) return rc;
 	rc = launch_threshold(P, p.gmax, Q, k, ws, p.tau, p.tau_stride, st);
 	if (rc != ANNCUR_OK) return rc;
@@ -2308,21 +2331,24 @@ extern "C" int anncur_score_topk_plan(int64_t Q, int64_t I, int32_t Kp, int32_t 
  * stage_end[3], stage body[3] (0: 32x32x16 with the ballot filter, 1: with the exec-mask filter, 2: 16x16x32, 4: Kp = 512 with the
  * wave-level queue on 16x16x32 MFMAs), ring drain period[3],
  * threshold ladder (1: the sweep raises its thresholds in-launch, score16.hpp; 0: staged), rank of the ladder's top level,
- * tiles between two fetches of a wave's ladder counters (LADDER_PERIOD)} --
- * what a test needs to see that a variant flag was honoured */
+ * tiles between two fetches of a wave's ladder counters (LADDER_PERIOD),
+ * workspace offset of the prepass' group maxima in 256-byte units, group maxima per query (row pitch of that array), prepass kernel
+ * (1: prepass16_kernel, the sweep's 16x16x32 body; 0: score_kernel<KP, 0, ..>), prepass item splits} --
+ * what a test needs to see that a variant flag was honoured, and to read the group maxima back */
 extern "C" int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, int32_t *out, int32_t n_out) {
 	ANNCUR_REQUIRE((flags & ~TOPK_FLAGS) == 0, ANNCUR_E_INVALID, "score_topk_plan_ex: unknown flags 0x%x", flags);
 	ANNCUR_REQUIRE(ring_flag_ok(flags), ANNCUR_E_UNSUPPORTED, "score_topk_plan_ex: ANNCUR_TOPK_RING (the tile-ring sweep body) is retired");
 	const FusedPlan P = plan_any(Q, I, Kp, k, flags);
 	ANNCUR_REQUIRE(P.ok && out && n_out >= 0, ANNCUR_E_UNSUPPORTED, "score_topk_plan_ex: unsupported shape");
 	const bool wide = wide_kp(Kp);
-	int32_t v[20] = {P.n_st, P.n_tiles, P.S, P.capg, P.group, wide ? 4 : P.lg, P.QT, P.n_stages};
+	int32_t v[24] = {P.n_st, P.n_tiles, P.S, P.capg, P.group, wide ? 4 : P.lg, P.QT, P.n_stages};
 	v[17] = (!wide && P.ladder) ? 1 : 0; v[18] = (!wide && P.ladder) ? P.ladder_k2 : 0; v[19] = LADDER_PERIOD;
+	v[20] = (int32_t)(P.off_gmax / 256); v[21] = P.n_groups; v[22] = (!wide && P.body16 && P.group == 16) ? 1 : 0; v[23] = P.S0;
 	for (int g = 0; g < 3; ++g) {
 		const bool on = g < P.n_stages;
 		v[8 + g] = on ? P.stage_end[g] : 0; v[11 + g] = on ? (wide ? P.stage_pred[g] : P.bodyef ? 6 : P.body16 ? 2 : P.bodyq16 ? 4 : P.stage_pred[g]) : 0; v[14 + g] = on ? P.stage_flush[g] : 0;
 	}
-	for (int i = 0; i < n_out && i < 20; ++i) out[i] = v[i];
+	for (int i = 0; i < n_out && i < 24; ++i) out[i] = v[i];
 	return ANNCUR_OK;
 }
 

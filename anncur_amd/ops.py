@@ -691,6 +691,17 @@ def fused_plan(Q, I, Kp, k, leading_sample=False, mfma16=False, qt1=False, mfma3
 	return plan
 
 
+def fused_group_maxima(workspace, Q, I, Kp, k, leading_sample=False, mfma16=False, qt1=False, mfma32=False, ring=False, staged=False):
+	"""The prepass output the last score_topk_fused call on `workspace` (same shape and flags) left behind (diagnostics): a float32 view
+	[Q x n_groups] into the workspace, gmax[q, 2 j + g] = the maximum score of query q over the 16 rows r of sample tile j with
+	(r >> 2) & 1 == g, and {"prepass16": the prepass ran on the sweep's 16x16x32 body, "prepass_splits", "n_groups"}."""
+	out = (ctypes.c_int32 * 24)()
+	check(_lib.load().anncur_score_topk_plan_ex(Q, I, Kp, k, _topk_flags(leading_sample, mfma16, qt1, mfma32, ring, staged), out, 24), "score_topk_plan_ex")
+	off, n_groups = int(out[20]) * 256, int(out[21])
+	gmax = workspace[off:off + Q * n_groups * 4].view(torch.float32).view(Q, n_groups)
+	return gmax, {"prepass16": bool(out[22]), "prepass_splits": int(out[23]), "n_groups": n_groups}
+
+
 def _dense_scores(X, Et):
 	"""S = X @ Et^T with fp32 products and sums: the strided fp32-MFMA kernel of this library (any strides, fp32 or bf16 operands).
 	No vendor GEMM anywhere on the path."""

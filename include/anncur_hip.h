@@ -243,7 +243,8 @@ int anncur_eval_topk(const void *A, int a_dtype, int64_t lda, int32_t k_exact, f
 
 /* Measurement only: same as anncur_score_topk but records HIP events on `stream` between the four
  * launches, synchronises, and returns their durations in stage_ms[9] (host floats, milliseconds):
- * {prepass, threshold, sweep stage (sweep launches + the threshold refinements between them), select,
+ * {prepass (its workgroups also clear the workspace header: there is no memset launch in front of it), threshold,
+ *  sweep stage (sweep launches + the threshold refinements between them), select,
  *  sum of the sweep-kernel launches alone, number of sweep launches, and the duration of each of the up to
  *  three sweep launches (0 where the plan has fewer stages; anncur_score_topk_plan_ex gives their tile ranges)}.
  *  bench.py's live roofline figure is (2*Q*Kp*I / launches) / (stage_ms[4] / launches). */
@@ -254,12 +255,13 @@ int anncur_score_topk_timed(const void *X, int64_t ldx, const void *Et, int64_t 
                             int32_t flags, const int32_t *item_ids, void *stream, float *stage_ms);
 /* Plan introspection: out5 = {sample tiles, item tiles, item splits S, segment capacity, group size}. */
 int anncur_score_topk_plan(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t *out5);
-/* The plan a call with `flags` (ANNCUR_TOPK_*) would run: out[0 .. n_out), n_out <= 20 = {sample tiles, item tiles, item splits S,
+/* The plan a call with `flags` (ANNCUR_TOPK_*) would run: out[0 .. n_out), n_out <= 24 = {sample tiles, item tiles, item splits S,
  * segment capacity, group size, candidate segments per (query, item split) -- 2: 32x32x16 sweep, 1: 16x16x32 sweep, 4: wide
  * kernel --, 32-query sub-tiles per wave, number of sweep stages, stage_end[3] (tiles), body per stage[3] (0: 32x32x16 with the ballot
  * filter, 1: 32x32x16 with the exec-mask filter, 2: 16x16x32, 3 / 4: the Kp = 512 body with the wave-level queue on 32x32x16 / 16x16x32 MFMAs), ring
  * drain period per stage[3], threshold ladder (1: in-launch ladder, 0: none), rank of the ladder's top level among the sampled group
- * maxima, tiles between two fetches of a wave's ladder counters}.  Lets a caller (and the parity tests) see that a variant flag was
+ * maxima, tiles between two fetches of a wave's ladder counters, workspace offset of the prepass' group maxima (256-byte units), group
+ * maxima per query, prepass kernel (1: prepass16_kernel on the sweep's 16x16x32 body, 0: score_kernel<Kp, 0, ..>), prepass item splits}.  Lets a caller (and the parity tests) see that a variant flag was
  * honoured for the shape. */
 int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, int32_t *out, int32_t n_out);
 /* Diagnostics: mean number of candidates per query the sweep of the last call on `workspace` kept (reads the segment counts it left
