@@ -252,10 +252,11 @@ __global__ __launch_bounds__(256) void scale_copy_kernel(const float *__restrict
 }  // namespace
 
 extern "C" int anncur_sumsq(const float *A, int64_t n_rows, int64_t n_cols, int64_t lda, float *out, void *stream) {
-	ANNCUR_REQUIRE(A && out && n_rows >= 0 && n_cols >= 0 && lda >= n_cols, ANNCUR_E_INVALID, "sumsq: bad arguments");
+	ANNCUR_REQUIRE(out && n_rows >= 0 && n_cols >= 0 && lda >= n_cols, ANNCUR_E_INVALID, "sumsq: bad arguments");
 	hipStream_t st = (hipStream_t)stream;
 	ANNCUR_HIP_OK(hipMemsetAsync(out, 0, 4, st));
-	if (n_rows * n_cols == 0) return ANNCUR_OK;
+	if (n_rows * n_cols == 0) return ANNCUR_OK;   // (empty tensors have null data pointers: nothing to do comes first)
+	ANNCUR_REQUIRE(A, ANNCUR_E_INVALID, "sumsq: null pointer");
 	const int64_t blocks = ceil_div64(n_rows * n_cols, 256 * 8);
 	hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, st, A, n_rows, n_cols, lda, out);
 	ANNCUR_LAUNCH_OK();

@@ -2334,21 +2334,41 @@ extern "C" int anncur_score_topk_plan(int64_t Q, int64_t I, int32_t Kp, int32_t 
  * tiles between two fetches of a wave's ladder counters (LADDER_PERIOD),
  * workspace offset of the prepass' group maxima in 256-byte units, group maxima per query (row pitch of that array), prepass kernel
  * (1: prepass16_kernel, the sweep's 16x16x32 body; 0: score_kernel<KP, 0, ..>), prepass item splits} --
- * what a test needs to see that a variant flag was honoured, and to read the group maxima back */
-extern "C" int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, int32_t *out, int32_t n_out) {
-	ANNCUR_REQUIRE((flags & ~TOPK_FLAGS) == 0, ANNCUR_E_INVALID, "score_topk_plan_ex: unknown flags 0x%x", flags);
-	ANNCUR_REQUIRE(ring_flag_ok(flags), ANNCUR_E_UNSUPPORTED, "score_topk_plan_ex: ANNCUR_TOPK_RING (the tile-ring sweep body) is retired");
-	const FusedPlan P = plan_any(Q, I, Kp, k, flags);
-	ANNCUR_REQUIRE(P.ok && out && n_out >= 0, ANNCUR_E_UNSUPPORTED, "score_topk_plan_ex: unsupported shape");
-	const bool wide = wide_kp(Kp);
-	int32_t v[24] = {P.n_st, P.n_tiles, P.S, P.capg, P.group, wide ? 4 : P.lg, P.QT, P.n_stages};
+ * what a test needs to see that a variant flag was honoured, and to read the group maxima back
+ * (describe_plan fills those 24 words, then the tiles per item split of each stage [3]: anncur_eval_fused_plan returns them too) */
+static void describe_plan(const FusedPlan &P, bool wide, int32_t (&v)[27]) {
+	const int32_t head[8] = {P.n_st, P.n_tiles, P.S, P.capg, P.group, wide ? 4 : P.lg, P.QT, P.n_stages};
+	for (int i = 0; i < 27; ++i) v[i] = i < 8 ? head[i] : 0;
 	v[17] = (!wide && P.ladder) ? 1 : 0; v[18] = (!wide && P.ladder) ? P.ladder_k2 : 0; v[19] = LADDER_PERIOD;
 	v[20] = (int32_t)(P.off_gmax / 256); v[21] = P.n_groups; v[22] = (!wide && P.body16 && P.group == 16) ? 1 : 0; v[23] = P.S0;
 	for (int g = 0; g < 3; ++g) {
 		const bool on = g < P.n_stages;
 		v[8 + g] = on ? P.stage_end[g] : 0; v[11 + g] = on ? (wide ? P.stage_pred[g] : P.bodyef ? 6 : P.body16 ? 2 : P.bodyq16 ? 4 : P.stage_pred[g]) : 0; v[14 + g] = on ? P.stage_flush[g] : 0;
+		v[24 + g] = on ? P.stage_tps[g] : 0;
 	}
+}
+
+extern "C" int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, int32_t *out, int32_t n_out) {
+	ANNCUR_REQUIRE((flags & ~TOPK_FLAGS) == 0, ANNCUR_E_INVALID, "score_topk_plan_ex: unknown flags 0x%x", flags);
+	ANNCUR_REQUIRE(ring_flag_ok(flags), ANNCUR_E_UNSUPPORTED, "score_topk_plan_ex: ANNCUR_TOPK_RING (the tile-ring sweep body) is retired");
+	const FusedPlan P = plan_any(Q, I, Kp, k, flags);
+	ANNCUR_REQUIRE(P.ok && out && n_out >= 0, ANNCUR_E_UNSUPPORTED, "score_topk_plan_ex: unsupported shape");
+	int32_t v[27];
+	describe_plan(P, wide_kp(Kp), v);
 	for (int i = 0; i < n_out && i < 24; ++i) out[i] = v[i];
+	return ANNCUR_OK;
+}
+
+/* the plan anncur_eval_fused(_ex) runs for the cell (plan_fused(..., evalf = true): item order, static contiguous tile shares, evalf_kernel in
+ * every stage -- body 6): the 24 words of anncur_score_topk_plan_ex, then the tiles per item split of each stage [3].  Host code only. */
+extern "C" int anncur_eval_fused_plan(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t *out, int32_t n_out) {
+	ANNCUR_REQUIRE(Kp == 64 || Kp == 128 || Kp == 256, ANNCUR_E_UNSUPPORTED, "eval_fused_plan: Kp must be 64, 128 or 256 (got %d)", Kp);
+	const FusedPlan P = plan_fused(Q, I, Kp, k, false, false, false, false, true);
+	ANNCUR_REQUIRE(P.ok && out && n_out >= 0, ANNCUR_E_UNSUPPORTED, "eval_fused_plan: shape (Q=%lld, I=%lld, Kp=%d, k=%d) is outside the fused path",
+				   (long long)Q, (long long)I, Kp, k);
+	int32_t v[27];
+	describe_plan(P, false, v);
+	for (int i = 0; i < n_out && i < 27; ++i) out[i] = v[i];
 	return ANNCUR_OK;
 }
 

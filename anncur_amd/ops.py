@@ -691,6 +691,19 @@ def fused_plan(Q, I, Kp, k, leading_sample=False, mfma16=False, qt1=False, mfma3
 	return plan
 
 
+def eval_fused_plan(Q, I, Kp, k):
+	"""The plan eval_fused runs for the cell (host query, no GPU needed): the keys of fused_plan ("stage_pred" 6 = evalf_kernel, no ladder) and
+	"stage_tiles_per_split".  Item split s of stage g sweeps the tiles [begin + s * tps, min(begin + (s + 1) * tps, stage_end[g])), begin = the
+	previous stage's end: static contiguous shares in item order.  The exact matrix' error terms come from the first I // 32 tiles only."""
+	out = (ctypes.c_int32 * 27)()
+	check(_lib.load().anncur_eval_fused_plan(Q, I, Kp, k, out, 27), "eval_fused_plan")
+	v = [int(x) for x in out]
+	plan = dict(zip(("n_sample_tiles", "n_tiles", "splits", "segment_capacity", "group", "lg", "QT", "n_stages"), v[:8]))
+	n = plan["n_stages"]
+	plan["stage_end"], plan["stage_pred"], plan["stage_flush"], plan["stage_tiles_per_split"] = v[8:8 + n], v[11:11 + n], v[14:14 + n], v[24:24 + n]
+	return plan
+
+
 def fused_group_maxima(workspace, Q, I, Kp, k, leading_sample=False, mfma16=False, qt1=False, mfma32=False, ring=False, staged=False):
 	"""The prepass output the last score_topk_fused call on `workspace` (same shape and flags) left behind (diagnostics): a float32 view
 	[Q x n_groups] into the workspace, gmax[q, 2 j + g] = the maximum score of query q over the 16 rows r of sample tile j with

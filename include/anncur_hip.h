@@ -264,6 +264,12 @@ int anncur_score_topk_plan(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t 
  * maxima per query, prepass kernel (1: prepass16_kernel on the sweep's 16x16x32 body, 0: score_kernel<Kp, 0, ..>), prepass item splits}.  Lets a caller (and the parity tests) see that a variant flag was
  * honoured for the shape. */
 int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, int32_t *out, int32_t n_out);
+/* The plan anncur_eval_fused(_ex) runs for a cell (read-only, host code, no device needed): out[0 .. n_out), n_out <= 27 = the 24 words of
+ * anncur_score_topk_plan_ex (body per stage: 6 = evalf_kernel; no ladder) followed by the tiles per item split of each sweep stage [3].
+ * Item split s of stage g sweeps the 32-item tiles [begin_g + s tps_g, min(begin_g + (s + 1) tps_g, stage_end[g])) with begin_0 = 0 and
+ * begin_g = stage_end[g - 1]: what a test needs to put an element on the first and last column of every split and stage.
+ * ANNCUR_E_UNSUPPORTED where anncur_eval_fused_workspace_bytes gives 0. */
+int anncur_eval_fused_plan(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t *out, int32_t n_out);
 /* Diagnostics: mean number of candidates per query the sweep of the last call on `workspace` kept (reads the segment counts it left
  * behind; synchronises `stream`).  k ln(I / k) is what a sequential threshold can reach. */
 int anncur_score_topk_survivors(const void *workspace, int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, double *mean_per_query,
