@@ -11,7 +11,9 @@ Differences from the reference, all deliberate:
   * tensors given on the CPU are moved to the GPU, results come back on the device of the
     tensor passed to the call (CPU in -> CPU out), so reference call sites run unchanged;
   * ``compute_dtype``: "fp32" (default for fp32 inputs: 1e-4 score parity with the CPU path)
-    or "bf16" (default for bf16 inputs: the fused MFMA score+top-k kernel).
+    or "bf16" (default for bf16 inputs: the fused MFMA score+top-k kernel), or "bf16x3" (opt-in: fp32 operands split into
+    bf16 hi + lo parts, the fused kernel on the 3K-wide split operands, then an fp32 rescore of its candidates -- the fp32
+    route's values without materialising S_hat).
 U = pinv(W) (:47,:49): ``pinv_backend="numpy"`` is the reference's own ``numpy.linalg.pinv`` call on the
 host (U bit-identical); the default "auto" computes it on the GPU in fp64 (exact pseudo-inverse of the
 fp32 block, within 1e-5 of numpy's on the golden cases) and keeps the host call for ill-conditioned
@@ -37,6 +39,9 @@ def _is_sorted(idx_list):
 def _pinv_host(M):
 	"""numpy.linalg.pinv (LAPACK SVD, rcond=1e-15) on the fp32 values, as the reference does."""
 	return torch.from_numpy(np.linalg.pinv(M.detach().float().cpu().numpy()))
+
+
+COMPUTE_DTYPES = ("fp32", "bf16", "bf16x3")
 
 
 AUTO_COND_LIMIT = 1e3   # pinv_backend "auto": the device result is taken while cond_2(W) stays below this (numpy's fp32 SVD is then good to ~1e-4)
@@ -109,7 +114,7 @@ class CURApprox(object):
 		self.approx_preference = approx_preference
 		if compute_dtype is None:
 			compute_dtype = "bf16" if self._R.dtype == torch.bfloat16 else "fp32"
-		if compute_dtype not in ("fp32", "bf16"):
+		if compute_dtype not in COMPUTE_DTYPES:
 			raise ValueError(f"compute_dtype = {compute_dtype} not supported")
 		self.compute_dtype = compute_dtype
 
@@ -132,6 +137,7 @@ class CURApprox(object):
 		self._Et = None   # [m x kc] fp32: latent_cols transposed ("rows" preference)
 		self._Etp = None  # bf16 packed copy for the fused kernel
 		self._Etp_sorted = self._item_ids = None
+		self._split = None  # "bf16x3": the split-bf16 operands of E^T (_SplitOperands)
 		self._latent_rows, self._latent_cols = self._build_latent_row_cols(self._C, self._U, self._R, self.approx_preference)
 
 	# ------------------------------------------------------------------ the reference's attributes (matrix_approx_zeshel.py:36-51)
@@ -179,6 +185,8 @@ class CURApprox(object):
 			if self.compute_dtype == "bf16" and kp is not None:
 				self._Etp = ops.pack_bf16(self._Et, kp, row_multiple=32)               # item order: error terms, dense route
 				self._Etp_sorted, self._item_ids = _norm_sorted_pack(self._Et, kp)     # norm order: fused top-k
+			if self.compute_dtype == "bf16x3":
+				self._split = _SplitOperands.build(self._Et)
 		else:
 			raise NotImplementedError(f"approx_preference = {approx_preference} not supported")
 		return latent_rows, latent_cols
@@ -230,9 +238,11 @@ class CURApprox(object):
 			raise NotImplementedError("This is not designed to give good approx of rows as C and U matrix are multiplied together. Build index w/ approx_preference = rows instead.")
 		X = self._to_dev(sparse_rows)
 		Q = X.shape[0]
+		if self._split is not None and self._split.takes(Q, self.m, k):
+			return self._split.topk(X, self._Et, k)
 		if self._Etp is not None and ops.fused_supported(Q, self.m, self._Etp.shape[1], k):
 			return ops.score_topk_fused(ops.pack_bf16(X, self._Etp.shape[1]), self._Etp_sorted, self.m, k, leading_sample=True, item_ids=self._item_ids)
-		Et = self._Et if self.compute_dtype == "fp32" else (self._Etp[:self.m, :X.shape[1]] if self._Etp is not None else self._Et)
+		Et = self._Et if self.compute_dtype != "bf16" else (self._Etp[:self.m, :X.shape[1]] if self._Etp is not None else self._Et)
 		if self.compute_dtype == "bf16" and X.dtype != torch.bfloat16:
 			X = ops.convert(X, torch.bfloat16)
 		return ops.score_topk_dense(X, Et, k)
@@ -259,6 +269,8 @@ class CURApprox(object):
 		"""Per-row sum (S_hat - A)^2 and sum A^2 (a11) without materialising S_hat.  On the bf16 route S_hat is the one the retrieval
 		ranks (bf16 item embeddings), computed on the sweep's MFMA loop."""
 		X, A = self._to_dev(sparse_rows), self._to_dev(exact_rows)
+		if self._split is not None and ops.approx_error_packed_ok(self._split.kp, A):
+			return self._split.approx_error(X, self._Et, A)
 		if self.compute_dtype == "bf16" and self._Etp is not None and ops.approx_error_packed_ok(self._Etp.shape[1], A):
 			return ops.approx_error_packed(ops.pack_bf16(X, self._Etp.shape[1]), self._Etp, A, self.m)
 		return ops.approx_error(X, self._Et, A)
@@ -273,6 +285,37 @@ def _norm_sorted_pack(Et, kp):
 	return ops.pack_bf16(ops.gather_rows(Et, order), kp, row_multiple=32), order
 
 
+class _SplitOperands(object):
+	"""The item side of the "bf16x3" route: E^T [m x K] fp32 split into bf16 hi + lo parts and packed as [hi | lo | hi]
+	rows of width Kp = split_kp(K), once in the descending-norm order of _norm_sorted_pack (the fused top-k, with the map back to item
+	ids) and -- lazily, only when the error sums ask for it -- once in item order.  kp is None where 3 K is too wide for the fused
+	kernels: every call then takes the fp32 route."""
+
+	def __init__(self, kp, sorted_pack, item_ids):
+		self.kp, self.sorted, self.item_ids = kp, sorted_pack, item_ids
+		self._item_order = None
+
+	@classmethod
+	def build(cls, Et):
+		kp = ops.split_kp(Et.shape[1])
+		if kp is None:
+			return cls(None, None, None)
+		order = ops.descending_norm_order(Et if Et.dtype == torch.float32 else ops.convert(Et, torch.float32))
+		return cls(kp, ops.pack_split_bf16(ops.gather_rows(Et, order), 1, kp, row_multiple=32), order)
+
+	def takes(self, Q, m, k):
+		return self.kp is not None and k <= min(m, ops._lib.MAX_TOPK) and ops.fused_supported(Q, m, self.kp, ops.split_candidates(m, k))
+
+	def topk(self, X, Et, k):
+		return ops.score_topk_split(X, Et, self.sorted, Et.shape[0], k, item_ids=self.item_ids, leading_sample=True)
+
+	def approx_error(self, X, Et, A):
+		"""a11 on the split operands (the sweep's bf16 MFMA loop, Kp <= 512): S_hat within (2^-16 + 3K 2^-23) |X|.|E|^T of the fp32 one."""
+		if self._item_order is None:
+			self._item_order = ops.pack_split_bf16(Et, 1, self.kp, row_multiple=32)
+		return ops.approx_error_packed(ops.pack_split_bf16(X, 0, self.kp), self._item_order, A, Et.shape[0])
+
+
 class CURRowIndex(object):
 	"""The "rows"-preference index alone: built from the anchor rows R [kr x m] and the anchor columns' ids, without the
 	(n x kc) matrix of every query's anchor scores.  This is what a rank of a row-sharded evaluation holds: R assembled by one
@@ -285,6 +328,8 @@ class CURRowIndex(object):
 		self.col_idxs = col_idxs
 		if compute_dtype is None:
 			compute_dtype = "bf16" if rows.dtype == torch.bfloat16 else "fp32"
+		if compute_dtype not in COMPUTE_DTYPES:
+			raise ValueError(f"compute_dtype = {compute_dtype} not supported")
 		self.compute_dtype = compute_dtype
 		W = ops.gather_cols(rows, col_idxs)                      # kr x kc
 		self.U = _pinv(W, rows.device, pinv_backend)             # kc x kr
@@ -294,13 +339,16 @@ class CURRowIndex(object):
 		if compute_dtype == "bf16" and kp is not None:
 			self._Etp = ops.pack_bf16(self._Et, kp, row_multiple=32)
 			self._Etp_sorted, self._item_ids = _norm_sorted_pack(self._Et, kp)
+		self._split = _SplitOperands.build(self._Et) if compute_dtype == "bf16x3" else None
 
 	def topk(self, X, k):
 		"""X [q x kc]: the queries' exact scores against the anchor items -> (values f32, indices int32) on the GPU."""
 		Q = X.shape[0]
+		if self._split is not None and self._split.takes(Q, self.m, k):
+			return self._split.topk(X, self._Et, k)
 		if self._Etp is not None and ops.fused_supported(Q, self.m, self._Etp.shape[1], k):
 			return ops.score_topk_fused(ops.pack_bf16(X, self._Etp.shape[1]), self._Etp_sorted, self.m, k, leading_sample=True, item_ids=self._item_ids)
-		Et = self._Et if self.compute_dtype == "fp32" or self._Etp is None else self._Etp[:self.m, :X.shape[1]]
+		Et = self._Et if self.compute_dtype != "bf16" or self._Etp is None else self._Etp[:self.m, :X.shape[1]]
 		if self.compute_dtype == "bf16" and X.dtype != torch.bfloat16:
 			X = ops.convert(X, torch.bfloat16)
 		return ops.score_topk_dense(X, Et, k)
@@ -344,6 +392,8 @@ class CURRowIndex(object):
 		return exact, approx, err, nrm
 
 	def approx_error_rows(self, X, exact_rows):
+		if self._split is not None and ops.approx_error_packed_ok(self._split.kp, exact_rows):
+			return self._split.approx_error(X, self._Et, exact_rows)
 		if self.compute_dtype == "bf16" and self._Etp is not None and ops.approx_error_packed_ok(self._Etp.shape[1], exact_rows):
 			return ops.approx_error_packed(ops.pack_bf16(X, self._Etp.shape[1]), self._Etp, exact_rows, self.m)
 		return ops.approx_error(X, self._Et, exact_rows)

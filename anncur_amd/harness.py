@@ -47,8 +47,9 @@ def _subset_metrics(counts_row, rows, k):
 
 
 # ------------------------------------------------------------------------------------------------ entry point A
-def run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, seed, exact_cache=None, pinv_backend="auto"):
-	"""One seed of one grid cell -> {"anchor": {...}, "non_anchor": {...}, "all": {...}} (crossenc.py:47-158)."""
+def run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, seed, exact_cache=None, pinv_backend="auto", compute_dtype=None):
+	"""One seed of one grid cell -> {"anchor": {...}, "non_anchor": {...}, "all": {...}} (crossenc.py:47-158).
+	compute_dtype: CURApprox's (None = by the matrix' dtype; "bf16x3" = the fp32-parity route on the bf16 matrix cores)."""
 	n_ments, n_ents = A_dev.shape
 	rng = np.random.default_rng(seed=seed)
 	row_idxs = _select(rng, n_ments, n_ment_anchors)          # rows first, then columns, same generator
@@ -57,9 +58,9 @@ def run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, 
 	cols = ops.gather_cols(A_dev, col_idxs)
 	non_anchor = sorted(set(range(n_ments)) - set(int(i) for i in row_idxs))
 	if approx_method == "cur":
-		cur = CURApprox(rows=rows, cols=cols, row_idxs=row_idxs, col_idxs=col_idxs, approx_preference="rows", pinv_backend=pinv_backend)
+		cur = CURApprox(rows=rows, cols=cols, row_idxs=row_idxs, col_idxs=col_idxs, approx_preference="rows", pinv_backend=pinv_backend, compute_dtype=compute_dtype)
 	elif approx_method == "cur_oracle":
-		cur = CURApprox(rows=rows, cols=cols, row_idxs=row_idxs, col_idxs=col_idxs, approx_preference="rows", A=A_dev, pinv_backend=pinv_backend)
+		cur = CURApprox(rows=rows, cols=cols, row_idxs=row_idxs, col_idxs=col_idxs, approx_preference="rows", A=A_dev, pinv_backend=pinv_backend, compute_dtype=compute_dtype)
 	else:
 		raise NotImplementedError(f"approx_method = {approx_method} not supported")
 	# approximate retrieval for EVERY query row + the per-row error terms: one sweep where the fused route takes the cell (cur.eval_rows)
@@ -85,11 +86,11 @@ def run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, 
 	return {"anchor": score(row_idxs), "non_anchor": score(non_anchor), "all": score(list(range(n_ments)))}
 
 
-def run_approx_eval(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, n_seeds, exact_cache=None, pinv_backend="auto"):
+def run_approx_eval(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, n_seeds, exact_cache=None, pinv_backend="auto", compute_dtype=None):
 	"""Mean over seeds (crossenc.py:162-200)."""
 	acc = defaultdict(lambda: defaultdict(list))
 	for seed in range(n_seeds):
-		res = run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, seed, exact_cache, pinv_backend)
+		res = run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, seed, exact_cache, pinv_backend, compute_dtype)
 		for ment_type, d in res.items():
 			for metric, val in d.items():
 				acc[ment_type][metric].append(float(val))
@@ -171,7 +172,7 @@ def default_grids_A(total_n_ment, total_n_ent):
 	}
 
 
-def run_entry_A(A_dev, grids, n_seeds, progress=None, pinv_backend="auto"):
+def run_entry_A(A_dev, grids, n_seeds, progress=None, pinv_backend="auto", compute_dtype=None):
 	"""-> res[method]["top_k=.."]["k_retvr=.."]["anc_n_m=..~anc_n_e=.."][anchor|non_anchor|all][metric]  (crossenc.py:349-383)."""
 	total_n_ment, total_n_ent = A_dev.shape
 	res = defaultdict(lambda: defaultdict(lambda: defaultdict(dict)))
@@ -186,7 +187,7 @@ def run_entry_A(A_dev, grids, n_seeds, progress=None, pinv_backend="auto"):
 			if progress:
 				progress(method, ctr, len(cells))
 			res[method][f"top_k={top_k}"][f"k_retvr={kr}"][f"anc_n_m={nm}~anc_n_e={ne}"] = \
-				run_approx_eval(method, A_dev, nm, ne, top_k, kr, n_seeds, exact_cache, pinv_backend)
+				run_approx_eval(method, A_dev, nm, ne, top_k, kr, n_seeds, exact_cache, pinv_backend, compute_dtype)
 	return {m: {a: {b: dict(c) for b, c in d.items()} for a, d in v.items()} for m, v in res.items()}
 
 

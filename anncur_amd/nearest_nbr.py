@@ -36,7 +36,9 @@ def _faiss_pad(v, i, nq, k, k_eff):
 
 class FlatIPIndex:
 	"""Exact maximum-inner-product search on the GPU.  fp32 by default (dense fp32-MFMA GEMM + exact scan);
-	dtype="bf16" uses the fused score+top-k kernel when the dimension fits (d <= 512)."""
+	dtype="bf16" uses the fused score+top-k kernel when the dimension fits (d <= 4096: the register-resident bodies up to 512, the
+	K-general wide kernel above); dtype="bf16x3" keeps fp32 parity on that kernel: the stored fp32 vectors split into bf16 hi + lo
+	parts (3 d <= 4096), the fused kernel for the candidates, an fp32 rescore for the values -- those of the fp32 route bit for bit."""
 
 	def __init__(self, d, dtype="fp32", device=None):
 		self.d = d
@@ -45,6 +47,7 @@ class FlatIPIndex:
 		self.ntotal = 0
 		self._X = None
 		self._Xp = self._ids = None  # packed bf16 copy in descending-norm order + row -> id map (built at the first bf16 search)
+		self._split = None           # dtype "bf16x3": the split-bf16 copy (built at the first search)
 		self.nprobe = 1  # accepted for FAISS API compatibility
 
 	def add(self, embeds):
@@ -52,7 +55,7 @@ class FlatIPIndex:
 		assert x.dim() == 2 and x.shape[1] == self.d, f"expected [n, {self.d}] embeddings"
 		self._X = x if self._X is None else torch.cat([self._X, x], dim=0)
 		self.ntotal = self._X.shape[0]
-		self._Xp = None
+		self._Xp = self._split = None
 
 	def train(self, embeds):  # FAISS API compatibility (flat index needs no training)
 		return None
@@ -62,6 +65,12 @@ class FlatIPIndex:
 		q = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(self.device)
 		k_eff = min(k, self.ntotal)
 		kp = ops.padded_k(self.d)
+		if self.dtype == "bf16x3":
+			if self._split is None:
+				from .cur import _SplitOperands
+				self._split = _SplitOperands.build(self._X)
+			if self._split.takes(q.shape[0], self.ntotal, k_eff):
+				return _faiss_pad(*self._split.topk(q, self._X, k_eff), q.shape[0], k, k_eff)
 		if self.dtype == "bf16" and kp is not None and ops.fused_supported(q.shape[0], self.ntotal, kp, k_eff):
 			if self._Xp is None:
 				from .cur import _norm_sorted_pack
@@ -194,6 +203,9 @@ class IVFFlatIPIndex:
 
 
 def build_flat_or_ivff_index(embeds, force_exact_search, probe_mult_factor=1, dtype="fp32", device=None):
+	"""models/nearest_nbr.py:24-55.  dtype: "fp32", "bf16", or "bf16x3" -- the flat index' fp32-parity route on the bf16 matrix cores.
+	The IVF lists stay fp32 / bf16: above 11 000 vectors without force_exact_search, dtype="bf16x3" raises the ValueError IVFFlatIPIndex
+	raises for a dtype it does not know."""
 	LOGGER.info(f"Beginning indexing given {len(embeds)} embeddings")
 	if type(embeds) is not np.ndarray:
 		embeds = embeds.detach().cpu().numpy() if torch.is_tensor(embeds) else np.array(embeds)

@@ -433,6 +433,89 @@ def pack_bf16(M, Kp, row_multiple=1):
 	return out
 
 
+def split_kp(K):
+	"""Inner dimension of the split-bf16 ("bf16x3") operands for a logical K: padded_k(3 K) -- three K-wide segments per row --, or None."""
+	return padded_k(3 * K)
+
+
+@_on_device
+def pack_split_bf16(M, role, Kp=None, row_multiple=1, out=None):
+	"""[n x K] (f32/bf16) -> bf16 [ceil(n/row_multiple)*row_multiple x Kp] split operand of the bf16x3 route: with hi = bf16(x) and
+	lo = bf16(x - hi), role 0 (queries) holds [lo | hi | hi | 0], role 1 (items) [hi | lo | hi | 0], so that a row of one times a row of
+	the other is lo.hi + hi.lo + hi.hi.  Kp defaults to split_kp(K).  The kernel writes the zero padding itself (no memset).
+	out: a contiguous bf16 [n_pad x Kp] tensor to fill (every element is overwritten)."""
+	_dev(M)
+	n, K = M.shape
+	if role not in (0, 1):
+		raise ValueError("pack_split_bf16: role is 0 (query rows) or 1 (item rows)")
+	if Kp is None:
+		Kp = split_kp(K)
+	if Kp is None or Kp < 3 * K or Kp % 8 != 0 or K < 1:
+		raise ValueError(f"pack_split_bf16: K = {K} does not fit Kp = {Kp} (need 1 <= 3 K <= Kp, Kp a multiple of 8)")
+	n_pad = -(-n // row_multiple) * row_multiple
+	if out is None:
+		out = torch.empty((n_pad, Kp), dtype=torch.bfloat16, device=M.device)
+	elif tuple(out.shape) != (n_pad, Kp) or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != M.device:
+		raise ValueError("pack_split_bf16: out must be a contiguous bf16 [n_pad x Kp] tensor on M's device")
+	M = _rowmajor(M)
+	check(_lib.load().anncur_pack_split_bf16(_p(M), _dt(M), _ld(M), n, K, role, _p(out), Kp, n_pad, _stream()), "pack_split_bf16")
+	return out
+
+
+@_on_device
+def rescore_topk(X, Et, cand_idx, k_out):
+	"""The k_out best of each query's candidates by the TRUE fp32 score: for i in cand_idx[q] (int32 [Q x n_cand], distinct; < 0 or
+	>= I: a hole) s = the k-ordered fp32 fmaf chain of <X[q], Et[i]> -- bit for bit the element gemm(X, Et.t()) holds --, then
+	TopK(values f32 [Q x k_out], item ids int32) by score descending, ties by the smaller id, padded with (-inf, -1).
+	(reference: the scores eval/matrix_approx_zeshel.py:118,126 and models/nearest_nbr.py:36-38 rank by.)"""
+	_dev(X, Et, cand_idx)
+	X, Et = _rowmajor(X), _rowmajor(Et)
+	if cand_idx.dim() != 2 or cand_idx.dtype != torch.int32 or (cand_idx.shape[1] > 1 and cand_idx.stride(1) != 1):
+		cand_idx = cand_idx.to(torch.int32).contiguous()
+	Q, K = X.shape
+	I = Et.shape[0]
+	n_cand = cand_idx.shape[1]
+	if Et.shape[1] != K or cand_idx.shape[0] != Q:
+		raise ValueError("rescore_topk: X [Q x K], Et [I x K], cand_idx [Q x n_cand]")
+	val = torch.empty((Q, k_out), dtype=torch.float32, device=X.device)
+	idx = torch.empty((Q, k_out), dtype=torch.int32, device=X.device)
+	scratch = _ScoreScratch.get(max(Q * n_cand, 1), X.device)
+	check(_lib.load().anncur_rescore_topk(_p(X), _dt(X), _ld(X), _p(Et), _dt(Et), _ld(Et), K, _p(cand_idx), _ld(cand_idx), n_cand, Q, I, k_out,
+										  _p(val), _p(idx), _p(scratch), _stream()), "rescore_topk")
+	return TopK(val, idx)
+
+
+SPLIT_RESCORE_EXTRA = 16   # candidates the bf16x3 sweep retrieves beyond k before the fp32 rescore: max(this, k // 8) (DESIGN 4.4a has the table)
+
+
+def split_rescore_extra(k):
+	return max(SPLIT_RESCORE_EXTRA, k // 8)
+
+
+def split_candidates(I, k, extra=None):
+	"""Candidates per query the bf16x3 sweep retrieves for a final top-k of k: min(I, MAX_TOPK, k + extra)."""
+	return min(I, _lib.MAX_TOPK, k + (split_rescore_extra(k) if extra is None else extra))
+
+
+@_on_device
+def score_topk_split(X, Et_f32, Etp_split, I, k, item_ids=None, leading_sample=False, extra=None):
+	"""The bf16x3 route: top-k of S_hat = X.E at fp32 parity without writing S_hat.  X [Q x K] (f32/bf16), Et_f32 [I x K] the item
+	embeddings in ITEM order, Etp_split = pack_split_bf16(rows of Et_f32, role 1, row_multiple=32), its rows in item order or -- with
+	item_ids / leading_sample as for score_topk_fused -- in the index builder's order.  The fused sweep retrieves
+	kc = min(I, MAX_TOPK, k + extra) candidates on the split operands (scores within (2^-16 + 3K 2^-23) |X|.|E|^T of exact), rescore_topk
+	ranks them by the true fp32 score: values bit-equal to the dense fp32 route's.  Raises where the shape is outside the fused path."""
+	_dev(X, Et_f32, Etp_split)
+	Q, K = X.shape
+	Kp = Etp_split.shape[1]
+	kc = split_candidates(I, k, extra)
+	if Kp < 3 * K or Et_f32.shape[0] != I or Et_f32.shape[1] != K or k > kc:
+		raise ValueError("score_topk_split: X [Q x K], Et_f32 [I x K], Etp_split [ceil32(I) x Kp >= 3 K], k <= min(I, MAX_TOPK)")
+	if not fused_supported(Q, I, Kp, kc):
+		raise _lib.AnncurHipError(f"score_topk_split: shape (Q={Q}, I={I}, Kp={Kp}, k={kc}) is outside the fused path")
+	cand = score_topk_fused(pack_split_bf16(X, 0, Kp), Etp_split, I, kc, leading_sample=leading_sample, item_ids=item_ids)
+	return rescore_topk(X, Et_f32, cand.indices, k)
+
+
 FUSED_WS_LIMIT_BYTES = 32 << 30   # default workspace above this size -> score_topk_fused runs the queries in row chunks
 
 

@@ -55,7 +55,7 @@ def plot(res_dir, method_vals):
 	return made
 
 
-def run(base_res_dir, data_info, n_seeds, plot_only, misc, arg_dict, grid_overrides, dtype, device, pinv_backend="auto", score_chunks=None):
+def run(base_res_dir, data_info, n_seeds, plot_only, misc, arg_dict, grid_overrides, dtype, device, pinv_backend="auto", score_chunks=None, compute_dtype=None):
 	from anncur_amd import harness
 	data_name, data_fname = data_info
 	world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -109,7 +109,7 @@ def run(base_res_dir, data_info, n_seeds, plot_only, misc, arg_dict, grid_overri
 			if torch.device(device).type == "cuda":
 				torch.cuda.set_device(device)   # the launch stream and torch's allocations follow --device
 			A_dev = chunked["A_local"] if chunked is not None else harness.to_device_matrix(scores, device, dtype)
-			eval_res = harness.run_entry_A(A_dev, grids, n_seeds, progress, pinv_backend)
+			eval_res = harness.run_entry_A(A_dev, grids, n_seeds, progress, pinv_backend, compute_dtype)
 		eval_res["other_args"] = other_args
 		with open(f"{res_dir}/retrieval_wrt_exact_crossenc.json", "w") as fout:
 			json.dump(obj=eval_res, fp=fout, indent=4)
@@ -121,9 +121,8 @@ def run(base_res_dir, data_info, n_seeds, plot_only, misc, arg_dict, grid_overri
 	return res_dir
 
 
-def main(argv=None):
-	data_dir = "../../data/zeshel"
-	worlds = get_zeshel_world_info()
+def build_parser(worlds=None, data_dir="../../data/zeshel"):
+	worlds = get_zeshel_world_info() if worlds is None else worlds
 	parser = argparse.ArgumentParser(description="Run eval for various retrieval methods wrt exact crossencoder scores. "
 												 "This evaluation does not use ground-truth entity information into account")
 	parser.add_argument("--data_name", type=str, choices=[w for _, w in worlds], help="Dataset name")
@@ -147,9 +146,17 @@ def main(argv=None):
 	parser.add_argument("--pinv", type=str, default="auto", choices=["numpy", "device", "auto", "device32"],
 						help="pseudo-inverse: numpy = the reference's numpy.linalg.pinv on the host (bit-identical U); device = fp64 Newton-Schulz on the GPU "
 							 "(exact pseudo-inverse of the fp32 block, rounded once); auto = device while the block is well conditioned, else numpy")
+	parser.add_argument("--compute_dtype", type=str, default="auto", choices=["auto", "fp32", "bf16", "bf16x3"],
+						help="arithmetic of the CUR retrieval: auto = by --dtype (fp32 matrix -> dense fp32 route, bf16 -> fused bf16 kernel); bf16x3 = for --dtype fp32: "
+							 "operands split into bf16 hi + lo parts on the fused kernel, candidates rescored in fp32 (the fp32 route's values, S_hat never written)")
 	parser.add_argument("--score_chunks", type=str, nargs="+", default=None,
 						help="the producer's per-chunk score pickles (mention order) instead of the combined file: ingested chunk by chunk, row-sharded under torchrun")
-	args = parser.parse_args(argv)
+	return parser
+
+
+def main(argv=None):
+	worlds = get_zeshel_world_info()
+	args = build_parser(worlds).parse_args(argv)
 	if args.bi_model_file != "":
 		raise SystemExit("--bi_model_file: the bi-encoder baseline needs the reference's BERT models and is out of scope of this build")
 	misc = "_" + args.misc if args.misc != "" else ""
@@ -159,7 +166,8 @@ def main(argv=None):
 			   n_seeds=args.n_seeds, plot_only=bool(args.plot_only), misc=misc, arg_dict=dict(args.__dict__),
 			   grid_overrides={"eval_methods": args.eval_methods, "n_ment_anchors_vals": args.n_ment_anchors_vals,
 							   "n_ent_anchors_vals": args.n_ent_anchors_vals, "top_k_vals": args.top_k_vals, "top_k_retr_vals": args.top_k_retr_vals},
-			   dtype=args.dtype, device=torch.device(args.device), pinv_backend=args.pinv, score_chunks=args.score_chunks)
+			   dtype=args.dtype, device=torch.device(args.device), pinv_backend=args.pinv, score_chunks=args.score_chunks,
+			   compute_dtype=None if args.compute_dtype == "auto" else args.compute_dtype)
 
 
 if __name__ == "__main__":

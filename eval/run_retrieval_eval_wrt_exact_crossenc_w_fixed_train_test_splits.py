@@ -52,7 +52,7 @@ def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, de
 	LOGGER.info(f"Computing approximate test mention-to-entity scores using method={curr_method}")
 	if curr_method == "cur":
 		A_train_dev = harness.to_device_matrix(A_train, device, args.dtype)
-		res = harness.run_eval_method_cur(A_test_dev, A_train_dev, seed, grids,
+		res = harness.run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None if args.compute_dtype == "auto" else args.compute_dtype,
 										  progress=lambda j, n: LOGGER.info(f"anchor count {j + 1}/{n}"), pinv_backend=args.pinv)
 	elif curr_method in ("bienc", "tfidf"):
 		if not (args.mention_embeds_file and args.entity_embeds_file):
@@ -103,8 +103,8 @@ def run(args, device):
 	return res_file
 
 
-def main(argv=None):
-	worlds = get_zeshel_world_info()
+def build_parser(worlds=None):
+	worlds = get_zeshel_world_info() if worlds is None else worlds
 	parser = argparse.ArgumentParser(description="Run eval for various retrieval methods wrt exact crossencoder scores using a fixed train/test "
 												 "split. This evaluation does not use ground-truth entity information into account")
 	parser.add_argument("--data_name", type=str, choices=[w for _, w in worlds], help="Dataset name")
@@ -133,7 +133,15 @@ def main(argv=None):
 	parser.add_argument("--pinv", type=str, default="auto", choices=["numpy", "device", "auto", "device32"],
 						help="pseudo-inverse: numpy = the reference's numpy.linalg.pinv on the host (bit-identical U); device = fp64 Newton-Schulz on the GPU "
 							 "(exact pseudo-inverse of the fp32 block, rounded once); auto = device while the block is well conditioned, else numpy")
-	args = parser.parse_args(argv)
+	parser.add_argument("--compute_dtype", type=str, default="auto", choices=["auto", "fp32", "bf16", "bf16x3"],
+						help="arithmetic of the CUR retrieval: auto = by --dtype (fp32 matrix -> dense fp32 route, bf16 -> fused bf16 kernel); bf16x3 = for --dtype fp32: "
+							 "operands split into bf16 hi + lo parts on the fused kernel, candidates rescored in fp32 (the fp32 route's values, S_hat never written)")
+	return parser
+
+
+def main(argv=None):
+	worlds = get_zeshel_world_info()
+	args = build_parser(worlds).parse_args(argv)
 	_ = get_dataset_info(data_dir="../../data/zeshel", res_dir=args.res_dir, worlds=worlds)  # kept for parity with the reference's main()
 	LOGGER.info(f"Running inference for world = {args.data_name}")
 	return run(args, torch.device(args.device))

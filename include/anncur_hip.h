@@ -228,6 +228,32 @@ int anncur_score_topk_ex(const void *X, int64_t ldx, const void *Et, int64_t lde
                          void *workspace, size_t workspace_bytes,
                          int32_t flags, const int32_t *item_ids, void *stream);
 
+/* a6+a7 at fp32 parity on the bf16 matrix cores: the split-bf16 ("bf16x3") route -------------------------------------------------
+ *   CURApprox.get_complete_row + topk_in_row on FloatTensors      eval/matrix_approx_zeshel.py:118,126
+ *   faiss IndexFlatIP.add / .search on float32 vectors            models/nearest_nbr.py:36-38
+ * The fp32 route materialises S_hat with anncur_gemm and scans it; this one keeps S_hat unwritten.  An fp32 operand is split as
+ * x = hi + lo, hi = bf16(x), lo = bf16(x - hi) (round-to-nearest-even; x - hi is exact), and  x.e ~= lo_x hi_e + hi_x lo_e + hi_x hi_e
+ * is ONE bf16 inner product of length 3K, so anncur_score_topk_ex sweeps the packed operands unchanged with Kp >= 3K; the dropped
+ * lo.lo term and the roundings of lo leave |S_split - S| <= (2^-16 + 3K 2^-23) (|X|.|E|^T) elementwise.  The few candidates it
+ * returns are then rescored in true fp32 (anncur_rescore_topk): the values the caller sees are those of anncur_gemm bit for bit.
+ *
+ * anncur_pack_split_bf16: src [n_rows x K] (F32 or BF16, row pitch lds_) -> dst bf16 [n_rows_pad x ldd], ldd >= 3K a multiple of 8,
+ *   dst 16-byte aligned.  role 0 (query rows) writes [ lo | hi | hi ], role 1 (item rows) [ hi | lo | hi ], each segment K wide at
+ *   element offsets 0, K, 2K.  The kernel writes EVERY element of dst -- zeros in columns 3K..ldd and in rows n_rows..n_rows_pad --,
+ *   the caller clears nothing.  Where hi is not finite (inf, NaN, a finite x that rounds to inf) lo = 0; BF16 input gives lo = 0. */
+int anncur_pack_split_bf16(const void *src, int src_dtype, int64_t lds_, int64_t n_rows, int64_t K, int role,
+                           void *dst, int64_t ldd, int64_t n_rows_pad, void *stream);
+/* anncur_rescore_topk: for query q and each of its n_cand candidate ids i = cand_idx[q*ld_idx + j] (distinct per row; an id < 0 or
+ *   >= I is a hole and is skipped), s = fmaf(X[q,K-1], Et[i,K-1], ... fmaf(X[q,0], Et[i,0], 0)) in fp32, k ascending -- the k-ordered
+ *   fmaf chain anncur_gemm is bit for bit -- and the k_out best: out_val float[Q x k_out], out_idx int32[Q x k_out] (item ids), score
+ *   descending, ties by the smaller id, NaN never selected, (-inf, -1) where fewer than k_out valid candidates exist.
+ *   X [Q x K] (x_dtype, pitch ldx), Et [I x K] (e_dtype, pitch lde; rows are read with 16-byte loads when Et and its pitch are 16-byte
+ *   aligned).  k_out <= n_cand <= ANNCUR_MAX_TOPK.  An HBM gather of Q n_cand K elements; no matrix cores.
+ *   Workspace: scratch = float[Q x n_cand] (4 Q n_cand bytes, caller-owned, contents undefined on entry and exit). */
+int anncur_rescore_topk(const void *X, int x_dtype, int64_t ldx, const void *Et, int e_dtype, int64_t lde, int64_t K,
+                        const int32_t *cand_idx, int64_t ld_idx, int32_t n_cand, int64_t Q, int64_t I, int32_t k_out,
+                        float *out_val, int32_t *out_idx, float *scratch, void *stream);
+
 /* a8 per-query evaluation loop: exact top-k of the stored scores AND the approximate retrieval, in one call ----------------------
  *   curr_ment_scores.topk(top_k) ; approx_curr_ment_scores.topk(top_k_retvr)          ...crossenc.py:97-106 ; ..._splits.py:80-89
  * = anncur_rowwise_topk(A, k_exact) + anncur_score_topk_ex(X, Et, k_retvr), same results, scheduled together: the retrieval is a chain
