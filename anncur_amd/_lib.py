@@ -61,6 +61,7 @@ SIGNATURES = {
 	"anncur_pack_split_bf16": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p]),
 	"anncur_rescore_topk": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int64, c_int64, c_int32,
 									c_void_p, c_void_p, c_void_p, c_void_p]),
+	"anncur_filter_topk": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
 	"anncur_eval_topk": (c_int, [c_void_p, c_int, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32,
 								 c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_void_p, c_void_p]),
 	"anncur_score_topk_timed": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p,

@@ -232,23 +232,26 @@ class CURApprox(object):
 		return self._back(ops.gemm(self._to_dev(sparse_rows), self._latent_cols), sparse_rows)
 
 	# ------------------------------------------------------------------ retrieval (a6 + a7)
-	def topk_in_row_device(self, sparse_rows, k):
-		"""(values f32 [Q,k], indices int32 [Q,k]) on the GPU; S_hat is never materialised on the bf16 route."""
+	def topk_in_row_device(self, sparse_rows, k, exclude=None):
+		"""(values f32 [Q,k], indices int32 [Q,k]) on the GPU; S_hat is never materialised on the bf16 route.
+		exclude: items left out of the result (ops.exclusion: one list for all queries, one per query, or a -1 padded [Q x w] array; rows
+		with fewer than k items left end in (-inf, -1)).  The route retrieves k + the longest list and one filter launch trims it."""
 		if self.approx_preference != "rows":
 			raise NotImplementedError("This is not designed to give good approx of rows as C and U matrix are multiplied together. Build index w/ approx_preference = rows instead.")
 		X = self._to_dev(sparse_rows)
 		Q = X.shape[0]
-		if self._split is not None and self._split.takes(Q, self.m, k):
-			return self._split.topk(X, self._Et, k)
-		if self._Etp is not None and ops.fused_supported(Q, self.m, self._Etp.shape[1], k):
-			return ops.score_topk_fused(ops.pack_bf16(X, self._Etp.shape[1]), self._Etp_sorted, self.m, k, leading_sample=True, item_ids=self._item_ids)
+		excl, kc = _exclusion_arg(exclude, Q, self.m, k, self.device)
+		if self._split is not None and self._split.takes(Q, self.m, k, excl):
+			return self._split.topk(X, self._Et, k, excl)
+		if self._Etp is not None and ops.fused_supported(Q, self.m, self._Etp.shape[1], kc):
+			return _filtered(ops.score_topk_fused(ops.pack_bf16(X, self._Etp.shape[1]), self._Etp_sorted, self.m, kc, leading_sample=True, item_ids=self._item_ids), excl, k)
 		Et = self._Et if self.compute_dtype != "bf16" else (self._Etp[:self.m, :X.shape[1]] if self._Etp is not None else self._Et)
 		if self.compute_dtype == "bf16" and X.dtype != torch.bfloat16:
 			X = ops.convert(X, torch.bfloat16)
-		return ops.score_topk_dense(X, Et, k)
+		return _filtered(ops.score_topk_dense(X, Et, kc), excl, k)
 
-	def topk_in_row(self, sparse_rows, k):
-		v, i = self.topk_in_row_device(sparse_rows, k)
+	def topk_in_row(self, sparse_rows, k, exclude=None):
+		v, i = self.topk_in_row_device(sparse_rows, k, exclude=exclude)
 		return TopK(self._back(v, sparse_rows), self._back(i.long(), sparse_rows))
 
 	def eval_rows(self, sparse_rows, exact_rows, k):
@@ -274,6 +277,21 @@ class CURApprox(object):
 		if self.compute_dtype == "bf16" and self._Etp is not None and ops.approx_error_packed_ok(self._Etp.shape[1], A):
 			return ops.approx_error_packed(ops.pack_bf16(X, self._Etp.shape[1]), self._Etp, A, self.m)
 		return ops.approx_error(X, self._Et, A)
+
+
+def _exclusion_arg(exclude, Q, m, k, device):
+	"""(Exclusion or None, candidates per query the route retrieves) for a top-k's `exclude=` argument.  Nothing to exclude -- None, empty
+	lists -- gives (None, k): the call then runs exactly as it does without the argument."""
+	if exclude is None:
+		return None, k
+	excl = ops.exclusion(exclude, Q, m, device)
+	if excl.e_max == 0:
+		return None, k
+	return excl, ops.filtered_k(k, excl.e_max, m)
+
+
+def _filtered(res, excl, k):
+	return res if excl is None else ops.filter_topk(res.values, res.indices, excl, k)
 
 
 def _norm_sorted_pack(Et, kp):
@@ -303,11 +321,12 @@ class _SplitOperands(object):
 		order = ops.descending_norm_order(Et if Et.dtype == torch.float32 else ops.convert(Et, torch.float32))
 		return cls(kp, ops.pack_split_bf16(ops.gather_rows(Et, order), 1, kp, row_multiple=32), order)
 
-	def takes(self, Q, m, k):
-		return self.kp is not None and k <= min(m, ops._lib.MAX_TOPK) and ops.fused_supported(Q, m, self.kp, ops.split_candidates(m, k))
+	def takes(self, Q, m, k, excl=None):
+		e = excl.e_max if excl is not None else 0
+		return self.kp is not None and k + e <= min(m, ops._lib.MAX_TOPK) and ops.fused_supported(Q, m, self.kp, ops.split_candidates(m, k, n_excl=e))
 
-	def topk(self, X, Et, k):
-		return ops.score_topk_split(X, Et, self.sorted, Et.shape[0], k, item_ids=self.item_ids, leading_sample=True)
+	def topk(self, X, Et, k, excl=None):
+		return ops.score_topk_split(X, Et, self.sorted, Et.shape[0], k, item_ids=self.item_ids, leading_sample=True, exclude=excl)
 
 	def approx_error(self, X, Et, A):
 		"""a11 on the split operands (the sweep's bf16 MFMA loop, Kp <= 512): S_hat within (2^-16 + 3K 2^-23) |X|.|E|^T of the fp32 one."""
@@ -341,17 +360,20 @@ class CURRowIndex(object):
 			self._Etp_sorted, self._item_ids = _norm_sorted_pack(self._Et, kp)
 		self._split = _SplitOperands.build(self._Et) if compute_dtype == "bf16x3" else None
 
-	def topk(self, X, k):
-		"""X [q x kc]: the queries' exact scores against the anchor items -> (values f32, indices int32) on the GPU."""
+	def topk(self, X, k, exclude=None):
+		"""X [q x kc]: the queries' exact scores against the anchor items -> (values f32, indices int32) on the GPU.
+		exclude: items left out of the result, as for CURApprox.topk_in_row_device (e.g. ops.exclusion(self.col_idxs, ...), built once:
+		the anchor items, whose exact scores the caller holds already)."""
 		Q = X.shape[0]
-		if self._split is not None and self._split.takes(Q, self.m, k):
-			return self._split.topk(X, self._Et, k)
-		if self._Etp is not None and ops.fused_supported(Q, self.m, self._Etp.shape[1], k):
-			return ops.score_topk_fused(ops.pack_bf16(X, self._Etp.shape[1]), self._Etp_sorted, self.m, k, leading_sample=True, item_ids=self._item_ids)
+		excl, kc = _exclusion_arg(exclude, Q, self.m, k, X.device)
+		if self._split is not None and self._split.takes(Q, self.m, k, excl):
+			return self._split.topk(X, self._Et, k, excl)
+		if self._Etp is not None and ops.fused_supported(Q, self.m, self._Etp.shape[1], kc):
+			return _filtered(ops.score_topk_fused(ops.pack_bf16(X, self._Etp.shape[1]), self._Etp_sorted, self.m, kc, leading_sample=True, item_ids=self._item_ids), excl, k)
 		Et = self._Et if self.compute_dtype != "bf16" or self._Etp is None else self._Etp[:self.m, :X.shape[1]]
 		if self.compute_dtype == "bf16" and X.dtype != torch.bfloat16:
 			X = ops.convert(X, torch.bfloat16)
-		return ops.score_topk_dense(X, Et, k)
+		return _filtered(ops.score_topk_dense(X, Et, kc), excl, k)
 
 	def eval_topk(self, X, exact_rows, k, k_retvr):
 		"""(exact top-k of exact_rows, approximate top-k_retvr of X) -- the two rankings of the reference's per-query loop

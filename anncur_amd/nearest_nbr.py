@@ -60,24 +60,29 @@ class FlatIPIndex:
 	def train(self, embeds):  # FAISS API compatibility (flat index needs no training)
 		return None
 
-	def search(self, x, k):
+	def search(self, x, k, exclude=None):
+		"""exclude: vector ids left out of the result, FAISS' id selector turned round (ops.exclusion: one list for all queries, one per
+		query, or a -1 padded [nq x w] array).  k_eff + the longest list may not exceed min(ntotal, MAX_TOPK): ValueError."""
 		assert self._X is not None, "index is empty"
 		q = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(self.device)
 		k_eff = min(k, self.ntotal)
 		kp = ops.padded_k(self.d)
+		from .cur import _exclusion_arg, _filtered
+		excl, kc = _exclusion_arg(exclude, q.shape[0], self.ntotal, k_eff, self.device)
 		if self.dtype == "bf16x3":
 			if self._split is None:
 				from .cur import _SplitOperands
 				self._split = _SplitOperands.build(self._X)
-			if self._split.takes(q.shape[0], self.ntotal, k_eff):
-				return _faiss_pad(*self._split.topk(q, self._X, k_eff), q.shape[0], k, k_eff)
-		if self.dtype == "bf16" and kp is not None and ops.fused_supported(q.shape[0], self.ntotal, kp, k_eff):
+			if self._split.takes(q.shape[0], self.ntotal, k_eff, excl):
+				return _faiss_pad(*self._split.topk(q, self._X, k_eff, excl), q.shape[0], k, k_eff)
+		if self.dtype == "bf16" and kp is not None and ops.fused_supported(q.shape[0], self.ntotal, kp, kc):
 			if self._Xp is None:
 				from .cur import _norm_sorted_pack
 				self._Xp, self._ids = _norm_sorted_pack(self._X, kp)   # largest-norm vectors first: the likeliest maximum inner products
-			v, i = ops.score_topk_fused(ops.pack_bf16(q, kp), self._Xp, self.ntotal, k_eff, leading_sample=True, item_ids=self._ids)
+			v, i = ops.score_topk_fused(ops.pack_bf16(q, kp), self._Xp, self.ntotal, kc, leading_sample=True, item_ids=self._ids)
 		else:
-			v, i = ops.score_topk_dense(q, self._X, k_eff)
+			v, i = ops.score_topk_dense(q, self._X, kc)
+		v, i = _filtered(ops.TopK(v, i), excl, k_eff)
 		return _faiss_pad(v, i, q.shape[0], k, k_eff)
 
 
@@ -172,9 +177,18 @@ class IVFFlatIPIndex:
 		self._Xs[:, :self.d] = ops.gather_rows(self._X, self._ids)
 		self._Xs16 = ops.convert(self._Xs, torch.bfloat16) if self.dtype == "bf16" else None
 
-	def search_device(self, q, k, profile=None):
+	def search_device(self, q, k, profile=None, exclude=None):
 		"""search() on DEVICE-RESIDENT queries q [nq x d] fp32 -> (values f32 [nq x k_eff], ids int32 [nq x k_eff]) on the device, no host copy
-		(k_eff = min(k, MAX_TOPK); slots without a result hold (-inf, -1)).  What bench.py times as the kernels' own rate."""
+		(k_eff = min(k, MAX_TOPK); slots without a result hold (-inf, -1)).  What bench.py times as the kernels' own rate.
+		exclude: vector ids left out of the result (ops.exclusion).  The probed lists are searched for k_eff + the longest list -- on the
+		one-call path up to IVF_GROUPED_MAX_K, on the older paths above --, one filter launch trims the rows; a row whose probed lists
+		hold fewer than k_eff allowed vectors ends in (-inf, -1)."""
+		k_eff = min(k, ops._lib.MAX_TOPK)
+		from .cur import _exclusion_arg, _filtered
+		excl, kc = _exclusion_arg(exclude, q.shape[0], self.ntotal, k_eff, self.device)
+		return _filtered(self._search_device(q, kc, profile), excl, k_eff)
+
+	def _search_device(self, q, k, profile):
 		assert self._Xs is not None, "index is empty"
 		nprobe = max(1, min(int(self.nprobe), self.nlist))
 		probe = ops.score_topk_dense(q, self.centroids, nprobe).indices        # the nprobe lists of largest <q, centroid>
@@ -195,10 +209,10 @@ class IVFFlatIPIndex:
 			return ops.ivf_scan_grouped(self._Xs, self._offsets, self._ids, self._sizes, qp, probe, k_eff, lists_bf16=self._Xs16, profile=profile)
 		return ops.ivf_scan(self._Xs, self._offsets, self._ids, qp, probe, k_eff)
 
-	def search(self, x, k):
+	def search(self, x, k, exclude=None):
 		assert self._Xs is not None, "index is empty"
 		q = self._dev32(x)
-		v, i = self.search_device(q, k)
+		v, i = self.search_device(q, k, exclude=exclude)
 		return _faiss_pad(v, i, q.shape[0], k, min(k, ops._lib.MAX_TOPK))
 
 

@@ -492,28 +492,146 @@ def split_rescore_extra(k):
 	return max(SPLIT_RESCORE_EXTRA, k // 8)
 
 
-def split_candidates(I, k, extra=None):
-	"""Candidates per query the bf16x3 sweep retrieves for a final top-k of k: min(I, MAX_TOPK, k + extra)."""
-	return min(I, _lib.MAX_TOPK, k + (split_rescore_extra(k) if extra is None else extra))
+def split_candidates(I, k, extra=None, n_excl=0):
+	"""Candidates per query the bf16x3 sweep retrieves for a final top-k of k: min(I, MAX_TOPK, k + extra); with an exclusion of at most
+	n_excl items per query, min(I, MAX_TOPK, k + n_excl + extra) -- the margin `extra` still belongs to k."""
+	return min(I, _lib.MAX_TOPK, k + n_excl + (split_rescore_extra(k) if extra is None else extra))
 
 
 @_on_device
-def score_topk_split(X, Et_f32, Etp_split, I, k, item_ids=None, leading_sample=False, extra=None):
+def score_topk_split(X, Et_f32, Etp_split, I, k, item_ids=None, leading_sample=False, extra=None, exclude=None):
 	"""The bf16x3 route: top-k of S_hat = X.E at fp32 parity without writing S_hat.  X [Q x K] (f32/bf16), Et_f32 [I x K] the item
 	embeddings in ITEM order, Etp_split = pack_split_bf16(rows of Et_f32, role 1, row_multiple=32), its rows in item order or -- with
 	item_ids / leading_sample as for score_topk_fused -- in the index builder's order.  The fused sweep retrieves
 	kc = min(I, MAX_TOPK, k + extra) candidates on the split operands (scores within (2^-16 + 3K 2^-23) |X|.|E|^T of exact), rescore_topk
-	ranks them by the true fp32 score: values bit-equal to the dense fp32 route's.  Raises where the shape is outside the fused path."""
+	ranks them by the true fp32 score: values bit-equal to the dense fp32 route's.  Raises where the shape is outside the fused path.
+	exclude: an Exclusion (exclusion()): the sweep retrieves e_max more candidates, filter_topk keeps the first k + extra allowed ones --
+	the top k + extra by split score among the allowed items -- and the rescore ranks those."""
 	_dev(X, Et_f32, Etp_split)
 	Q, K = X.shape
 	Kp = Etp_split.shape[1]
-	kc = split_candidates(I, k, extra)
-	if Kp < 3 * K or Et_f32.shape[0] != I or Et_f32.shape[1] != K or k > kc:
-		raise ValueError("score_topk_split: X [Q x K], Et_f32 [I x K], Etp_split [ceil32(I) x Kp >= 3 K], k <= min(I, MAX_TOPK)")
+	e = exclude.e_max if exclude is not None else 0
+	kc = split_candidates(I, k, extra, e)
+	if Kp < 3 * K or Et_f32.shape[0] != I or Et_f32.shape[1] != K or k + e > kc:
+		raise ValueError("score_topk_split: X [Q x K], Et_f32 [I x K], Etp_split [ceil32(I) x Kp >= 3 K], k (+ excluded per query) <= min(I, MAX_TOPK)")
 	if not fused_supported(Q, I, Kp, kc):
 		raise _lib.AnncurHipError(f"score_topk_split: shape (Q={Q}, I={I}, Kp={Kp}, k={kc}) is outside the fused path")
 	cand = score_topk_fused(pack_split_bf16(X, 0, Kp), Etp_split, I, kc, leading_sample=leading_sample, item_ids=item_ids)
+	if e:
+		cand = filter_topk(cand.values, cand.indices, exclude, min(kc, split_candidates(I, k, extra)))
 	return rescore_topk(X, Et_f32, cand.indices, k)
+
+
+# ------------------------------------------------------------------ filtered retrieval (DESIGN 4.4b)
+Exclusion = namedtuple("Exclusion", ["off", "ids", "e_max"])
+
+
+def _sorted_unique_ids(a, I, what, pad=False):
+	"""One exclusion list -> sorted, distinct int64 numpy ids; pad: -1 entries are padding and dropped."""
+	a = np.asarray(a)
+	if a.ndim != 1:
+		raise ValueError(f"exclude: {what} must be a flat list of item ids")
+	if a.size and not np.issubdtype(a.dtype, np.integer):
+		if not np.issubdtype(a.dtype, np.floating) or not np.array_equal(a, np.floor(a)):
+			raise ValueError(f"exclude: {what} must hold integer item ids")
+	a = a.astype(np.int64)
+	if pad:
+		a = a[a != -1]
+	if a.size:
+		lo, hi = int(a.min()), int(a.max())
+		if lo < 0:
+			raise ValueError(f"exclude: {what} holds the negative id {lo}" + (" (only -1 pads a 2-D array)" if pad else ""))
+		if I is not None and hi >= I:
+			raise ValueError(f"exclude: {what} holds the id {hi}, but there are only {I} items")
+		if hi > 0x7fffffff:
+			raise ValueError(f"exclude: {what} holds the id {hi}, beyond int32")
+	return np.unique(a)
+
+
+def _host_array(x):
+	return x.detach().cpu().numpy() if torch.is_tensor(x) else x
+
+
+def exclusion(exclude, Q, I, device):
+	"""The `exclude=` argument of the top-k calls -> Exclusion(off, ids, e_max) for anncur_filter_topk: ids int32 on `device`, each
+	list sorted and de-duplicated; off int64 [Q + 1] on `device` (per-query lists, segment q = ids[off[q]:off[q + 1]]) or None (one
+	list shared by all queries); e_max = the longest list.  Accepted:
+	  * a flat sequence / 1-D array / 1-D tensor of ids: shared by all queries;
+	  * a sequence of Q sequences (lists, arrays, tensors), one per query;
+	  * a 2-D [Q x w] integer array or tensor, rows padded with -1.
+	ValueError: an id >= I (I None: not checked), a negative id other than the 2-D form's -1 padding, a wrong number of lists.
+	An Exclusion passes through (its Q is checked), so an index can normalise a fixed set -- its anchor items -- once and reuse it:
+	lists given as GPU tensors are copied to the host here, a synchronisation."""
+	device = torch.device(device)
+	if isinstance(exclude, Exclusion):
+		if exclude.off is not None and exclude.off.numel() != Q + 1:
+			raise ValueError(f"exclude: the exclusion was built for {exclude.off.numel() - 1} queries, the call has {Q}")
+		return exclude
+	if exclude is None:
+		return Exclusion(None, None, 0)
+	x = _host_array(exclude)
+	per_query = None
+	if isinstance(x, np.ndarray):
+		if x.ndim == 1:
+			shared = _sorted_unique_ids(x, I, "the shared list")
+		elif x.ndim == 2:
+			if x.shape[0] != Q:
+				raise ValueError(f"exclude: the 2-D array has {x.shape[0]} rows, the call has {Q} queries")
+			per_query = [_sorted_unique_ids(r, I, f"row {q}", pad=True) for q, r in enumerate(x)]
+		else:
+			raise ValueError("exclude: an array must be 1-D (shared) or 2-D [Q x w] (-1 padded)")
+	else:
+		x = list(x)
+		if any(torch.is_tensor(r) or isinstance(r, (list, tuple, np.ndarray, range)) for r in x):
+			if len(x) != Q:
+				raise ValueError(f"exclude: {len(x)} per-query lists, the call has {Q} queries")
+			per_query = [_sorted_unique_ids(_host_array(r), I, f"list {q}") for q, r in enumerate(x)]
+		else:
+			shared = _sorted_unique_ids(np.asarray(x) if x else np.zeros(0, dtype=np.int64), I, "the shared list")
+	if per_query is None:
+		return Exclusion(None, torch.from_numpy(shared.astype(np.int32)).to(device), int(shared.size))
+	lens = np.array([r.size for r in per_query], dtype=np.int64)
+	off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+	ids = np.concatenate(per_query).astype(np.int32) if per_query else np.zeros(0, dtype=np.int32)
+	return Exclusion(torch.from_numpy(off).to(device), torch.from_numpy(ids).to(device), int(lens.max(initial=0)))
+
+
+def filtered_k(k, e_max, I):
+	"""Candidates per query a top-k asks for when up to e_max items per query are excluded: kc = k + e_max, because the unfiltered
+	top-(k + e) contains the filtered top-k.  ValueError beyond what one top-k call returns."""
+	kc = k + e_max
+	limit = min(I, _lib.MAX_TOPK)
+	if kc > limit:
+		raise ValueError(f"exclude: k + the longest exclusion list = {k} + {e_max} = {kc} candidates per query, above the limit of min(items, ANNCUR_MAX_TOPK) = "
+						 f"min({I}, {_lib.MAX_TOPK}) = {limit} of one top-k call; to exclude a set this large, rebuild the index without those items")
+	return kc
+
+
+@_on_device
+def filter_topk(val, idx, exclude, k_out):
+	"""The first k_out entries of each row of (val f32 [Q x n_cand], idx int32 [Q x n_cand]) -- a top-k result: descending, id < 0 a
+	hole -- that are neither holes nor excluded, in the row's order, padded with (-inf, -1).  exclude: anything exclusion() takes
+	(ids are not checked against an item count here)."""
+	_dev(val, idx)
+	if val.dim() != 2 or tuple(val.shape) != tuple(idx.shape):
+		raise ValueError("filter_topk: val and idx must be 2-D tensors of one shape")
+	if val.dtype != torch.float32:
+		raise TypeError("filter_topk takes float32 scores")
+	if idx.dtype != torch.int32:
+		idx = idx.to(torch.int32)
+	val, idx = _rowmajor(val), _rowmajor(idx)
+	if _ld(val) != _ld(idx):
+		val, idx = val.contiguous(), idx.contiguous()
+	Q, n_cand = val.shape
+	ex = exclusion(exclude, Q, None, val.device)
+	out_val = torch.empty((Q, k_out), dtype=torch.float32, device=val.device)
+	out_idx = torch.empty((Q, k_out), dtype=torch.int32, device=val.device)
+	n_ids = ex.ids.numel() if ex.ids is not None else 0
+	if Q == 0:
+		return TopK(out_val, out_idx)
+	check(_lib.load().anncur_filter_topk(_p(val), _p(idx), _ld(val), n_cand, Q, _p(ex.off) if ex.off is not None else None,
+										 _p(ex.ids) if n_ids else None, n_ids if ex.off is None else 0, k_out, _p(out_val), _p(out_idx), _stream()), "filter_topk")
+	return TopK(out_val, out_idx)
 
 
 FUSED_WS_LIMIT_BYTES = 32 << 30   # default workspace above this size -> score_topk_fused runs the queries in row chunks

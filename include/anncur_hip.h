@@ -254,6 +254,25 @@ int anncur_rescore_topk(const void *X, int x_dtype, int64_t ldx, const void *Et,
                         const int32_t *cand_idx, int64_t ld_idx, int32_t n_cand, int64_t Q, int64_t I, int32_t k_out,
                         float *out_val, int32_t *out_idx, float *scratch, void *stream);
 
+/* filtered retrieval: the best k items OUTSIDE a given set, behind every top-k above ---------------------------------------------
+ *   the anchor items every query has scored already               ..._w_fixed_train_test_splits.py:297-301
+ *   the gold entity removed by hand after the search              utils/data_process.py:343-351,393-397
+ * (FAISS, whose calling convention models/nearest_nbr.py follows, has an id selector for this.)  If query q excludes e_q distinct
+ * items, the unfiltered top-(k + e_q) contains the filtered top-k: the caller asks its top-k for k + max_q e_q candidates and this call
+ * compacts each row.  No other entry point, plan or workspace knows about it.
+ *
+ * anncur_filter_topk: row q of in_val / in_idx (both with row pitch ld_in) holds n_cand (score, id) entries in the producer's order
+ *   -- descending --; an id < 0 is a hole.  excl_off != NULL: query q excludes excl_ids[excl_off[q] .. excl_off[q+1]) (excl_off
+ *   int64[Q + 1], ascending); excl_off == NULL: every query excludes excl_ids[0 .. n_excl_shared) (n_excl_shared is ignored otherwise).
+ *   The ids of a segment are STRICTLY ASCENDING (the kernel binary-searches them and trusts this; the Python layer sorts and
+ *   de-duplicates); empty segments are fine, and excl_ids may be NULL when there is nothing to exclude.
+ *   out_val float[Q x k_out], out_idx int32[Q x k_out], contiguous: the first k_out entries of row q that are neither holes nor
+ *   excluded, IN INPUT ORDER (a stable compaction), then (-inf, -1).  The outputs must not alias the inputs.
+ *   1 <= k_out <= n_cand <= ANNCUR_MAX_TOPK, Q >= 1.  One wave per query; latency-bound, the rows and segments come from L2. */
+int anncur_filter_topk(const float *in_val, const int32_t *in_idx, int64_t ld_in, int64_t n_cand, int64_t Q,
+                       const int64_t *excl_off, const int32_t *excl_ids, int64_t n_excl_shared, int32_t k_out,
+                       float *out_val, int32_t *out_idx, void *stream);
+
 /* a8 per-query evaluation loop: exact top-k of the stored scores AND the approximate retrieval, in one call ----------------------
  *   curr_ment_scores.topk(top_k) ; approx_curr_ment_scores.topk(top_k_retvr)          ...crossenc.py:97-106 ; ..._splits.py:80-89
  * = anncur_rowwise_topk(A, k_exact) + anncur_score_topk_ex(X, Et, k_retvr), same results, scheduled together: the retrieval is a chain
