@@ -72,6 +72,8 @@ SIGNATURES = {
 	"anncur_score_topk_survivors": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, ctypes.POINTER(ctypes.c_double), c_void_p]),
 	"anncur_score_topk_ladder_state": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 	"anncur_rerank": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+	"anncur_rerank_scored": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+	"anncur_gather_pairs": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p]),
 	"anncur_overlap_counts": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, _p32, _p32, c_int32, c_void_p, c_void_p]),
 	"anncur_copy_bytes": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
 	"anncur_ivf_build_lists": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

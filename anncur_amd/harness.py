@@ -18,6 +18,7 @@ import torch
 from . import ops
 from .cur import CURApprox, CURRowIndex
 from .eval_utils import flatten_overlap, overlap_stats_from_counts
+from .retrieval import POOL_PREFIX, overlap_pool_cells, pool_cell_limit, split_pool_cells
 
 LOGGER = logging.getLogger(__name__)
 
@@ -42,14 +43,34 @@ def _select(rng, n, size):
 	return sorted(rng.choice(n, size=size, replace=False))
 
 
-def _subset_metrics(counts_row, rows, k):
-	return flatten_overlap(overlap_stats_from_counts(np.asarray(counts_row)[np.asarray(rows, dtype=np.int64)], k))
+def _subset_metrics(counts_row, rows, k, prefix=None):
+	stats = overlap_stats_from_counts(np.asarray(counts_row)[np.asarray(rows, dtype=np.int64)], k)
+	return flatten_overlap(stats) if prefix is None else flatten_overlap(stats, prefix=prefix)
+
+
+RERANK_POOLS = ("retrieved", "retrieved+anchors")   # --rerank_pool of both entry points
+
+
+def _check_rerank_pool(rerank_pool):
+	if rerank_pool not in RERANK_POOLS:
+		raise ValueError(f"rerank_pool = {rerank_pool} not supported (one of {', '.join(RERANK_POOLS)})")
+	return rerank_pool == "retrieved+anchors"
+
+
+def _log_skipped_pool_cells(skipped, n_anc, n_ent):
+	LOGGER.info("rerank_pool=retrieved+anchors: %d cell(s) with %d anchor items left out of %s (k_retvr %s): k_retvr + n_anc exceeds min(n_ent, ANNCUR_MAX_TOPK, %d) = %d, "
+				"what one retrieval with the anchors excluded and one overlap list hold", len(skipped), n_anc, POOL_PREFIX,
+				",".join(str(kr) for kr in sorted({c[1] for c in skipped})), 4096, pool_cell_limit(n_ent))
 
 
 # ------------------------------------------------------------------------------------------------ entry point A
-def run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, seed, exact_cache=None, pinv_backend="auto", compute_dtype=None):
+def run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, seed, exact_cache=None, pinv_backend="auto", compute_dtype=None,
+						   rerank_pool="retrieved", literal_rerank=False):
 	"""One seed of one grid cell -> {"anchor": {...}, "non_anchor": {...}, "all": {...}} (crossenc.py:47-158).
-	compute_dtype: CURApprox's (None = by the matrix' dtype; "bf16x3" = the fp32-parity route on the bf16 matrix cores)."""
+	compute_dtype: CURApprox's (None = by the matrix' dtype; "bf16x3" = the fp32-parity route on the bf16 matrix cores).
+	rerank_pool "retrieved+anchors": every subset also reports the overlap metrics of the pool anchor items + top_k_retvr NEW items under
+	POOL_PREFIX (a second retrieval, with the anchor items excluded); a cell beyond pool_cell_limit is left out of that prefix."""
+	with_pool = _check_rerank_pool(rerank_pool)
 	n_ments, n_ents = A_dev.shape
 	rng = np.random.default_rng(seed=seed)
 	row_idxs = _select(rng, n_ments, n_ment_anchors)          # rows first, then columns, same generator
@@ -73,9 +94,20 @@ def run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, 
 			exact_cache.update(k=top_k, topk=exact)
 	counts = ops.overlap_counts(exact.indices, approx.indices, [(top_k, top_k_retvr)]).cpu().numpy()[0]
 	err_sq, norm_sq = err_sq.double().cpu().numpy(), norm_sq.double().cpu().numpy()
+	pool_counts = None
+	if with_pool:
+		cell = [(top_k, top_k_retvr)]
+		kept, skipped = split_pool_cells(cell, n_ent_anchors, n_ents)
+		if skipped:
+			_log_skipped_pool_cells(skipped, n_ent_anchors, n_ents)
+		else:
+			new_items = cur.topk_in_row_device(cols, top_k_retvr, exclude=np.asarray(col_idxs))
+			pool_counts = overlap_pool_cells(exact.indices, col_idxs, new_items.indices, kept, A_dev, literal_rerank).cpu().numpy()[0]
 
 	def score(idxs):
 		res = _subset_metrics(counts, idxs, top_k) if len(idxs) else flatten_overlap(overlap_stats_from_counts([], top_k))
+		if pool_counts is not None:
+			res.update(_subset_metrics(pool_counts, idxs, top_k, POOL_PREFIX) if len(idxs) else flatten_overlap(overlap_stats_from_counts([], top_k), prefix=POOL_PREFIX))
 		ii = np.asarray(idxs, dtype=np.int64)
 		err = np.float32(np.sqrt(err_sq[ii].sum()))
 		with np.errstate(invalid="ignore", divide="ignore"):
@@ -86,11 +118,13 @@ def run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, 
 	return {"anchor": score(row_idxs), "non_anchor": score(non_anchor), "all": score(list(range(n_ments)))}
 
 
-def run_approx_eval(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, n_seeds, exact_cache=None, pinv_backend="auto", compute_dtype=None):
+def run_approx_eval(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, n_seeds, exact_cache=None, pinv_backend="auto", compute_dtype=None,
+					rerank_pool="retrieved", literal_rerank=False):
 	"""Mean over seeds (crossenc.py:162-200)."""
 	acc = defaultdict(lambda: defaultdict(list))
 	for seed in range(n_seeds):
-		res = run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, seed, exact_cache, pinv_backend, compute_dtype)
+		res = run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, seed, exact_cache, pinv_backend, compute_dtype,
+									 rerank_pool=rerank_pool, literal_rerank=literal_rerank)
 		for ment_type, d in res.items():
 			for metric, val in d.items():
 				acc[ment_type][metric].append(float(val))
@@ -172,7 +206,7 @@ def default_grids_A(total_n_ment, total_n_ent):
 	}
 
 
-def run_entry_A(A_dev, grids, n_seeds, progress=None, pinv_backend="auto", compute_dtype=None):
+def run_entry_A(A_dev, grids, n_seeds, progress=None, pinv_backend="auto", compute_dtype=None, rerank_pool="retrieved", literal_rerank=False):
 	"""-> res[method]["top_k=.."]["k_retvr=.."]["anc_n_m=..~anc_n_e=.."][anchor|non_anchor|all][metric]  (crossenc.py:349-383)."""
 	total_n_ment, total_n_ent = A_dev.shape
 	res = defaultdict(lambda: defaultdict(lambda: defaultdict(dict)))
@@ -187,7 +221,7 @@ def run_entry_A(A_dev, grids, n_seeds, progress=None, pinv_backend="auto", compu
 			if progress:
 				progress(method, ctr, len(cells))
 			res[method][f"top_k={top_k}"][f"k_retvr={kr}"][f"anc_n_m={nm}~anc_n_e={ne}"] = \
-				run_approx_eval(method, A_dev, nm, ne, top_k, kr, n_seeds, exact_cache, pinv_backend, compute_dtype)
+				run_approx_eval(method, A_dev, nm, ne, top_k, kr, n_seeds, exact_cache, pinv_backend, compute_dtype, rerank_pool=rerank_pool, literal_rerank=literal_rerank)
 	return {m: {a: {b: dict(c) for b, c in d.items()} for a, d in v.items()} for m, v in res.items()}
 
 
@@ -211,8 +245,27 @@ def _sweep_cells(A_test_dev, approx_idx, exact, top_k_vals, top_k_retr_vals, n_e
 	return {cell: flatten_overlap(overlap_stats_from_counts(counts[j], cell[0])) for j, cell in enumerate(cells)}
 
 
-def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None, progress=None, key_n_m=None, pinv_backend="auto"):
-	"""eval_method == "cur" of entry point B for one seed (splits.py:286-303 + 399-429)."""
+def _sweep_pool_cells(A_test_dev, anc, retrieved_idx, exact, top_k_vals, top_k_retr_vals, n_ent, literal_rerank=False):
+	"""The pool-mode metrics (POOL_PREFIX) of all (top_k, k_retvr) cells of one anchor set from ONE retrieval with the anchors excluded, at the
+	largest k_retvr the pool takes: the pool of a cell is the anchor items + the first k_retvr retrieved.  Cells beyond pool_cell_limit
+	are left out, with one log line."""
+	cells = [(k, kr) for kr in top_k_retr_vals if 0 < kr <= min(n_ent, ops._lib.MAX_TOPK) for k in top_k_vals if k <= kr and k <= exact.indices.shape[1]]
+	kept, skipped = split_pool_cells(cells, len(anc), n_ent)
+	if skipped:
+		_log_skipped_pool_cells(skipped, len(anc), n_ent)
+	kept = [c for c in kept if c[1] <= retrieved_idx.shape[1]]
+	if not kept:
+		return {}
+	counts = overlap_pool_cells(exact.indices, anc, retrieved_idx, kept, A_test_dev, literal_rerank).cpu().numpy()
+	return {cell: flatten_overlap(overlap_stats_from_counts(counts[j], cell[0]), prefix=POOL_PREFIX) for j, cell in enumerate(kept)}
+
+
+def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None, progress=None, key_n_m=None, pinv_backend="auto", rerank_pool="retrieved",
+						literal_rerank=False):
+	"""eval_method == "cur" of entry point B for one seed (splits.py:286-303 + 399-429).
+	rerank_pool "retrieved+anchors": every cell also reports, under POOL_PREFIX, the metrics of the pool anchor items + k_retvr NEW items (a
+	second retrieval per anchor count, with the anchor items excluded, at the largest k_retvr with k_retvr + n_anc <= pool_cell_limit)."""
+	with_pool = _check_rerank_pool(rerank_pool)
 	n_train, n_ent = A_train_dev.shape
 	top_k_vals, retr_vals, anc_vals = grids["top_k_vals"], grids["top_k_retr_vals"], grids["n_ent_anchors_vals"]
 	kr_max = max([kr for kr in retr_vals if kr <= min(n_ent, ops._lib.MAX_TOPK)] or [0])
@@ -233,12 +286,22 @@ def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None
 			approx_idx = torch.arange(kr_max, dtype=torch.int32, device=A_test_dev.device).expand(A_test_dev.shape[0], kr_max).contiguous()
 			for (k, kr), metrics in _sweep_cells(A_test_dev, approx_idx, exact, top_k_vals, retr_vals, n_ent).items():
 				res[f"top_k={k}"][f"k_retvr={kr}"][f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}"] = metrics
+			if with_pool:   # no anchors: the pool is the retrieved list
+				for (k, kr), metrics in _sweep_pool_cells(A_test_dev, anc, approx_idx, exact, top_k_vals, retr_vals, n_ent, literal_rerank).items():
+					res[f"top_k={k}"][f"k_retvr={kr}"][f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}"].update(metrics)
 			continue
 		cur = CURApprox(rows=A_train_dev, cols=ops.gather_cols(A_train_dev, anc), row_idxs=np.arange(n_train), col_idxs=anc,
 						approx_preference="rows", compute_dtype=compute_dtype, pinv_backend=pinv_backend)
-		approx = cur.topk_in_row_device(ops.gather_cols(A_test_dev, anc), kr_max)
+		X = ops.gather_cols(A_test_dev, anc)
+		approx = cur.topk_in_row_device(X, kr_max)
 		for (k, kr), metrics in _sweep_cells(A_test_dev, approx.indices, exact, top_k_vals, retr_vals, n_ent).items():
 			res[f"top_k={k}"][f"k_retvr={kr}"][f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}"] = metrics
+		if with_pool:
+			kr_pool = max([kr for kr in retr_vals if 0 < kr and kr + n_anc <= pool_cell_limit(n_ent)] or [0])
+			new_items = cur.topk_in_row_device(X, kr_pool, exclude=np.asarray(anc)).indices if kr_pool else approx.indices[:, :0]
+			for (k, kr), metrics in _sweep_pool_cells(A_test_dev, anc, new_items, exact, top_k_vals, retr_vals, n_ent, literal_rerank).items():
+				res[f"top_k={k}"][f"k_retvr={kr}"][f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}"].update(metrics)
+			del new_items
 		del cur, approx
 	return {a: {b: dict(c) for b, c in d.items()} for a, d in res.items()}
 
@@ -261,7 +324,7 @@ def run_eval_method_embeds(A_test_dev, mention_embeds, label_embeds, n_train, gr
 	return {a: {b: dict(c) for b, c in d.items()} for a, d in res.items()}
 
 
-def run_eval_method_fixed_anc_ent_cur(A_test_dev, e2e_scores_dev, n_fixed_anc_ent, grids, key_n_m=None):
+def run_eval_method_fixed_anc_ent_cur(A_test_dev, e2e_scores_dev, n_fixed_anc_ent, grids, key_n_m=None, rerank_pool="retrieved"):
 	"""fixed_anc_ent_cur (splits.py:327-358): R = ent_to_ent_scores[:, :n_fixed].T, anchors from rng(0), U = pinv(R[:, anc])."""
 	R = e2e_scores_dev[:, :n_fixed_anc_ent].t().contiguous()     # n_fixed x n_ents
-	return run_eval_method_cur(A_test_dev, R, seed=0, grids=grids, key_n_m=key_n_m)
+	return run_eval_method_cur(A_test_dev, R, seed=0, grids=grids, key_n_m=key_n_m, rerank_pool=rerank_pool)

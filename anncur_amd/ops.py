@@ -955,6 +955,122 @@ def rerank(A, approx_idx, k_retvr, k_out):
 	return TopK(val, idx)
 
 
+# ------------------------------------------------------------------ re-rank from caller-supplied scores
+SharedIds = namedtuple("SharedIds", ["ids", "n"])
+MAX_SHARED_IDS = 65535   # n_sh limit of anncur_rerank_scored
+
+
+def shared_id_list(ids, device):
+	"""The `shared_ids=` argument of rerank_scored -> SharedIds(ids int32 on `device`, n), checked on the host: a flat list of
+	non-negative int32 ids, STRICTLY ASCENDING (nothing is sorted here: column j of shared_scores belongs to ids[j], and the kernel
+	binary-searches the list).  ValueError otherwise.  A SharedIds passes through, so a searcher checks its anchor ids once; a list
+	given as a GPU tensor is copied to the host here, a synchronisation (the rule of exclusion())."""
+	if isinstance(ids, SharedIds):
+		return ids
+	a = np.asarray(_host_array(ids))
+	if a.ndim != 1:
+		raise ValueError("rerank_scored: shared_ids must be a flat list of item ids")
+	if a.size and not np.issubdtype(a.dtype, np.integer):
+		raise ValueError("rerank_scored: shared_ids must hold integer item ids")
+	a = a.astype(np.int64)
+	if a.size > MAX_SHARED_IDS:
+		raise ValueError(f"rerank_scored: {a.size} shared ids, above the limit of {MAX_SHARED_IDS}")
+	if a.size:
+		if int(a[0]) < 0:
+			raise ValueError(f"rerank_scored: shared_ids holds the negative id {int(a[0])}")
+		if int(a.max()) > 0x7fffffff:
+			raise ValueError(f"rerank_scored: shared_ids holds the id {int(a.max())}, beyond int32")
+		bad = np.flatnonzero(a[1:] <= a[:-1])
+		if bad.size:
+			j = int(bad[0])
+			raise ValueError(f"rerank_scored: shared_ids must be strictly ascending (ids[{j}] = {int(a[j])}, ids[{j + 1}] = {int(a[j + 1])}); "
+							 "sort the ids and the columns of shared_scores together")
+	return SharedIds(torch.from_numpy(a.astype(np.int32)).to(device), int(a.size))
+
+
+def _rerank_scored_args(k, cand, cand_scores, shared_ids, shared_scores):
+	"""Host-side validation of rerank_scored, before any tensor has to be on the GPU: -> (Q, n_sh, n_pq, cand indices or None)."""
+	if isinstance(cand, TopK):
+		cand = cand.indices
+	if (cand is None) != (cand_scores is None):
+		raise ValueError("rerank_scored: cand and cand_scores come together")
+	if (shared_ids is None) != (shared_scores is None):
+		raise ValueError("rerank_scored: shared_ids and shared_scores come together")
+	Q = None
+	n_pq = n_sh = 0
+	if cand is not None:
+		if not (torch.is_tensor(cand) and torch.is_tensor(cand_scores)) or cand.dim() != 2 or tuple(cand.shape) != tuple(cand_scores.shape):
+			raise ValueError("rerank_scored: cand and cand_scores must be 2-D tensors [Q x n_pq] of one shape")
+		if cand.dtype != torch.int32:
+			raise ValueError(f"rerank_scored: cand must hold int32 ids (got {cand.dtype})")
+		if cand_scores.dtype != torch.float32:
+			raise ValueError(f"rerank_scored: cand_scores must be float32 (got {cand_scores.dtype})")
+		Q, n_pq = cand.shape
+		if n_pq > _lib.MAX_TOPK:
+			raise ValueError(f"rerank_scored: {n_pq} candidates per query, above the limit of ANNCUR_MAX_TOPK = {_lib.MAX_TOPK}")
+	if shared_ids is not None:
+		n_sh = shared_ids.n if isinstance(shared_ids, SharedIds) else len(shared_ids)
+		if not torch.is_tensor(shared_scores) or shared_scores.dim() != 2 or shared_scores.shape[1] != n_sh:
+			raise ValueError(f"rerank_scored: shared_scores must be a 2-D tensor [Q x {n_sh}], one column per shared id")
+		if shared_scores.dtype not in _DT:
+			raise ValueError(f"rerank_scored: shared_scores must be float32 or bfloat16 (got {shared_scores.dtype})")
+		if n_sh > MAX_SHARED_IDS:
+			raise ValueError(f"rerank_scored: {n_sh} shared ids, above the limit of {MAX_SHARED_IDS}")
+		if Q is not None and shared_scores.shape[0] != Q:
+			raise ValueError(f"rerank_scored: shared_scores has {shared_scores.shape[0]} rows, cand has {Q}")
+		Q = shared_scores.shape[0]
+	if n_sh + n_pq < 1:
+		raise ValueError("rerank_scored: the pool is empty: give cand / cand_scores, shared_ids / shared_scores or both")
+	limit = min(n_sh + n_pq, _lib.MAX_TOPK)
+	if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or k > limit:
+		raise ValueError(f"rerank_scored: k = {k} outside 1..min(pool size, ANNCUR_MAX_TOPK) = min({n_sh + n_pq}, {_lib.MAX_TOPK}) = {limit}")
+	return Q, n_sh, n_pq, cand
+
+
+@_on_device
+def rerank_scored(k, cand=None, cand_scores=None, shared_ids=None, shared_scores=None):
+	"""The k best of a pool of items whose exact scores the CALLER holds (reference: ..._splits.py:91-96 without the resident matrix):
+	  cand [Q x n_pq] int32 ids (or a TopK: its .indices; id < 0 = hole) with cand_scores [Q x n_pq] float32, in candidate order;
+	  shared_ids [n_sh] strictly ascending, one list for all queries, with shared_scores [Q x n_sh] float32 / bfloat16 -- the anchor scores X.
+	Either source may be missing.  A candidate that is also a shared id is dropped (the shared score stands).  -> TopK, score descending,
+	ties by the smaller id, NaN never selected, (-inf, -1) padding.  Validated on the host (ValueError with the limit); nothing is sorted."""
+	Q, n_sh, n_pq, cand = _rerank_scored_args(k, cand, cand_scores, shared_ids, shared_scores)
+	dev = (shared_scores if cand is None else cand).device
+	sh = None
+	if shared_ids is not None:
+		sh = shared_id_list(shared_ids, dev)
+		_dev(shared_scores, sh.ids)
+		shared_scores = _rowmajor(shared_scores)
+	if cand is not None:
+		_dev(cand, cand_scores)
+		cand, cand_scores = _rowmajor(cand), _rowmajor(cand_scores)
+		if _ld(cand) != _ld(cand_scores):
+			cand, cand_scores = cand.contiguous(), cand_scores.contiguous()
+	val = torch.empty((Q, k), dtype=torch.float32, device=dev)
+	idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
+	check(_lib.load().anncur_rerank_scored(_p(sh.ids) if n_sh else None, _p(shared_scores) if n_sh else None, _dt(shared_scores) if n_sh else F32,
+										   _ld(shared_scores) if n_sh else 0, n_sh, _p(cand) if n_pq else None, _p(cand_scores) if n_pq else None,
+										   _ld(cand) if n_pq else 0, n_pq, Q, int(k), _p(val), _p(idx), _stream()), "rerank_scored")
+	return TopK(val, idx)
+
+
+@_on_device
+def gather_pairs(A, idx):
+	"""out[q, j] = A[q, idx[q, j]] as float32 [Q x n]; an id outside [0, I) (a hole) gives NaN (reference: ..._splits.py:91-96 reads
+	these cells of the exact matrix)."""
+	_dev(A, idx)
+	A = _rowmajor(A)
+	if idx.dim() != 2 or idx.shape[0] != A.shape[0]:
+		raise ValueError(f"gather_pairs: idx must be a 2-D tensor with one row per row of A ({A.shape[0]})")
+	if idx.dtype != torch.int32:
+		idx = idx.to(torch.int32)
+	idx = _rowmajor(idx)
+	Q, n = idx.shape
+	out = torch.empty((Q, n), dtype=torch.float32, device=A.device)
+	check(_lib.load().anncur_gather_pairs(_p(A), _dt(A), Q, A.shape[1], _ld(A), _p(idx), _ld(idx), n, _p(out), max(n, 1), _stream()), "gather_pairs")
+	return out
+
+
 @_on_device
 def overlap_counts(a, b, pairs, mapped_host_out=None):
 	"""common[p, q] = |set(a[q, :ka_p]) & set(b[q, :kb_p])| for pairs = [(ka, kb), ...] -> int32 [n_pairs, Q].

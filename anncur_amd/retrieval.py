@@ -33,6 +33,68 @@ def overlap_cells(exact_idx, approx_idx, cells, A_dev=None, literal_rerank=False
 	return out
 
 
+# ------------------------------------------------------------------ the pool "retrieved + anchors" 
+POOL_PREFIX = "exact_vs_reranked_approx_retvr_w_anchors"
+OVERLAP_MAX_LIST = 4096   # longest list anncur_overlap_counts takes
+
+
+def pool_cell_limit(n_ent):
+	"""Largest n_anc + k_retvr of a pool cell: the retrieval with the anchors excluded asks one top-k call for k_retvr + n_anc candidates
+	(ops.filtered_k: at most min(n_ent, ANNCUR_MAX_TOPK)), and the pool is one list of the overlap kernel (at most 4096 ids)."""
+	return min(n_ent, ops._lib.MAX_TOPK, OVERLAP_MAX_LIST)
+
+
+def split_pool_cells(cells, n_anc, n_ent):
+	"""cells = [(top_k, k_retvr), ...] -> (cells the pool mode reports, cells it leaves out): k_retvr counts NEW items, so a cell needs
+	k_retvr + n_anc <= pool_cell_limit(n_ent)."""
+	limit = pool_cell_limit(n_ent)
+	kept = [c for c in cells if c[1] + n_anc <= limit]
+	return kept, [c for c in cells if c[1] + n_anc > limit]
+
+
+def pool_pairs(cells, n_anc):
+	"""Prefix-length pairs of the closed form over the list of pool_list: (top_k, n_anc + k_retvr) per cell."""
+	return [(k, n_anc + kr) for k, kr in cells]
+
+
+def pool_list(anchor_ids, retrieved_idx):
+	"""[Q x (n_anc + k_retvr_max)] int32: the anchor ids FIRST (the same in every row), then the retrieved ids in retrieval order -- the
+	pool of a cell (top_k, k_retvr) is the prefix of length n_anc + k_retvr."""
+	Q = retrieved_idx.shape[0]
+	anc = torch.as_tensor(anchor_ids, dtype=torch.int32, device=retrieved_idx.device).reshape(1, -1)
+	return torch.cat([anc.expand(Q, anc.shape[1]), retrieved_idx.to(torch.int32)], dim=1).contiguous()
+
+
+def overlap_pool_cells(exact_idx, anchor_ids, retrieved_idx, cells, A_dev=None, literal_rerank=False):
+	"""common counts [n_cells, Q] of the pool mode for cells = [(top_k, k_retvr), ...]: the pool of a query is the anchor items plus its
+	first k_retvr retrieved items (retrieved_idx: a retrieval with the anchors EXCLUDED, so they are new items).
+
+	Closed form (default): |exact[:top_k] & rerank(pool)[:top_k]| == |exact[:top_k] & pool| (the argument of overlap_cells), one
+	ops.overlap_counts call on pool_list / pool_pairs.  literal_rerank=True scores the pool like a search does -- anchors as one shared
+	list, candidates per query, from MatrixScorer(A_dev) -- and runs ops.rerank_scored per k_retvr (tests check both agree)."""
+	anchor_ids = np.asarray(anchor_ids, dtype=np.int64).reshape(-1)
+	if not literal_rerank:
+		return ops.overlap_counts(exact_idx, pool_list(anchor_ids, retrieved_idx), pool_pairs(cells, anchor_ids.size))
+	from .search import MatrixScorer
+	scorer = MatrixScorer(A_dev)
+	qids = np.arange(A_dev.shape[0], dtype=np.int64)
+	retrieved_idx = retrieved_idx.to(torch.int32).contiguous()
+	shared = ops.shared_id_list(anchor_ids, A_dev.device) if anchor_ids.size else None
+	X = scorer(qids, shared.ids) if shared is not None else None
+	scores = scorer(qids, retrieved_idx)
+	if scores.dtype != torch.float32:
+		scores = ops.convert(scores, torch.float32)
+	out = torch.empty((len(cells), exact_idx.shape[0]), dtype=torch.int32, device=exact_idx.device)
+	for kr in sorted({c[1] for c in cells}):
+		sel = [j for j, c in enumerate(cells) if c[1] == kr]
+		kmax = max(cells[j][0] for j in sel)
+		rr = ops.rerank_scored(kmax, retrieved_idx[:, :kr], scores[:, :kr], shared, X)
+		cnt = ops.overlap_counts(exact_idx, rr.indices, [(cells[j][0], cells[j][0]) for j in sel])
+		for r, j in enumerate(sel):
+			out[j] = cnt[r]
+	return out
+
+
 def eval_topk_recall(A_dev, approx_idx, top_k_vals, k_retvr_vals, exact=None, row_subsets=None, literal_rerank=False):
 	"""-> {(top_k, k_retvr): {"exact_vs_reranked_approx_retvr~common_mean": ..., ...}} in the reference's
 	metric names and 4-decimal rounding.  approx_idx [Q, >= max k_retvr] sorted by approximate score.

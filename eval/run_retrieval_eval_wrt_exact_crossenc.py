@@ -55,7 +55,8 @@ def plot(res_dir, method_vals):
 	return made
 
 
-def run(base_res_dir, data_info, n_seeds, plot_only, misc, arg_dict, grid_overrides, dtype, device, pinv_backend="auto", score_chunks=None, compute_dtype=None):
+def run(base_res_dir, data_info, n_seeds, plot_only, misc, arg_dict, grid_overrides, dtype, device, pinv_backend="auto", score_chunks=None, compute_dtype=None,
+		rerank_pool="retrieved"):
 	from anncur_amd import harness
 	data_name, data_fname = data_info
 	world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -102,6 +103,8 @@ def run(base_res_dir, data_info, n_seeds, plot_only, misc, arg_dict, grid_overri
 			if "cur_oracle" in grids["eval_methods"]:
 				LOGGER.info("row-sharded run: only method=cur is evaluated (cur_oracle needs the whole matrix on one device)")
 			grids["eval_methods"] = ["cur"]
+			if rerank_pool != "retrieved":
+				LOGGER.info("row-sharded run: --rerank_pool is ignored (the pool metrics are evaluated on one device)")
 			eval_res = harness.run_entry_A_sharded(sharded, grids, n_seeds, progress)
 			if eval_res is None:          # ranks > 0 are done
 				return res_dir
@@ -109,7 +112,10 @@ def run(base_res_dir, data_info, n_seeds, plot_only, misc, arg_dict, grid_overri
 			if torch.device(device).type == "cuda":
 				torch.cuda.set_device(device)   # the launch stream and torch's allocations follow --device
 			A_dev = chunked["A_local"] if chunked is not None else harness.to_device_matrix(scores, device, dtype)
-			eval_res = harness.run_entry_A(A_dev, grids, n_seeds, progress, pinv_backend, compute_dtype)
+			if rerank_pool == "retrieved":
+				eval_res = harness.run_entry_A(A_dev, grids, n_seeds, progress, pinv_backend, compute_dtype)
+			else:
+				eval_res = harness.run_entry_A(A_dev, grids, n_seeds, progress, pinv_backend, compute_dtype, rerank_pool=rerank_pool)
 		eval_res["other_args"] = other_args
 		with open(f"{res_dir}/retrieval_wrt_exact_crossenc.json", "w") as fout:
 			json.dump(obj=eval_res, fp=fout, indent=4)
@@ -149,6 +155,10 @@ def build_parser(worlds=None, data_dir="../../data/zeshel"):
 	parser.add_argument("--compute_dtype", type=str, default="auto", choices=["auto", "fp32", "bf16", "bf16x3"],
 						help="arithmetic of the CUR retrieval: auto = by --dtype (fp32 matrix -> dense fp32 route, bf16 -> fused bf16 kernel); bf16x3 = for --dtype fp32: "
 							 "operands split into bf16 hi + lo parts on the fused kernel, candidates rescored in fp32 (the fp32 route's values, S_hat never written)")
+	parser.add_argument("--rerank_pool", type=str, default="retrieved", choices=["retrieved", "retrieved+anchors"],
+						help="items the exact re-rank of a CUR cell chooses from: retrieved = the k_retvr retrieved items (the reference's cell); retrieved+anchors = "
+							 "additionally report, under exact_vs_reranked_approx_retvr_w_anchors~..., the pool of the anchor items (whose exact scores every query has "
+							 "paid for) plus k_retvr NEW items, a budget of n_anc + k_retvr exact scores per query")
 	parser.add_argument("--score_chunks", type=str, nargs="+", default=None,
 						help="the producer's per-chunk score pickles (mention order) instead of the combined file: ingested chunk by chunk, row-sharded under torchrun")
 	return parser
@@ -160,14 +170,18 @@ def main(argv=None):
 	if args.bi_model_file != "":
 		raise SystemExit("--bi_model_file: the bi-encoder baseline needs the reference's BERT models and is out of scope of this build")
 	misc = "_" + args.misc if args.misc != "" else ""
+	arg_dict = dict(args.__dict__)
+	if args.rerank_pool == "retrieved":
+		del arg_dict["rerank_pool"]   # the default run writes the output it wrote before the flag existed, byte for byte
 	datasets = get_dataset_info(data_dir=args.data_dir, res_dir=args.res_dir, worlds=worlds, n_ment=args.n_ment)
 	LOGGER.info(f"Running inference for world = {args.data_name}")
 	return run(base_res_dir=f"{args.res_dir}/{args.data_name}/Retrieval_wrt_Exact_CrossEnc", data_info=(args.data_name, datasets[args.data_name]),
-			   n_seeds=args.n_seeds, plot_only=bool(args.plot_only), misc=misc, arg_dict=dict(args.__dict__),
+			   n_seeds=args.n_seeds, plot_only=bool(args.plot_only), misc=misc, arg_dict=arg_dict,
 			   grid_overrides={"eval_methods": args.eval_methods, "n_ment_anchors_vals": args.n_ment_anchors_vals,
 							   "n_ent_anchors_vals": args.n_ent_anchors_vals, "top_k_vals": args.top_k_vals, "top_k_retr_vals": args.top_k_retr_vals},
 			   dtype=args.dtype, device=torch.device(args.device), pinv_backend=args.pinv, score_chunks=args.score_chunks,
-			   compute_dtype=None if args.compute_dtype == "auto" else args.compute_dtype)
+			   compute_dtype=None if args.compute_dtype == "auto" else args.compute_dtype,
+			   **({} if args.rerank_pool == "retrieved" else {"rerank_pool": args.rerank_pool}))
 
 
 if __name__ == "__main__":

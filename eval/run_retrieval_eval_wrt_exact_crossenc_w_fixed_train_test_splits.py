@@ -49,11 +49,12 @@ def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, de
 		if getattr(args, key) is not None:
 			grids[key] = sorted(set(getattr(args, key)))
 	A_test_dev = harness.to_device_matrix(A_test, device, args.dtype)
+	pool_kw = {} if args.rerank_pool == "retrieved" else {"rerank_pool": args.rerank_pool}   # (non-CUR methods ignore the flag)
 	LOGGER.info(f"Computing approximate test mention-to-entity scores using method={curr_method}")
 	if curr_method == "cur":
 		A_train_dev = harness.to_device_matrix(A_train, device, args.dtype)
 		res = harness.run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None if args.compute_dtype == "auto" else args.compute_dtype,
-										  progress=lambda j, n: LOGGER.info(f"anchor count {j + 1}/{n}"), pinv_backend=args.pinv)
+										  progress=lambda j, n: LOGGER.info(f"anchor count {j + 1}/{n}"), pinv_backend=args.pinv, **pool_kw)
 	elif curr_method in ("bienc", "tfidf"):
 		if not (args.mention_embeds_file and args.entity_embeds_file):
 			raise SystemExit(f"eval_method={curr_method}: pass --mention_embeds_file and --entity_embeds_file (.npy); "
@@ -74,7 +75,7 @@ def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, de
 			ment = ops.gather_cols(A_test_dev, anc, out_dtype=torch.float32)
 			res = harness.run_eval_method_embeds(A_test_dev, ment, full[:, :args.n_fixed_anc_ent].contiguous(), n_train, grids)
 		else:
-			res = harness.run_eval_method_fixed_anc_ent_cur(A_test_dev, full, args.n_fixed_anc_ent, grids, key_n_m=n_train)
+			res = harness.run_eval_method_fixed_anc_ent_cur(A_test_dev, full, args.n_fixed_anc_ent, grids, key_n_m=n_train, **pool_kw)
 	else:
 		raise NotImplementedError(f"Method = {curr_method} not supported")
 	params = {"top_k_retr_vals": grids["top_k_retr_vals"], "top_k_vals": grids["top_k_vals"], "n_ent_anchors_vals": grids["n_ent_anchors_vals"]}
@@ -93,6 +94,8 @@ def run(args, device):
 		curr_res, retvr_params = run_eval_method(eval_method, args.test_data_file, args.train_data_file, args, seed, device)
 		eval_res[f"seed={seed}"] = curr_res
 	arg_dict = dict(args.__dict__)
+	if args.rerank_pool == "retrieved":
+		del arg_dict["rerank_pool"]   # the default run writes the output it wrote before the flag existed, byte for byte
 	eval_res["other_args"] = arg_dict
 	eval_res["other_args"]["retriever_params"] = retvr_params
 	res_file = f"{args.res_dir}/method={eval_method}_{args.misc}.json"
@@ -133,6 +136,10 @@ def build_parser(worlds=None):
 	parser.add_argument("--pinv", type=str, default="auto", choices=["numpy", "device", "auto", "device32"],
 						help="pseudo-inverse: numpy = the reference's numpy.linalg.pinv on the host (bit-identical U); device = fp64 Newton-Schulz on the GPU "
 							 "(exact pseudo-inverse of the fp32 block, rounded once); auto = device while the block is well conditioned, else numpy")
+	parser.add_argument("--rerank_pool", type=str, default="retrieved", choices=["retrieved", "retrieved+anchors"],
+						help="items the exact re-rank of a CUR cell chooses from: retrieved = the k_retvr retrieved items (the reference's cell); retrieved+anchors = "
+							 "additionally report, under exact_vs_reranked_approx_retvr_w_anchors~..., the pool of the anchor items (whose exact scores every query has "
+							 "paid for) plus k_retvr NEW items, a budget of n_anc + k_retvr exact scores per query (cur, fixed_anc_ent_cur; other methods ignore it)")
 	parser.add_argument("--compute_dtype", type=str, default="auto", choices=["auto", "fp32", "bf16", "bf16x3"],
 						help="arithmetic of the CUR retrieval: auto = by --dtype (fp32 matrix -> dense fp32 route, bf16 -> fused bf16 kernel); bf16x3 = for --dtype fp32: "
 							 "operands split into bf16 hi + lo parts on the fused kernel, candidates rescored in fp32 (the fp32 route's values, S_hat never written)")

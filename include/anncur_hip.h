@@ -342,6 +342,30 @@ int anncur_overlap_counts(const int32_t *a, int32_t la, const int32_t *b, int32_
                           const int32_t *ka, const int32_t *kb, int32_t n_pairs,
                           int32_t *common, void *stream);
 
+/* search without the exact matrix: re-rank from caller-supplied scores ---------------------------------------------
+ *   temp[approx_idx] = exact[approx_idx]; temp.topk(k)      ..._splits.py:91-96 ; ...crossenc.py:108-113
+ *   the anchor items' exact scores, which every query has paid for already        ..._w_fixed_train_test_splits.py:297-301
+ * anncur_rerank reads exact scores from a resident [Q x I] matrix; a caller who searches holds them in two other forms, and the pool of
+ * query q is the union of the two:
+ *   shared source     sh_ids int32[n_sh], STRICTLY ASCENDING and non-negative (the kernel binary-searches them and trusts the order, as
+ *                     anncur_filter_topk does), with scores sh_val[q*ld_sh + 0..n_sh) of sh_dtype (ANNCUR_F32 / ANNCUR_BF16) -- the anchor
+ *                     scores X.  n_sh may be 0; both pointers may then be NULL;
+ *   per-query source  pq_idx int32[Q x ld_pq], pq_val float[Q x ld_pq], the first n_pq entries of a row; an id < 0 is a hole and is
+ *                     skipped; the ids of a row are distinct (a contract, as for anncur_rerank).  n_pq may be 0 (NULL pointers allowed).
+ * A per-query entry whose id occurs in sh_ids is dropped and the shared source's score stands: a caller who did not exclude the anchors at
+ * retrieval still gets every item once.  out_val float[Q x k_out], out_idx int32[Q x k_out], contiguous: the k_out best of the pool, score
+ * descending, ties by the smaller id; NaN is never selected, -inf is an ordinary candidate, (-inf, -1) pads a row with fewer than k_out
+ * valid entries.  0 <= n_sh <= 65535, 0 <= n_pq <= ANNCUR_MAX_TOPK, n_sh + n_pq >= 1, 1 <= k_out <= min(ANNCUR_MAX_TOPK, n_sh + n_pq),
+ * Q >= 0 (Q == 0 returns OK); anything else is ANNCUR_E_INVALID and nothing is written.  One workgroup per query; no workspace. */
+int anncur_rerank_scored(const int32_t *sh_ids, const void *sh_val, int sh_dtype, int64_t ld_sh, int64_t n_sh,
+                         const int32_t *pq_idx, const float *pq_val, int64_t ld_pq, int32_t n_pq,
+                         int64_t Q, int32_t k_out, float *out_val, int32_t *out_idx, void *stream);
+/* out[q*ldo + j] = (float) A[q, idx[q*ld_idx + j]] for j < n: the exact scores of per-query candidates out of a stored matrix (the
+ * evaluation mode's stand-in for the cross-encoder call of step 3; ..._splits.py:91-96 reads the same cells).  A [Q x I] (dtype, pitch
+ * lda); an id outside [0, I) yields NaN, which no selector here takes.  Q n random sectors, as anncur_gather_cols. */
+int anncur_gather_pairs(const void *A, int dtype, int64_t Q, int64_t I, int64_t lda, const int32_t *idx, int64_t ld_idx, int32_t n,
+                        float *out, int64_t ldo, void *stream);
+
 /* f3: IVF-flat inner-product index (the branch of build_flat_or_ivff_index above 11 000 vectors) -------------------------------
  *   faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT).train / .add / .search     models/nearest_nbr.py:40-52
  * FAISS is not vendored nor pinned by the reference (parity unpinned): restated from the published algorithm, judged on recall
