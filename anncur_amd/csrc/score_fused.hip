@@ -92,9 +92,9 @@ struct FusedParams {
 	int nseg;                         // candidate segments per query (2 S: 32x32x16 body, lane halves; S: 16x16x32 body)
 	int rb_major;                     // work id -> (row block, split): 0 = split-major (1 = row-block-major: see launch_fused)
 	int flush_tiles;                  // wave-cooperative queue flush period (tiles)
-	// Left over from retired tuning experiments, always 0 / their defaults: tau_bias and rb_major are still read by the kernels;
-	// debug_nostore, debug_stamp, prio_mode, nfb, ring_stagger and ring_spin_sleep by none.  They stay while removing them would
-	// change the kernel argument layout.
+	// Left over from retired tuning experiments, always 0: tau_bias and rb_major are still read by the kernels; debug_nostore,
+	// debug_stamp, prio_mode, ring_stagger and ring_spin_sleep by none (launch_fused leaves them zero).  They stay while removing them
+	// would change the kernel argument layout.
 	int debug_nostore;
 	int debug_stamp;
 	float tau_bias;
@@ -110,7 +110,7 @@ struct FusedParams {
 	int prio_mode;
 	int ladder_on; uint32_t ladder_k, ladder_mask;   // ladder_mask = period - 1 (a power of two): tiles between two fetches of a wave's counter words
 	const float *ladder; uint32_t *ladder_cnt; float *tau_final;
-	uint32_t *nfb;                    // workspace word 0
+	uint32_t *nfb;                    // workspace word 0 (zero_ws_header)
 	int ring_stagger, ring_spin_sleep;
 	uint32_t zero_bytes;              // prepass kernels: workspace bytes [0, zero_bytes) to clear (a multiple of 16; 0: none) -- see zero_ws_header
 };
@@ -1496,10 +1496,13 @@ namespace {
 // ------------------------------------------------------------------ host-side plan
 struct FusedPlan {
 	bool ok;
+	bool wide;    // the plan of wide_kernel (Kp > 512, score_wide.hpp): n_tiles, stage_end, tiles_per_split count block tiles of 256 items, not tiles of 32
 	int QT, BQ, n_rb, n_tiles, n_full, S, tiles_per_split, group, n_st, S0, st_per_split, n_groups, capg, kmax, flush_tiles;
 	int n_stages, stage_end[3], stage_tps[3], stage_flush[3], stage_pred[3];
 	int leading;
-	int lg;   // candidate segments per query and item split: 2 (32x32x16 sweep: lane halves), 1 (16x16x32 sweep: wave-level queue)
+	int lg;   // candidate segments per query and item split: 2 (32x32x16 sweep: lane halves), 1 (16x16x32 sweep: wave-level queue),
+	          // 4 (wide kernel: lane half x wave item half)
+	int nseg;     // candidate segments per query: lg S
 	bool body16;  // the sweep stages run score16_kernel
 	bool bodyef;  // the sweep stages run evalf_kernel (anncur_eval_fused: candidates + error sums in one pass; 32x32x16, wave queue, static shares)
 	bool bodyq16; // the sweep stages run scoreq16_kernel (Kp = 512: wave-level queue and tickets on 16x16x32 MFMAs)
@@ -1580,31 +1583,90 @@ void plan_stages(FusedPlan &P, int64_t Q, int k, double exp_hits, bool staged, d
 	}
 }
 
-FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, bool mfma16 = false, bool qt1 = false, bool mfma32 = false, bool evalf = false,
-					 bool no_ladder = false) {
+// ---- what plan_fused and plan_wide share: one plan structure in two tile units (32 items; block tiles of 256 items).  Where the two differ,
+// it shows as an argument here or stays in the planner.
+// `slack`: items the last tile may reach past I while indices stay below 2^31
+bool plan_shape_ok(int64_t Q, int64_t I, int k, int slack) {
+	return k >= 1 && k <= ANNCUR_MAX_TOPK && Q >= 1 && I >= 1 && I < (int64_t)0x7fffffff - slack && k <= I;
+}
+// Prepass sample: enough groups that the k-th largest group maximum is a tight bound.  A sampled tile gives `gpt16` groups of 16 items or
+// 4 gpt16 groups of 4, and stands for at least `min_sweep` full tiles.  False: the problem is too small for the fused path (dense GEMM + scan).
+bool plan_sample(FusedPlan &P, int k, int gpt16, int min_sweep) {
+	const int target = (4 * k > 512) ? 4 * k : 512;
+	const int n16 = (target + gpt16 - 1) / gpt16;
+	if ((int64_t)n16 * 8 <= P.n_full) { P.group = 16; P.n_st = n16; }
+	else { P.group = 4; P.n_st = (target + 4 * gpt16 - 1) / (4 * gpt16); }
+	if ((int64_t)P.n_st * min_sweep > P.n_full) return false;
+	P.n_groups = P.n_st * (P.group == 16 ? gpt16 : 4 * gpt16);
+	return P.n_groups >= k;
+}
+// item splits of the prepass over the sample tiles
+void plan_prepass_splits(FusedPlan &P, int slots) {
+	int S0 = slots / P.n_rb;
+	if (S0 < 1) S0 = 1;
+	if (S0 > P.n_st) S0 = P.n_st;
+	P.st_per_split = (P.n_st + S0 - 1) / S0;
+	P.S0 = (P.n_st + P.st_per_split - 1) / P.st_per_split;
+}
+// Candidate segments (P.lg and P.S are set): capacity for the expected survivors per query ~ 1.3 k * (tiles / sample tiles), spread over the
+// lg S segments of a query.  Returns the survivors the stage plan should expect.
+// (segment capacity -- hence the workspace size -- is planned for the strided sample whatever the hint; with item rows ordered
+//  by descending norm the leading sample's threshold lets ~40 % fewer elements through: measured on the synthetic protocol)
+double plan_segments(FusedPlan &P, int k, bool leading) {
+	P.nseg = P.lg * P.S;
+	const double exp_hits_cap = 1.3 * k * ((double)P.n_tiles / P.n_st);
+	const double per_seg = exp_hits_cap / (double)P.nseg;
+	int capg = next_pow2((int)(4.0 * per_seg) + 32);
+	if (capg < 64) capg = 64;
+	if (capg > 16384) capg = 16384;
+	P.capg = capg;
+	return (leading ? 0.65 : 1.0) * exp_hits_cap;
+}
+// The workspace: 256-byte aligned regions behind the 256-byte header.  A region the plan does not have (the ladder's; the wide plan's ticket
+// counters and owner map) has size 0 and leaves the offset where it was.  Last step of a plan: sets kmax and ok.
+void plan_workspace(FusedPlan &P, int64_t Q, int k, size_t ctr_bytes, size_t owner_bytes) {
+	P.kmax = k <= 128 ? 128 : (k <= 512 ? 512 : 2048);
+	const size_t ladder_rows = P.ladder ? (size_t)P.n_rb * P.BQ : 0;
+	size_t off = 256;
+	auto region = [&off](size_t bytes) { const size_t at = off; off = align256(off + bytes); return at; };
+	P.off_ctr = region(ctr_bytes);                            // ticket counters [stage][row block][slice]: zeroed with the header by the prepass (zero_ws_header)
+	P.off_lcnt = region(ladder_rows * 16);                    // ladder counter words: zeroed with the header too
+	P.off_gmax = region((size_t)Q * P.n_groups * 4);
+	P.off_tval = region((size_t)Q * k * 4);
+	P.off_tidx = region((size_t)Q * k * 4);
+	P.off_segcnt = region((size_t)Q * P.nseg * 4);
+	P.off_tau = region((size_t)Q * 4);
+	P.off_hard = region((size_t)Q * 4);
+	P.off_owner = region(owner_bytes);                        // chunk owners
+	P.off_lvl = region(ladder_rows * 4 * LADDER_LEVELS);
+	P.off_tau2 = region(P.ladder ? (size_t)Q * 4 : 0);
+	P.off_cand = region((size_t)Q * P.nseg * (size_t)P.capg * 8);
+	P.total = off;
+	P.ok = true;
+}
+
+// What a caller asks of the plan: the flags word of the C entry points (plan_opts_of_flags below: ANNCUR_TOPK_LEADING_SAMPLE, _MFMA16, _QT1,
+// _MFMA32, _STAGED = no_ladder), or anncur_eval_fused (evalf: the sweep stages run evalf_kernel)
+struct PlanOpts { bool leading = false, mfma16 = false, qt1 = false, mfma32 = false, evalf = false, no_ladder = false; };
+PlanOpts evalf_opts() { PlanOpts o; o.evalf = true; return o; }
+
+FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, const PlanOpts &opts) {
 	FusedPlan P{};
-	P.ok = false;
+	if (!(KP == 64 || KP == 128 || KP == 256 || KP == 512) || !plan_shape_ok(Q, I, k, 64)) return P;
+	const bool evalf = opts.evalf;
+	if (evalf && !(KP <= 256 && I < (int64_t)(1 << 26))) return P;   // anncur_eval_fused: Kp <= 256 (two workgroups per CU), queue entries carry the query
+	// (anncur_eval_fused has one body and samples in item order: the variants and the hint do not apply)
+	const bool leading = opts.leading && !evalf, mfma16 = opts.mfma16 && !evalf, qt1 = opts.qt1 && !evalf, mfma32 = opts.mfma32 && !evalf, no_ladder = opts.no_ladder;
 	P.leading = leading ? 1 : 0;
-	if (!(KP == 64 || KP == 128 || KP == 256 || KP == 512)) return P;
-	if (k < 1 || k > ANNCUR_MAX_TOPK || Q < 1 || I < 1 || I >= (int64_t)0x7fffffff - 64 || k > I) return P;
+	P.bodyef = evalf;
 	// qt1 (ANNCUR_TOPK_QT1, Kp = 128 / 256): one 32-query sub-tile per wave with the cross-tile pipeline of the Kp = 512 sweep,
 	// 3 workgroups per CU (<= 168 VGPRs) instead of two sub-tiles staggered inside a wave at 2 workgroups per CU
-	if (evalf && !(KP <= 256 && I < (int64_t)(1 << 26))) return P;   // anncur_eval_fused: Kp <= 256 (two workgroups per CU), queue entries carry the query
-	if (evalf) { qt1 = false; mfma16 = false; mfma32 = false; leading = false; P.leading = 0; }
-	P.bodyef = evalf;
 	P.QT = (KP <= 256 && !(qt1 && KP >= 128)) ? 2 : 1;
 	P.BQ = 128 * P.QT;
 	P.n_rb = (int)ceil_div64(Q, P.BQ);
 	P.n_tiles = (int)ceil_div64(I, TILE_I);
 	P.n_full = (int)(I / TILE_I);
-	// prepass sample: enough groups that the k-th largest group maximum is a tight bound
-	int target = (4 * k > 512) ? 4 * k : 512;
-	int n_st16 = (target + 1) / 2;
-	if ((int64_t)n_st16 * 8 <= P.n_full) { P.group = 16; P.n_st = n_st16; }
-	else { P.group = 4; P.n_st = (target + 7) / 8; }
-	if ((int64_t)P.n_st * 4 > P.n_full) return P;  // problem too small for the fused path: use dense GEMM + scan
-	P.n_groups = P.n_st * (P.group == 16 ? 2 : 8);
-	if (P.n_groups < k) return P;
+	if (!plan_sample(P, k, 2, 4)) return P;   // two groups of 16 per sampled tile (the sub-tile rows with bit 2 clear / set)
 	int slots = ((P.QT == 1 && KP <= 256) ? 3 : 2) * num_cu();
 	// Dynamic tile schedule (staggered 32x32x16 sweep, Kp <= 256): tickets of CHUNK_TILES tiles per query row block instead of fixed shares
 	// (score_kernel).  Workgroups per row block: enough to fill every slot (rounded UP -- a workgroup that finds no ticket left ends at
@@ -1653,23 +1715,10 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 	// tiles' elements pass the first threshold: the rings' raw-tile hand-over is built for that).  ANNCUR_TOPK_MFMA16 / _MFMA32 force one.
 	// Measured at cfg2, MI355X, same box, alternating (round 3): sweep launches 0.457 ms (16x16x32) vs 0.479 (32x32x16) at equal stage
 	// split, 0.450 with the split below; a mixed plan (first stage 32x32x16, later stages 16x16x32) was level with 16x16x32 throughout.
-	int S0 = slots / P.n_rb;
-	if (S0 < 1) S0 = 1;
-	if (S0 > P.n_st) S0 = P.n_st;
-	P.st_per_split = (P.n_st + S0 - 1) / S0;
-	P.S0 = (P.n_st + P.st_per_split - 1) / P.st_per_split;
+	plan_prepass_splits(P, slots);
 	// candidate segments per (query, item split): two (lane halves) in the 32x32x16 sweep, ONE in the 16x16x32 sweep (wave-level queue)
 	P.lg = (P.body16 || P.bodyq16 || P.bodyef) ? 1 : 2;
-	// expected survivors per query ~ 1.3 k * (tiles / sample tiles), spread over lg S lane segments
-	// (segment capacity -- hence the workspace size -- is planned for the strided sample whatever the hint; with item rows ordered
-	//  by descending norm the leading sample's threshold lets ~40 % fewer elements through: measured on the synthetic protocol)
-	const double exp_hits_cap = 1.3 * k * ((double)P.n_tiles / P.n_st);
-	const double exp_hits = (leading ? 0.65 : 1.0) * exp_hits_cap;
-	const double per_seg = exp_hits_cap / ((double)P.lg * P.S);
-	int capg = next_pow2((int)(4.0 * per_seg) + 32);
-	if (capg < 64) capg = 64;
-	if (capg > 16384) capg = 16384;
-	P.capg = capg;
+	const double exp_hits = plan_segments(P, k, leading);
 	// queue window: keep the expected hits per (lane, sub-tile) window near 0.5 so that 8 slots overflow with p ~ 1e-9
 	const double per_lane_tile = exp_hits / ((double)P.n_tiles * 2.0);  // hits per query-half per tile
 	int ft = (int)(0.35 / (per_lane_tile > 1e-9 ? per_lane_tile : 1e-9));
@@ -1686,50 +1735,26 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, bool leading = false, 
 		if (k2 > k) k2 = k;
 		P.ladder_k2 = k2;
 	}
-	plan_stages(P, Q, k, exp_hits, !P.ladder && (k <= WQ_K2 ? P.lg * P.S <= WAVE : true) && P.n_tiles >= 24 * P.S, 4.0 * P.S / P.n_tiles, TILE_I);
-	P.kmax = k <= 128 ? 128 : (k <= 512 ? 512 : 2048);
-	size_t off = 256;
-	P.off_ctr = off;    off = align256(off + (size_t)P.n_rb * 3 * 4 * N_SLICES);   // ticket counters [stage][row block][slice]: zeroed with the header by the prepass (zero_ws_header)
-	P.off_lcnt = off;   off = align256(off + (P.ladder ? (size_t)P.n_rb * P.BQ * 16 : 0));   // ladder counter words: zeroed with the header too
-	P.off_gmax = off;   off = align256(off + (size_t)Q * P.n_groups * 4);
-	P.off_tval = off;   off = align256(off + (size_t)Q * k * 4);
-	P.off_tidx = off;   off = align256(off + (size_t)Q * k * 4);
-	P.off_segcnt = off; off = align256(off + (size_t)Q * P.lg * P.S * 4);
-	P.off_tau = off;    off = align256(off + (size_t)Q * 4);
-	P.off_hard = off;   off = align256(off + (size_t)Q * 4);
-	P.off_owner = off;  off = align256(off + (size_t)3 * P.n_rb * (size_t)(P.n_tiles / (P.chunk > 0 ? P.chunk : P.n_tiles) + 2));   // chunk owners
-	P.off_lvl = off;    off = align256(off + (P.ladder ? (size_t)P.n_rb * P.BQ * 4 * LADDER_LEVELS : 0));
-	P.off_tau2 = off;   off = align256(off + (P.ladder ? (size_t)Q * 4 : 0));
-	P.off_cand = off;   off = align256(off + (size_t)Q * P.lg * P.S * (size_t)P.capg * 8);
-	P.total = off;
-	P.ok = true;
+	plan_stages(P, Q, k, exp_hits, !P.ladder && (k <= WQ_K2 ? P.nseg <= WAVE : true) && P.n_tiles >= 24 * P.S, 4.0 * P.S / P.n_tiles, TILE_I);
+	plan_workspace(P, Q, k, (size_t)P.n_rb * 3 * 4 * N_SLICES, (size_t)3 * P.n_rb * (size_t)(P.n_tiles / (P.chunk > 0 ? P.chunk : P.n_tiles) + 2));
 	return P;
 }
-
-#define EV(i) do { if (ev) ANNCUR_HIP_OK(hipEventRecord(ev[i], st)); } while (0)
-
-// k <= 128: the buffer-and-compact wave-level select runs; the streaming one (select_stream_kernel<false, 2>) stays compiled, never chosen
-constexpr bool STREAM_SELECT_SMALL = false;
 
 // Threshold refinement between two sweep stages: tau[q] = max(tau[q], k-th best candidate collected so far).
 int launch_tau_refine(const uint2 *cand, const uint32_t *seg_cnt, int nseg, int capg, int64_t Q, int k, int kmax, float *tau, int tau_stride,
 					  int prefilter, hipStream_t st) {
 	int rc;
 	if (k <= WQ_K2 && nseg <= WAVE) {
-#define LAUNCH_WTAU(KW)                                                                                                           \
-		do {                                                                                                                      \
-			constexpr int lds = 4 * WaveSelLayout<WqCfg<KW>::CAP>::BYTES;                                                         \
-			if ((rc = anncur_ensure_dyn_lds((const void *)select_wave_kernel<true, KW>, lds)) != ANNCUR_OK) return rc;            \
-			hipLaunchKernelGGL((select_wave_kernel<true, KW>), dim3((unsigned)ceil_div64(Q, 4)), dim3(256), lds, st, cand, seg_cnt, nseg, capg, Q, \
-							   (uint32_t)k, (float *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, tau, tau_stride, prefilter, (const int32_t *)nullptr); \
-		} while (0)
-		if (k <= WSEL_K) LAUNCH_WTAU(128);
-		else {  // streaming radix select (select_stream.hpp): 1 KB of LDS per wave
+		if (k <= WSEL_K) {
+			constexpr int lds = 4 * WaveSelLayout<WqCfg<128>::CAP>::BYTES;
+			if ((rc = anncur_ensure_dyn_lds((const void *)select_wave_kernel<true, 128>, lds)) != ANNCUR_OK) return rc;
+			hipLaunchKernelGGL((select_wave_kernel<true, 128>), dim3((unsigned)ceil_div64(Q, 4)), dim3(256), lds, st, cand, seg_cnt, nseg, capg, Q,
+							   (uint32_t)k, (float *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, tau, tau_stride, prefilter, (const int32_t *)nullptr);
+		} else {  // streaming radix select (select_stream.hpp): 1 KB of LDS per wave
 			constexpr int lds = 4 * StreamSelLayout::BYTES;
 			hipLaunchKernelGGL((select_stream_kernel<true, 2>), dim3((unsigned)ceil_div64(Q, 4)), dim3(256), lds, st, cand, seg_cnt, nseg, capg, Q,
 							   (uint32_t)k, (float *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, tau, tau_stride, prefilter, (const int32_t *)nullptr);
 		}
-#undef LAUNCH_WTAU
 	} else {
 #define LAUNCH_TAU(KM)                                                                                                        \
 		do {                                                                                                                  \
@@ -1746,7 +1771,7 @@ int launch_tau_refine(const uint2 *cand, const uint32_t *seg_cnt, int nseg, int 
 
 // Per-query exact top-k of the collected candidates.  Fast path: one wave per query (k <= 128, <= 64 segments); what it cannot
 // take (overflowed segment, fewer than k candidates) lands in hard_list for the workgroup-level kernel, which repairs it exactly.
-int launch_select(const FusedPlan &P, int nseg, const SweepStages &stages, const uint2 *cand, const uint32_t *seg_cnt, const uint16_t *X, int64_t ldx,
+int launch_select(const FusedPlan &P, const SweepStages &stages, const uint2 *cand, const uint32_t *seg_cnt, const uint16_t *X, int64_t ldx,
 				  const uint16_t *Et, int64_t Q, int64_t I, int KP, int k, float *out_val, int32_t *out_idx, unsigned char *ws, const float *tau,
 				  int tau_stride, hipStream_t st, const int32_t *remap = nullptr) {
 	int rc;
@@ -1754,30 +1779,30 @@ int launch_select(const FusedPlan &P, int nseg, const SweepStages &stages, const
 	do {                                                                                                               \
 		const size_t lds = SelCfg<KM>::LDS_BYTES + (size_t)KP * 4 + 32;                                                \
 		if ((rc = anncur_ensure_dyn_lds((const void *)select_candidates_kernel<KM>, (int)lds)) != ANNCUR_OK) return rc; \
-		hipLaunchKernelGGL((select_candidates_kernel<KM>), dim3(sel_grid), dim3(SEL_THREADS), lds, st, cand, seg_cnt, nseg, \
+		hipLaunchKernelGGL((select_candidates_kernel<KM>), dim3(sel_grid), dim3(SEL_THREADS), lds, st, cand, seg_cnt, P.nseg, \
 						   P.S, stages, P.capg, X, ldx, Et, I, KP, (uint32_t)k, out_val, out_idx, (uint32_t *)ws, hard_list, hard_cnt,      \
 						   (P.n_stages > 1 || P.ladder) ? tau : (const float *)nullptr, tau_stride, remap);                              \
 	} while (0)
 	const int32_t *hard_list = nullptr;
 	const uint32_t *hard_cnt = nullptr;
 	unsigned sel_grid = (unsigned)Q;
-	if (k <= WQ_K2 && nseg <= WAVE) {
+	if (k <= WQ_K2 && P.nseg <= WAVE) {
 		int32_t *hl = (int32_t *)(ws + P.off_hard);
 		uint32_t *hc = (uint32_t *)(ws + 4);
 #define LAUNCH_WSEL(KW)                                                                                                           \
 		do {                                                                                                                      \
 			constexpr int lds = 4 * WaveSelLayout<WqCfg<KW>::CAP>::BYTES;                                                         \
 			if ((rc = anncur_ensure_dyn_lds((const void *)select_wave_kernel<false, KW>, lds)) != ANNCUR_OK) return rc;           \
-			hipLaunchKernelGGL((select_wave_kernel<false, KW>), dim3((unsigned)ceil_div64(Q, 4)), dim3(256), lds, st, cand, seg_cnt, nseg, P.capg, Q, \
+			hipLaunchKernelGGL((select_wave_kernel<false, KW>), dim3((unsigned)ceil_div64(Q, 4)), dim3(256), lds, st, cand, seg_cnt, P.nseg, P.capg, Q, \
 							   (uint32_t)k, out_val, out_idx, hc, hl, const_cast<float *>(tau), tau_stride, (P.n_stages > 1 || P.ladder) ? 1 : 0, remap); \
 		} while (0)
 #define LAUNCH_SSEL(EE)                                                                                                           \
 		do {                                                                                                                      \
 			constexpr int lds = 4 * StreamSelLayout::BYTES;                                                                       \
-			hipLaunchKernelGGL((select_stream_kernel<false, EE>), dim3((unsigned)ceil_div64(Q, 4)), dim3(256), lds, st, cand, seg_cnt, nseg, P.capg, Q, \
+			hipLaunchKernelGGL((select_stream_kernel<false, EE>), dim3((unsigned)ceil_div64(Q, 4)), dim3(256), lds, st, cand, seg_cnt, P.nseg, P.capg, Q, \
 							   (uint32_t)k, out_val, out_idx, hc, hl, const_cast<float *>(tau), tau_stride, (P.n_stages > 1 || P.ladder) ? 1 : 0, remap); \
 		} while (0)
-		if (k <= WSEL_K) { if (STREAM_SELECT_SMALL) LAUNCH_SSEL(2); else LAUNCH_WSEL(128); }
+		if (k <= WSEL_K) LAUNCH_WSEL(128);
 		else if (k <= 256) LAUNCH_SSEL(4);
 		else if (k <= 512) LAUNCH_SSEL(8);
 		else LAUNCH_SSEL(16);
@@ -1890,70 +1915,121 @@ bool exact_tile_offsets_fit(int64_t lda, int bq) { return lda >= 0 && (uint64_t)
 // anncur_eval_fused: the exact matrix and the two per-row sums the sweep stages also produce (evalf_kernel)
 struct EvalArgs { const uint16_t *A; int64_t lda; float *err_sq, *norm_sq; const uint16_t *Et_hint; };   // Et_hint: see anncur_eval_fused_ex (may be null)
 
+// one fused top-k call as the launchers see it (score_topk_impl has checked the arguments against the plan)
+struct TopkCall {
+	const void *X; int64_t ldx; const void *Et; int64_t Q, I; int KP, k; float *out_val; int32_t *out_idx; unsigned char *ws; hipStream_t st;
+	hipEvent_t *ev;             // anncur_score_topk_timed: its 11 events (null otherwise)
+	CoScan *co;                 // anncur_eval_topk: the exact scan to co-schedule (null otherwise)
+	const int32_t *item_ids;    // may be null
+	const EvalArgs *ea;         // anncur_eval_fused (null otherwise)
+};
+
+// The launch sequence of every route: prepass, threshold, sweep in stages (between two stages the thresholds are raised from the candidates
+// collected so far), select.  A route supplies its two MFMA-bound launches -- launch_prepass(), launch_stage(stg, first tile): both return an
+// error code --, where the threshold goes (tau, tau_stride of its parameter struct, set before the first stage) and what the select's repair
+// path needs of it (`stages`; the stage ranges are filled in here, `unit` 32-item tiles per tile of the plan).  Owned here, once: the event
+// points of anncur_score_topk_timed (0..4 the boundaries, 5 + 2 stg / 6 + 2 stg around each sweep launch) and the co-scan protocol (CoScan).
+template <typename Prepass, typename Stage>
+int run_pipeline(const FusedPlan &P, const TopkCall &c, SweepStages stages, int unit, const float *&tau, int &tau_stride, Prepass launch_prepass, Stage launch_stage) {
+#define EV(i) do { if (c.ev) ANNCUR_HIP_OK(hipEventRecord(c.ev[i], st)); } while (0)
+	unsigned char *const ws = c.ws; const hipStream_t st = c.st;
+	const uint2 *cand = (const uint2 *)(ws + P.off_cand);
+	const uint32_t *seg_cnt = (const uint32_t *)(ws + P.off_segcnt);
+	int rc;
+	EV(0);
+	// 1. prepass
+	if ((rc = launch_prepass()) != ANNCUR_OK) return rc;
+	ANNCUR_LAUNCH_OK();
+	EV(1);
+	// 2. tau = k-th largest group maximum (beside it: the first chunk of the exact scan, anncur_eval_topk only)
+	if ((rc = co_fork(c.co, st)) != ANNCUR_OK) return rc;
+	if ((rc = launch_threshold(P, (const float *)(ws + P.off_gmax), c.Q, c.k, ws, tau, tau_stride, st)) != ANNCUR_OK) return rc;
+	if ((rc = co_join(c.co, st)) != ANNCUR_OK) return rc;
+	EV(2);
+	// 3. sweep, in stages; between stages the thresholds are raised from the candidates collected so far
+	for (int stg = 0, prev = 0; stg < P.n_stages; prev = P.stage_end[stg], ++stg) {
+		EV(5 + 2 * stg);
+		if ((rc = launch_stage(stg, prev)) != ANNCUR_OK) return rc;
+		ANNCUR_LAUNCH_OK();
+		EV(6 + 2 * stg);
+		if (stg + 1 < P.n_stages) {
+			if ((rc = co_fork(c.co, st)) != ANNCUR_OK) return rc;
+			if ((rc = launch_tau_refine(cand, seg_cnt, P.nseg, P.capg, c.Q, c.k, P.kmax, const_cast<float *>(tau), tau_stride, stg > 0 ? 1 : 0, st)) != ANNCUR_OK)
+				return rc;
+			if ((rc = co_join(c.co, st)) != ANNCUR_OK) return rc;
+		}
+	}
+	EV(3);
+	// 4. select (beside it: the last chunk of the exact scan; the caller joins)
+	if ((rc = co_fork(c.co, st)) != ANNCUR_OK) return rc;
+	stages.n = P.n_stages;
+	const int n_tiles32 = (int)ceil_div64(c.I, TILE_I);
+	for (int g = 0, prev = 0; g < P.n_stages; prev = P.stage_end[g], ++g) {
+		stages.begin[g] = prev * unit;
+		stages.end[g] = P.stage_end[g] * unit < n_tiles32 ? P.stage_end[g] * unit : n_tiles32;
+		stages.tps[g] = P.stage_tps[g] * unit;
+	}
+	// (ladder: the prefilter is the highest threshold a workgroup ended the sweep with -- k candidates at or above it were counted)
+	if ((rc = launch_select(P, stages, cand, seg_cnt, (const uint16_t *)c.X, c.ldx, (const uint16_t *)c.Et, c.Q, c.I, c.KP, c.k, c.out_val, c.out_idx, ws,
+							P.ladder ? (const float *)(ws + P.off_tau2) : tau, P.ladder ? 1 : tau_stride, st, c.item_ids)) != ANNCUR_OK) return rc;
+	EV(4);
+	return ANNCUR_OK;
+#undef EV
+}
+
 template <int KP, int QTV = FusedCfg<KP>::QT>
-int launch_fused(const FusedPlan &P, const void *X, int64_t ldx, const void *Et, int64_t Q, int64_t I, int k, float *out_val,
-				 int32_t *out_idx, unsigned char *ws, hipStream_t st, hipEvent_t *ev, CoScan *co = nullptr, const int32_t *item_ids = nullptr,
-				 const EvalArgs *ea = nullptr) {
+int launch_fused(const FusedPlan &P, const TopkCall &c) {
 	using Cfg = FusedCfg<KP, QTV>;
-	FusedParams p{};
-	p.X = (const uint16_t *)X; p.ldx = ldx; p.Et = (const uint16_t *)Et; p.Q = Q; p.I = I;
+	unsigned char *const ws = c.ws; const hipStream_t st = c.st; const EvalArgs *const ea = c.ea;
+	FusedParams p{};   // (the fields no kernel reads stay zero)
+	p.X = (const uint16_t *)c.X; p.ldx = c.ldx; p.Et = (const uint16_t *)c.Et; p.Q = c.Q; p.I = c.I;
 	p.n_tiles = P.n_tiles; p.n_full_tiles = P.n_full; p.S = P.S; p.tiles_per_split = P.tiles_per_split;
 	p.tile_begin = 0; p.tile_end = P.n_tiles; p.carry = 0; p.tile_step = 1;
 	p.n_st = P.n_st; p.S0 = P.S0; p.st_per_split = P.st_per_split; p.sample_leading = P.leading;
 	p.gmax = (float *)(ws + P.off_gmax); p.n_groups = P.n_groups;
 	p.cand = (uint2 *)(ws + P.off_cand); p.seg_cnt = (uint32_t *)(ws + P.off_segcnt); p.capg = P.capg; p.flush_tiles = P.flush_tiles;
 	p.tau_bias = 0.f;
-	p.chunk_tiles = 0; p.n_chunks = 0; p.chunk_ctr = nullptr; p.chunk_owner = nullptr;
-	p.nfb = (uint32_t *)ws;
-	p.ring_stagger = 0; p.ring_spin_sleep = 1;
-	p.nseg = P.lg * P.S;
-	p.prio_mode = 0;
-	p.ladder_on = P.ladder ? 1 : 0; p.ladder_k = (uint32_t)k; p.ladder_mask = (uint32_t)(LADDER_PERIOD - 1);
+	p.nfb = (uint32_t *)ws; p.nseg = P.nseg;
+	p.ladder_on = P.ladder ? 1 : 0; p.ladder_k = (uint32_t)c.k; p.ladder_mask = (uint32_t)(LADDER_PERIOD - 1);
 	p.ladder = (const float *)(ws + P.off_lvl); p.ladder_cnt = (uint32_t *)(ws + P.off_lcnt); p.tau_final = (float *)(ws + P.off_tau2);
 
 	const int chunk = (P.chunk > 0 && (Cfg::QT == 2 || P.bodyq16)) ? P.chunk : 0;   // (the one-sub-tile bodies with per-lane rings keep static shares)
 	const int owner_stride = P.n_rb * (P.n_tiles / (chunk > 0 ? chunk : P.n_tiles) + 2);
-	int rc;
-	EV(0);
-	// 1. prepass; its workgroups also clear the header (+ the stages' ticket counters, the ladder's counter words): zero_ws_header -- no memset launch
-	p.n_wg = P.n_rb * P.S0;
-	{
-		// anncur_eval_fused_ex's hint: the prepass samples the LEADING tiles of the norm-ordered copy (the likeliest high scorers: a tighter first
-		// threshold), the sweep keeps the item order the exact tiles need.  Any subset of the items gives a valid threshold.
-		FusedParams pp = p;
-		pp.zero_bytes = (uint32_t)((chunk > 0 || P.ladder) ? P.off_gmax : 256);
-		if (ea && ea->Et_hint) { pp.Et = ea->Et_hint; pp.sample_leading = 1; }
-		bool pre16 = false;
-		if constexpr (KP <= 256 && QTV == 2) {   // the plans that sweep with score16_kernel: the prepass on the same body (prepass16.hpp)
-			if (P.body16 && P.group == 16) {
-				if ((rc = anncur_ensure_dyn_lds((const void *)prepass16_kernel<KP>, Prepass16Cfg<KP>::LDS_BYTES)) != ANNCUR_OK) return rc;
-				hipLaunchKernelGGL((prepass16_kernel<KP>), dim3(p.n_wg), dim3(256), Prepass16Cfg<KP>::LDS_BYTES, st, pp);
-				pre16 = true;
-			}
-		}
-		if (!pre16 && P.group == 16)
-			hipLaunchKernelGGL((score_kernel<KP, 0, 16, false, false, QTV>), dim3(p.n_wg), dim3(256), 2 * Cfg::TILE_BYTES, st, pp);
-		else if (!pre16)
-			hipLaunchKernelGGL((score_kernel<KP, 0, 4, false, false, QTV>), dim3(p.n_wg), dim3(256), 2 * Cfg::TILE_BYTES, st, pp);
-	}
-	ANNCUR_LAUNCH_OK();
-	EV(1);
-	// 2. tau = k-th largest group maximum (beside it: the first chunk of the exact scan, anncur_eval_topk only)
-	if ((rc = co_fork(co, st)) != ANNCUR_OK) return rc;
-	rc = launch_threshold(P, p.gmax, Q, k, ws, p.tau, p.tau_stride, st);
-	if (rc != ANNCUR_OK) return rc;
-	if ((rc = co_join(co, st)) != ANNCUR_OK) return rc;
-	EV(2);
-	// 3. sweep, in stages; between stages the thresholds are raised from the candidates collected so far.
 	// Item split s of a stage sweeps the tiles begin + s, begin + s + S, ... (interleaved), not a contiguous range: with norm-ordered rows
 	// the survivors crowd into the leading tiles, all the workgroups of a stage run at once, and with contiguous ranges the stage took
 	// as long as its FIRST split (cfg2: the first stage, 22 % of the tiles, 0.236 ms against 0.306 ms for the other 78 %).
 	// (score16_kernel keeps contiguous ranges)
 	const int tile_step = (!P.body16 && !P.bodyq16 && !P.bodyef && P.S > 1 && chunk == 0) ? P.S : 1;
-	p.n_wg = P.n_rb * P.S;
-	if ((rc = anncur_ensure_dyn_lds((const void *)score_kernel<KP, 1, 16, false, false, QTV>, Cfg::LDS_BYTES)) != ANNCUR_OK) return rc;
-	for (int stg = 0, prev = 0; stg < P.n_stages; prev = P.stage_end[stg], ++stg) {
-		EV(5 + 2 * stg);
+	SweepStages stages{};
+	stages.stride = tile_step; stages.chunk = chunk; stages.bq = P.BQ;
+	for (int g = 0, prev = 0; g < P.n_stages; prev = P.stage_end[g], ++g) {
+		stages.n_chunks[g] = chunk > 0 ? (P.stage_end[g] - prev + chunk - 1) / chunk : 0;
+		stages.owner[g] = (const uint8_t *)(ws + P.off_owner) + (size_t)g * owner_stride;
+	}
+
+	// prepass; its workgroups also clear the header (+ the stages' ticket counters, the ladder's counter words): zero_ws_header -- no memset launch
+	auto launch_prepass = [&]() -> int {
+		p.n_wg = P.n_rb * P.S0;
+		// anncur_eval_fused_ex's hint: the prepass samples the LEADING tiles of the norm-ordered copy (the likeliest high scorers: a tighter first
+		// threshold), the sweep keeps the item order the exact tiles need.  Any subset of the items gives a valid threshold.
+		FusedParams pp = p;
+		pp.zero_bytes = (uint32_t)((chunk > 0 || P.ladder) ? P.off_gmax : 256);
+		if (ea && ea->Et_hint) { pp.Et = ea->Et_hint; pp.sample_leading = 1; }
+		if constexpr (KP <= 256 && QTV == 2) {   // the plans that sweep with score16_kernel: the prepass on the same body (prepass16.hpp)
+			if (P.body16 && P.group == 16) {
+				if (const int rcl = anncur_ensure_dyn_lds((const void *)prepass16_kernel<KP>, Prepass16Cfg<KP>::LDS_BYTES)) return rcl;
+				hipLaunchKernelGGL((prepass16_kernel<KP>), dim3(p.n_wg), dim3(256), Prepass16Cfg<KP>::LDS_BYTES, st, pp);
+				return ANNCUR_OK;
+			}
+		}
+		if (P.group == 16)
+			hipLaunchKernelGGL((score_kernel<KP, 0, 16, false, false, QTV>), dim3(p.n_wg), dim3(256), 2 * Cfg::TILE_BYTES, st, pp);
+		else
+			hipLaunchKernelGGL((score_kernel<KP, 0, 4, false, false, QTV>), dim3(p.n_wg), dim3(256), 2 * Cfg::TILE_BYTES, st, pp);
+		return ANNCUR_OK;
+	};
+	auto launch_stage = [&](int stg, int prev) -> int {
+		p.n_wg = P.n_rb * P.S;
 		p.tile_begin = prev; p.tile_end = P.stage_end[stg]; p.tiles_per_split = P.stage_tps[stg];
 		p.flush_tiles = P.stage_flush[stg]; p.carry = stg > 0;
 		p.tile_step = tile_step;
@@ -1971,63 +2047,28 @@ int launch_fused(const FusedPlan &P, const void *X, int64_t ldx, const void *Et,
 			p.chunk_ctr = (uint32_t *)(ws + P.off_ctr) + (size_t)stg * P.n_rb * N_SLICES;
 			p.chunk_owner = (uint8_t *)(ws + P.off_owner) + (size_t)stg * owner_stride;
 		}
-		bool launched = false;
+		// the first body that applies (`if constexpr`: a body is instantiated only for the KP / QTV it exists for)
+		auto launch = [&](auto kernel, int lds, auto... more) -> int {
+			if (const int rcl = anncur_ensure_dyn_lds((const void *)kernel, lds)) return rcl;
+			hipLaunchKernelGGL(kernel, dim3(p.n_wg), dim3(256), lds, st, p, more...);
+			return ANNCUR_OK;
+		};
 		if constexpr (KP <= 256 && QTV == 2) {  // anncur_eval_fused: candidates + error sums in one pass (score_evalf.hpp)
-			if (!launched && P.bodyef) {
-				if (!ea) { anncur_set_error("launch_fused: evalf plan without the exact matrix"); return ANNCUR_E_INVALID; }
-				if ((rc = anncur_ensure_dyn_lds((const void *)evalf_kernel<KP>, EvalFCfg<KP>::LDS_BYTES)) != ANNCUR_OK) return rc;
-				hipLaunchKernelGGL((evalf_kernel<KP>), dim3(p.n_wg), dim3(256), EvalFCfg<KP>::LDS_BYTES, st, p, ea->A, ea->lda, ea->err_sq, ea->norm_sq);
-				launched = true;
-			}
+			if (P.bodyef && !ea) { anncur_set_error("launch_fused: evalf plan without the exact matrix"); return ANNCUR_E_INVALID; }
+			if (P.bodyef) return launch(evalf_kernel<KP>, EvalFCfg<KP>::LDS_BYTES, ea->A, ea->lda, ea->err_sq, ea->norm_sq);
 		}
 		if constexpr (KP == 512) {  // Kp = 512 with the wave-level queue and tickets (score_q16.hpp)
-			if (!launched && P.bodyq16) {
-				if ((rc = anncur_ensure_dyn_lds((const void *)scoreq16_kernel<KP>, FusedQ16Cfg<KP>::LDS_BYTES)) != ANNCUR_OK) return rc;
-				hipLaunchKernelGGL((scoreq16_kernel<KP>), dim3(p.n_wg), dim3(256), FusedQ16Cfg<KP>::LDS_BYTES, st, p);
-				launched = true;
-			}
+			if (P.bodyq16) return launch(scoreq16_kernel<KP>, FusedQ16Cfg<KP>::LDS_BYTES);
 		}
 		if constexpr (KP <= 256 && QTV == 2) {  // 16x16x32 sweep (score16.hpp): one segment per (query, item split)
-			if (!launched && P.body16) {
-				if ((rc = anncur_ensure_dyn_lds((const void *)score16_kernel<KP>, Fused16Cfg<KP>::LDS_BYTES)) != ANNCUR_OK) return rc;
-				hipLaunchKernelGGL((score16_kernel<KP>), dim3(p.n_wg), dim3(256), Fused16Cfg<KP>::LDS_BYTES, st, p);
-				launched = true;
-			}
+			if (P.body16) return launch(score16_kernel<KP>, Fused16Cfg<KP>::LDS_BYTES);
 		}
-		if constexpr (Cfg::QT == 2) {  // (the branch-free filter lives in the staggered path)
-			if (!launched && P.stage_pred[stg]) {
-				if ((rc = anncur_ensure_dyn_lds((const void *)score_kernel<KP, 1, 16, true, false, QTV>, Cfg::LDS_BYTES)) != ANNCUR_OK) return rc;
-				hipLaunchKernelGGL((score_kernel<KP, 1, 16, true, false, QTV>), dim3(p.n_wg), dim3(256), Cfg::LDS_BYTES, st, p);
-				launched = true;
-			}
+		if constexpr (Cfg::QT == 2) {  // the exec-mask filter (the branch-free filter lives in the staggered path)
+			if (P.stage_pred[stg]) return launch(score_kernel<KP, 1, 16, true, false, QTV>, Cfg::LDS_BYTES);
 		}
-		if (!launched) hipLaunchKernelGGL((score_kernel<KP, 1, 16, false, false, QTV>), dim3(p.n_wg), dim3(256), Cfg::LDS_BYTES, st, p);
-		ANNCUR_LAUNCH_OK();
-		EV(6 + 2 * stg);
-		if (stg + 1 < P.n_stages) {
-			if ((rc = co_fork(co, st)) != ANNCUR_OK) return rc;
-			if ((rc = launch_tau_refine(p.cand, p.seg_cnt, P.lg * P.S, P.capg, Q, k, P.kmax, const_cast<float *>(p.tau), p.tau_stride, stg > 0 ? 1 : 0, st)) != ANNCUR_OK)
-				return rc;
-			if ((rc = co_join(co, st)) != ANNCUR_OK) return rc;
-		}
-	}
-	EV(3);
-	// 4. select (beside it: the last chunk of the exact scan; the caller joins)
-	if ((rc = co_fork(co, st)) != ANNCUR_OK) return rc;
-	SweepStages stages{};
-	stages.n = P.n_stages;
-	stages.stride = tile_step;
-	stages.chunk = chunk; stages.bq = P.BQ;
-	for (int g = 0, prev = 0; g < P.n_stages; prev = P.stage_end[g], ++g) {
-		stages.begin[g] = prev; stages.end[g] = P.stage_end[g]; stages.tps[g] = P.stage_tps[g];
-		stages.n_chunks[g] = chunk > 0 ? (P.stage_end[g] - prev + chunk - 1) / chunk : 0;
-		stages.owner[g] = (const uint8_t *)(ws + P.off_owner) + (size_t)g * owner_stride;
-	}
-	// (ladder: the prefilter is the highest threshold a workgroup ended the sweep with -- k candidates at or above it were counted)
-	if ((rc = launch_select(P, P.lg * P.S, stages, p.cand, p.seg_cnt, p.X, ldx, p.Et, Q, I, KP, k, out_val, out_idx, ws, P.ladder ? p.tau_final : p.tau,
-							P.ladder ? 1 : p.tau_stride, st, item_ids)) != ANNCUR_OK) return rc;
-	EV(4);
-	return ANNCUR_OK;
+		return launch(score_kernel<KP, 1, 16, false, false, QTV>, Cfg::LDS_BYTES);
+	};
+	return run_pipeline(P, c, stages, 1, p.tau, p.tau_stride, launch_prepass, launch_stage);
 }
 
 // ------------------------------------------------------------------ wide inner dimension (Kp > 512): score_wide.hpp
@@ -2036,24 +2077,16 @@ bool wide_kp(int KP) { return KP > 512 && KP <= WIDE_KP_MAX && (KP % 128) == 0; 
 
 // Same plan structure in units of 256-item block tiles (P.n_tiles, stage_end, tiles_per_split); candidate segments per query:
 // 4 S = lane half x wave item half x item split.
-FusedPlan plan_wide(int64_t Q, int64_t I, int KP, int k, bool leading = false) {
+FusedPlan plan_wide(int64_t Q, int64_t I, int KP, int k, bool leading) {
 	FusedPlan P{};
-	P.ok = false;
+	P.wide = true;
 	P.leading = leading ? 1 : 0;
-	if (!wide_kp(KP)) return P;
-	if (k < 1 || k > ANNCUR_MAX_TOPK || Q < 1 || I < 1 || I >= (int64_t)0x7fffffff - 512 || k > I) return P;
-	P.QT = 2;
-	P.BQ = WBN;
+	if (!wide_kp(KP) || !plan_shape_ok(Q, I, k, 512)) return P;
+	P.QT = 2; P.BQ = WBN;
 	P.n_rb = (int)ceil_div64(Q, WBN);
 	P.n_tiles = (int)ceil_div64(I, WBM);
 	P.n_full = (int)(I / WBM);
-	const int target = (4 * k > 512) ? 4 * k : 512;  // groups: enough that the k-th largest group maximum is a tight bound
-	const int n16 = (target + 15) / 16;               // 16 groups of 16 items per sampled block tile
-	if ((int64_t)n16 * 8 <= P.n_full) { P.group = 16; P.n_st = n16; }
-	else { P.group = 4; P.n_st = (target + 63) / 64; }
-	if ((int64_t)P.n_st * 2 > P.n_full) return P;     // problem too small for a sampled threshold: dense GEMM + scan
-	P.n_groups = P.n_st * (P.group == 16 ? 16 : 64);
-	if (P.n_groups < k) return P;
+	if (!plan_sample(P, k, 16, 2)) return P;           // 16 groups of 16 items per sampled block tile
 	const int slots = num_cu();                        // one 512-thread workgroup (128 KiB of LDS) per CU
 	int S = slots / P.n_rb;
 	if (S < 1) S = 1;
@@ -2062,105 +2095,60 @@ FusedPlan plan_wide(int64_t Q, int64_t I, int KP, int k, bool leading = false) {
 	if (S > P.n_tiles) S = P.n_tiles;
 	P.tiles_per_split = (P.n_tiles + S - 1) / S;
 	P.S = (P.n_tiles + P.tiles_per_split - 1) / P.tiles_per_split;
-	int S0 = slots / P.n_rb;
-	if (S0 < 1) S0 = 1;
-	if (S0 > P.n_st) S0 = P.n_st;
-	P.st_per_split = (P.n_st + S0 - 1) / S0;
-	P.S0 = (P.n_st + P.st_per_split - 1) / P.st_per_split;
-	const double exp_hits_cap = 1.3 * k * ((double)P.n_tiles / P.n_st);
-	const double exp_hits = (leading ? 0.65 : 1.0) * exp_hits_cap;
-	const double per_seg = exp_hits_cap / (4.0 * P.S);
-	int capg = next_pow2((int)(4.0 * per_seg) + 32);
-	if (capg < 64) capg = 64;
-	if (capg > 16384) capg = 16384;
-	while (capg > 64 && (int64_t)capg * 4 * P.S >= (1 << 21)) capg >>= 1;  // a workgroup's 256 x 4 S segments span < 4 GiB (32-bit store offsets)
-	P.capg = capg;
+	plan_prepass_splits(P, slots);
+	P.lg = 4;
+	const double exp_hits = plan_segments(P, k, leading);
+	while (P.capg > 64 && (int64_t)P.capg * P.nseg >= (1 << 21)) P.capg >>= 1;  // a workgroup's 256 x 4 S segments span < 4 GiB (32-bit store offsets)
 	P.flush_tiles = 1;
-	plan_stages(P, Q, k, exp_hits, (k <= WQ_K2 ? 4 * P.S <= WAVE : true) && P.n_tiles >= 4 * P.S, 1.0 * P.S / P.n_tiles, WBM);
-	P.kmax = k <= 128 ? 128 : (k <= 512 ? 512 : 2048);
-	size_t off = 256;
-	P.off_gmax = off;   off = align256(off + (size_t)Q * P.n_groups * 4);
-	P.off_tval = off;   off = align256(off + (size_t)Q * k * 4);
-	P.off_tidx = off;   off = align256(off + (size_t)Q * k * 4);
-	P.off_segcnt = off; off = align256(off + (size_t)Q * 4 * P.S * 4);
-	P.off_tau = off;    off = align256(off + (size_t)Q * 4);
-	P.off_hard = off;   off = align256(off + (size_t)Q * 4);
-	P.off_cand = off;   off = align256(off + (size_t)Q * 4 * P.S * (size_t)P.capg * 8);
-	P.total = off;
-	P.ok = true;
+	plan_stages(P, Q, k, exp_hits, (k <= WQ_K2 ? P.nseg <= WAVE : true) && P.n_tiles >= 4 * P.S, 1.0 * P.S / P.n_tiles, WBM);
+	plan_workspace(P, Q, k, 0, 0);   // (no ticket counters, no owner map, no ladder)
 	return P;
 }
 
-int launch_wide(const FusedPlan &P, const void *X, int64_t ldx, const void *Et, int64_t Q, int64_t I, int KP, int k, float *out_val,
-				int32_t *out_idx, unsigned char *ws, hipStream_t st, hipEvent_t *ev, CoScan *co = nullptr, const int32_t *item_ids = nullptr) {
+int launch_wide(const FusedPlan &P, const TopkCall &c) {
+	unsigned char *const ws = c.ws; const hipStream_t st = c.st;
 	WideParams p{};
-	p.X = (const uint16_t *)X; p.ldx = ldx; p.Et = (const uint16_t *)Et; p.et_rows = ceil_div64(I, TILE_I) * TILE_I; p.Q = Q; p.I = I; p.Kp = KP;
+	p.X = (const uint16_t *)c.X; p.ldx = c.ldx; p.Et = (const uint16_t *)c.Et; p.et_rows = ceil_div64(c.I, TILE_I) * TILE_I; p.Q = c.Q; p.I = c.I; p.Kp = c.KP;
 	p.n_rb = P.n_rb; p.S = P.S;
 	p.n_st = P.n_st; p.S0 = P.S0; p.st_per_split = P.st_per_split; p.sample_leading = P.leading; p.n_bt_full = P.n_full;
 	p.gmax = (float *)(ws + P.off_gmax); p.n_groups = P.n_groups;
 	p.cand = (uint2 *)(ws + P.off_cand); p.seg_cnt = (uint32_t *)(ws + P.off_segcnt); p.capg = P.capg;
 	p.tau_bias = 0.f;
-	int rc;
-	ANNCUR_HIP_OK(hipMemsetAsync(ws, 0, 256, st));
-	EV(0);
-	// 1. prepass over the sampled block tiles
-	p.n_wg = P.n_rb * P.S0;
-	if (P.group == 16) {
-		if ((rc = anncur_ensure_dyn_lds((const void *)wide_kernel<0, 16>, W_LDS_TOTAL)) != ANNCUR_OK) return rc;
-		hipLaunchKernelGGL((wide_kernel<0, 16>), dim3(p.n_wg), dim3(512), W_LDS_TOTAL, st, p);
-	} else {
-		if ((rc = anncur_ensure_dyn_lds((const void *)wide_kernel<0, 4>, W_LDS_TOTAL)) != ANNCUR_OK) return rc;
-		hipLaunchKernelGGL((wide_kernel<0, 4>), dim3(p.n_wg), dim3(512), W_LDS_TOTAL, st, p);
-	}
-	ANNCUR_LAUNCH_OK();
-	EV(1);
-	// 2. threshold
-	if ((rc = co_fork(co, st)) != ANNCUR_OK) return rc;
-	if ((rc = launch_threshold(P, p.gmax, Q, k, ws, p.tau, p.tau_stride, st)) != ANNCUR_OK) return rc;
-	if ((rc = co_join(co, st)) != ANNCUR_OK) return rc;
-	EV(2);
-	// 3. sweep in stages
-	p.n_wg = P.n_rb * P.S;
-	if ((rc = anncur_ensure_dyn_lds((const void *)wide_kernel<1, 16>, W_LDS_TOTAL)) != ANNCUR_OK) return rc;
-	for (int stg = 0, prev = 0; stg < P.n_stages; prev = P.stage_end[stg], ++stg) {
-		EV(5 + 2 * stg);
+	if (const int rc = anncur_ensure_dyn_lds((const void *)wide_kernel<1, 16>, W_LDS_TOTAL)) return rc;
+	ANNCUR_HIP_OK(hipMemsetAsync(ws, 0, 256, st));   // (the wide prepass does not clear the header)
+	// prepass over the sampled block tiles
+	auto launch_prepass = [&]() -> int {
+		p.n_wg = P.n_rb * P.S0;
+		if (const int rcl = anncur_ensure_dyn_lds(P.group == 16 ? (const void *)wide_kernel<0, 16> : (const void *)wide_kernel<0, 4>, W_LDS_TOTAL)) return rcl;
+		if (P.group == 16) hipLaunchKernelGGL((wide_kernel<0, 16>), dim3(p.n_wg), dim3(512), W_LDS_TOTAL, st, p);
+		else hipLaunchKernelGGL((wide_kernel<0, 4>), dim3(p.n_wg), dim3(512), W_LDS_TOTAL, st, p);
+		return ANNCUR_OK;
+	};
+	auto launch_stage = [&](int stg, int prev) -> int {
+		p.n_wg = P.n_rb * P.S;
 		p.bt_begin = prev; p.bt_end = P.stage_end[stg]; p.bt_per_split = P.stage_tps[stg]; p.carry = stg > 0;
 		hipLaunchKernelGGL((wide_kernel<1, 16>), dim3(p.n_wg), dim3(512), W_LDS_TOTAL, st, p);
-		ANNCUR_LAUNCH_OK();
-		EV(6 + 2 * stg);
-		if (stg + 1 < P.n_stages) {
-			if ((rc = co_fork(co, st)) != ANNCUR_OK) return rc;
-			if ((rc = launch_tau_refine(p.cand, p.seg_cnt, 4 * P.S, P.capg, Q, k, P.kmax, const_cast<float *>(p.tau), p.tau_stride, stg > 0 ? 1 : 0, st)) != ANNCUR_OK)
-				return rc;
-			if ((rc = co_join(co, st)) != ANNCUR_OK) return rc;
-		}
-	}
-	EV(3);
-	// 4. select (stage ranges in 32-item tiles for the repair path)
-	if ((rc = co_fork(co, st)) != ANNCUR_OK) return rc;
-	SweepStages stages{};
-	stages.n = P.n_stages;
-	const int n_tiles32 = (int)ceil_div64(I, TILE_I), u = WBM / TILE_I;
-	for (int g = 0, prev = 0; g < P.n_stages; prev = P.stage_end[g], ++g) {
-		stages.begin[g] = prev * u;
-		stages.end[g] = P.stage_end[g] * u < n_tiles32 ? P.stage_end[g] * u : n_tiles32;
-		stages.tps[g] = P.stage_tps[g] * u;
-	}
-	if ((rc = launch_select(P, 4 * P.S, stages, p.cand, p.seg_cnt, p.X, ldx, p.Et, Q, I, KP, k, out_val, out_idx, ws, p.tau, p.tau_stride, st, item_ids)) != ANNCUR_OK) return rc;
-	EV(4);
+		return ANNCUR_OK;
+	};
+	return run_pipeline(P, c, SweepStages{}, WBM / TILE_I, p.tau, p.tau_stride, launch_prepass, launch_stage);
+}
+
+constexpr int TOPK_FLAGS = ANNCUR_TOPK_LEADING_SAMPLE | ANNCUR_TOPK_MFMA16 | ANNCUR_TOPK_QT1 | ANNCUR_TOPK_MFMA32 | ANNCUR_TOPK_RING | ANNCUR_TOPK_STAGED;
+
+// The one reading of a flags word (`who`: the entry point, for the error text): unknown bits and the retired ring body are refused,
+// ANNCUR_TOPK_MFMA16 yields to ANNCUR_TOPK_QT1
+int plan_opts_of_flags(const char *who, int flags, PlanOpts &opts) {
+	ANNCUR_REQUIRE((flags & ~TOPK_FLAGS) == 0, ANNCUR_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+	ANNCUR_REQUIRE((flags & ANNCUR_TOPK_RING) == 0, ANNCUR_E_UNSUPPORTED, "%s: ANNCUR_TOPK_RING (the tile-ring sweep body) is retired: measured slower than the default body", who);
+	opts = PlanOpts{};
+	opts.leading = (flags & ANNCUR_TOPK_LEADING_SAMPLE) != 0; opts.qt1 = (flags & ANNCUR_TOPK_QT1) != 0; opts.mfma32 = (flags & ANNCUR_TOPK_MFMA32) != 0;
+	opts.mfma16 = (flags & ANNCUR_TOPK_MFMA16) != 0 && !opts.qt1; opts.no_ladder = (flags & ANNCUR_TOPK_STAGED) != 0;
 	return ANNCUR_OK;
 }
-#undef EV
 
-FusedPlan plan_any(int64_t Q, int64_t I, int KP, int k, int flags = 0) {
-	const bool leading = (flags & ANNCUR_TOPK_LEADING_SAMPLE) != 0, mfma16 = (flags & ANNCUR_TOPK_MFMA16) != 0, qt1 = (flags & ANNCUR_TOPK_QT1) != 0;
-	return wide_kp(KP) ? plan_wide(Q, I, KP, k, leading) : plan_fused(Q, I, KP, k, leading, mfma16 && !qt1, qt1, (flags & ANNCUR_TOPK_MFMA32) != 0, false,
-																	  (flags & ANNCUR_TOPK_STAGED) != 0);
+FusedPlan plan_any(int64_t Q, int64_t I, int KP, int k, const PlanOpts &opts = PlanOpts{}) {
+	return wide_kp(KP) ? plan_wide(Q, I, KP, k, opts.leading) : plan_fused(Q, I, KP, k, opts);
 }
-bool ring_flag_ok(int flags) {
-	return (flags & ANNCUR_TOPK_RING) == 0;
-}
-constexpr int TOPK_FLAGS = ANNCUR_TOPK_LEADING_SAMPLE | ANNCUR_TOPK_MFMA16 | ANNCUR_TOPK_QT1 | ANNCUR_TOPK_MFMA32 | ANNCUR_TOPK_RING | ANNCUR_TOPK_STAGED;
 
 }  // namespace
 
@@ -2168,8 +2156,10 @@ extern "C" size_t anncur_score_topk_workspace_bytes(int64_t Q, int64_t I, int32_
 	const FusedPlan P = plan_any(Q, I, Kp, k);
 	if (!P.ok) return 0;
 	size_t t = P.total;
-	for (int flags : {ANNCUR_TOPK_MFMA16, ANNCUR_TOPK_MFMA32, ANNCUR_TOPK_QT1, ANNCUR_TOPK_RING, ANNCUR_TOPK_STAGED}) {  // (whatever variant flag the call will carry)
-		const FusedPlan V = plan_any(Q, I, Kp, k, flags);
+	PlanOpts variant[4];   // (whatever variant flag the call will carry)
+	variant[0].mfma16 = variant[1].mfma32 = variant[2].qt1 = variant[3].no_ladder = true;
+	for (const PlanOpts &o : variant) {
+		const FusedPlan V = plan_any(Q, I, Kp, k, o);
 		if (V.ok && V.total > t) t = V.total;
 	}
 	return t;
@@ -2184,9 +2174,10 @@ extern "C" int anncur_score_topk_supported(int64_t Q, int64_t I, int32_t Kp, int
 static int score_topk_impl(const void *X, int64_t ldx, const void *Et, int64_t lde, int64_t Q, int64_t I, int32_t Kp,
 						   int32_t k, float *out_val, int32_t *out_idx, void *workspace, size_t workspace_bytes,
 						   void *stream, hipEvent_t *ev, int32_t flags = 0, const int32_t *item_ids = nullptr, CoScan *co = nullptr, const EvalArgs *ea = nullptr) {
-	ANNCUR_REQUIRE((flags & ~TOPK_FLAGS) == 0, ANNCUR_E_INVALID, "score_topk: unknown flags 0x%x", flags);
-	ANNCUR_REQUIRE(ring_flag_ok(flags), ANNCUR_E_UNSUPPORTED, "score_topk: ANNCUR_TOPK_RING (the tile-ring sweep body) is retired: measured slower than the default body");
-	const FusedPlan P = ea ? plan_fused(Q, I, Kp, k, false, false, false, false, true) : plan_any(Q, I, Kp, k, flags);
+	PlanOpts opts;
+	int rc;
+	if ((rc = plan_opts_of_flags("score_topk", flags, opts)) != ANNCUR_OK) return rc;
+	const FusedPlan P = ea ? plan_fused(Q, I, Kp, k, evalf_opts()) : plan_any(Q, I, Kp, k, opts);
 	ANNCUR_REQUIRE(P.ok, ANNCUR_E_UNSUPPORTED,
 				   "score_topk: (Q=%lld, I=%lld, Kp=%d, k=%d) is outside the fused path (Kp in {64,128,256,512} or a multiple of 128 up to %d, "
 				   "1<=k<=%d, I large enough for a sampled threshold); use anncur_gemm + anncur_rowwise_topk",
@@ -2198,17 +2189,14 @@ static int score_topk_impl(const void *X, int64_t ldx, const void *Et, int64_t l
 	ANNCUR_REQUIRE(workspace && workspace_bytes >= P.total && ((uintptr_t)workspace % 256) == 0, ANNCUR_E_WORKSPACE,
 				   "score_topk: workspace of %zu bytes (256-byte aligned) required, got %zu", P.total, workspace_bytes);
 	hipStream_t st = (hipStream_t)stream;
-	unsigned char *ws = (unsigned char *)workspace;
-	int rc;
+	const TopkCall c{X, ldx, Et, Q, I, Kp, k, out_val, out_idx, (unsigned char *)workspace, st, ev, co, item_ids, ea};
 	if (co && (rc = co_plan(*co, P.n_stages + 1)) != ANNCUR_OK) return rc;   // one chunk per latency-bound launch: threshold, refinements, select
-	switch (Kp) {
-		case 64: rc = launch_fused<64>(P, X, ldx, Et, Q, I, k, out_val, out_idx, ws, st, ev, co, item_ids, ea); break;
-		case 128: rc = P.QT == 1 ? launch_fused<128, 1>(P, X, ldx, Et, Q, I, k, out_val, out_idx, ws, st, ev, co, item_ids)
-								  : launch_fused<128>(P, X, ldx, Et, Q, I, k, out_val, out_idx, ws, st, ev, co, item_ids, ea); break;
-		case 256: rc = P.QT == 1 ? launch_fused<256, 1>(P, X, ldx, Et, Q, I, k, out_val, out_idx, ws, st, ev, co, item_ids)
-								  : launch_fused<256>(P, X, ldx, Et, Q, I, k, out_val, out_idx, ws, st, ev, co, item_ids, ea); break;
-		case 512: rc = launch_fused<512>(P, X, ldx, Et, Q, I, k, out_val, out_idx, ws, st, ev, co, item_ids); break;
-		default: rc = launch_wide(P, X, ldx, Et, Q, I, Kp, k, out_val, out_idx, ws, st, ev, co, item_ids); break;
+	if (P.wide) rc = launch_wide(P, c);
+	else switch (Kp) {
+		case 64: rc = launch_fused<64>(P, c); break;
+		case 128: rc = P.QT == 1 ? launch_fused<128, 1>(P, c) : launch_fused<128>(P, c); break;
+		case 256: rc = P.QT == 1 ? launch_fused<256, 1>(P, c) : launch_fused<256>(P, c); break;
+		default: rc = launch_fused<512>(P, c); break;
 	}
 	if (rc == ANNCUR_OK) rc = co_finish(co, st);
 	if (rc != ANNCUR_OK) co_abort(co, st);   // (never return with forked chunks unjoined)
@@ -2251,13 +2239,10 @@ extern "C" int anncur_eval_topk(const void *A, int a_dtype, int64_t lda, int32_t
  * norm_sq[q] = sum_i A^2 (score_evalf.hpp).  Operands as anncur_score_topk (Et in ITEM order) + the exact matrix as
  * anncur_approx_error_packed's lds route takes it (bf16, 16-byte aligned rows). */
 extern "C" size_t anncur_eval_fused_workspace_bytes(int64_t Q, int64_t I, int32_t Kp, int32_t k) {
-	const FusedPlan P = plan_fused(Q, I, Kp, k, false, false, false, false, true);
+	const FusedPlan P = plan_fused(Q, I, Kp, k, evalf_opts());
 	return P.ok ? P.total : 0;
 }
 
-extern "C" int anncur_eval_fused_ex(const void *X, int64_t ldx, const void *Et, int64_t lde, const void *Et_hint, const void *A, int a_dtype, int64_t lda,
-									int64_t Q, int64_t I, int32_t Kp, int32_t k, float *out_val, int32_t *out_idx, float *err_sq, float *norm_sq,
-									void *workspace, size_t workspace_bytes, void *stream);
 extern "C" int anncur_eval_fused(const void *X, int64_t ldx, const void *Et, int64_t lde, const void *A, int a_dtype, int64_t lda,
 								 int64_t Q, int64_t I, int32_t Kp, int32_t k, float *out_val, int32_t *out_idx, float *err_sq, float *norm_sq,
 								 void *workspace, size_t workspace_bytes, void *stream) {
@@ -2293,11 +2278,14 @@ extern "C" int anncur_score_topk_timed(const void *X, int64_t ldx, const void *E
 									   int32_t k, float *out_val, int32_t *out_idx, void *workspace, size_t workspace_bytes,
 									   int32_t flags, const int32_t *item_ids, void *stream, float *stage_ms) {
 	ANNCUR_REQUIRE(stage_ms, ANNCUR_E_INVALID, "score_topk_timed: stage_ms is null");
-	constexpr int NEV = 11;  // 0..4 stage boundaries, 5..10 begin/end of up to three sweep launches
+	PlanOpts opts;
+	int rc;
+	if ((rc = plan_opts_of_flags("score_topk_timed", flags, opts)) != ANNCUR_OK) return rc;
+	constexpr int NEV = 11;  // 0..4 stage boundaries, 5..10 begin/end of up to three sweep launches (run_pipeline)
 	hipEvent_t ev[NEV];
 	for (int i = 0; i < NEV; ++i) ANNCUR_HIP_OK(hipEventCreate(&ev[i]));
-	const FusedPlan P = plan_any(Q, I, Kp, k, flags);
-	int rc = score_topk_impl(X, ldx, Et, lde, Q, I, Kp, k, out_val, out_idx, workspace, workspace_bytes, stream, ev, flags, item_ids);
+	const FusedPlan P = plan_any(Q, I, Kp, k, opts);
+	rc = score_topk_impl(X, ldx, Et, lde, Q, I, Kp, k, out_val, out_idx, workspace, workspace_bytes, stream, ev, flags, item_ids);
 	if (rc == ANNCUR_OK) {
 		hipError_t e = hipEventSynchronize(ev[4]);
 		if (e != hipSuccess) { anncur_set_error("hipEventSynchronize: %s", hipGetErrorString(e)); rc = ANNCUR_E_HIP; }
@@ -2326,36 +2314,41 @@ extern "C" int anncur_score_topk_plan(int64_t Q, int64_t I, int32_t Kp, int32_t 
 	return ANNCUR_OK;
 }
 
-/* the same for the flags of anncur_score_topk_ex: out[0 .. n_out) = {sample tiles, item tiles, S, segment capacity, group, segments per
- * query and item split (2: 32x32x16 sweep, 1: 16x16x32 sweep, 4: wide kernel), 32-query sub-tiles per wave, sweep stages,
- * stage_end[3], stage body[3] (0: 32x32x16 with the ballot filter, 1: with the exec-mask filter, 2: 16x16x32, 4: Kp = 512 with the
- * wave-level queue on 16x16x32 MFMAs), ring drain period[3],
- * threshold ladder (1: the sweep raises its thresholds in-launch, score16.hpp; 0: staged), rank of the ladder's top level,
- * tiles between two fetches of a wave's ladder counters (LADDER_PERIOD),
- * workspace offset of the prepass' group maxima in 256-byte units, group maxima per query (row pitch of that array), prepass kernel
- * (1: prepass16_kernel, the sweep's 16x16x32 body; 0: score_kernel<KP, 0, ..>), prepass item splits} --
- * what a test needs to see that a variant flag was honoured, and to read the group maxima back
- * (describe_plan fills those 24 words, then the tiles per item split of each stage [3]: anncur_eval_fused_plan returns them too) */
-static void describe_plan(const FusedPlan &P, bool wide, int32_t (&v)[27]) {
-	const int32_t head[8] = {P.n_st, P.n_tiles, P.S, P.capg, P.group, wide ? 4 : P.lg, P.QT, P.n_stages};
-	for (int i = 0; i < 27; ++i) v[i] = i < 8 ? head[i] : 0;
-	v[17] = (!wide && P.ladder) ? 1 : 0; v[18] = (!wide && P.ladder) ? P.ladder_k2 : 0; v[19] = LADDER_PERIOD;
-	v[20] = (int32_t)(P.off_gmax / 256); v[21] = P.n_groups; v[22] = (!wide && P.body16 && P.group == 16) ? 1 : 0; v[23] = P.S0;
-	for (int g = 0; g < 3; ++g) {
-		const bool on = g < P.n_stages;
-		v[8 + g] = on ? P.stage_end[g] : 0; v[11 + g] = on ? (wide ? P.stage_pred[g] : P.bodyef ? 6 : P.body16 ? 2 : P.bodyq16 ? 4 : P.stage_pred[g]) : 0; v[14 + g] = on ? P.stage_flush[g] : 0;
-		v[24 + g] = on ? P.stage_tps[g] : 0;
+/* the same for the flags of anncur_score_topk_ex, in words: what a test needs to see that a variant flag was honoured, and to read the group
+ * maxima back.  The positions are listed in include/anncur_hip.h and named again in ops.py (_plan_words). */
+enum PlanWord {
+	PW_N_ST, PW_N_TILES, PW_S, PW_CAPG, PW_GROUP,   // sample tiles, item tiles, item splits, segment capacity, group
+	PW_LG,                   // segments per query and item split (2: 32x32x16 sweep, 1: 16x16x32 sweep, 4: wide kernel)
+	PW_QT, PW_N_STAGES,      // 32-query sub-tiles per wave, sweep stages
+	PW_STAGE_END = 8,        // [3]
+	PW_STAGE_BODY = 11,      // [3] 0: 32x32x16 with the ballot filter, 1: with the exec-mask filter, 2: 16x16x32, 4: Kp = 512 with the wave-level queue on 16x16x32 MFMAs, 6: evalf_kernel
+	PW_STAGE_FLUSH = 14,     // [3] ring drain period
+	PW_LADDER = 17, PW_LADDER_K2, PW_LADDER_PERIOD,   // threshold ladder (1: the sweep raises its thresholds in-launch, score16.hpp; 0: staged), rank of its top level, LADDER_PERIOD
+	PW_GMAX_OFF256, PW_N_GROUPS,   // workspace offset of the prepass' group maxima in 256-byte units, group maxima per query (row pitch of that array)
+	PW_PREPASS16, PW_S0,     // prepass kernel (1: prepass16_kernel, the sweep's 16x16x32 body; 0: score_kernel<KP, 0, ..>), prepass item splits
+	PW_N_EX = 24,            // anncur_score_topk_plan_ex returns the words up to here
+	PW_STAGE_TPS = 24,       // [3] tiles per item split of each stage: anncur_eval_fused_plan returns them too
+	PW_N = 27
+};
+static void describe_plan(const FusedPlan &P, int32_t *out, int n_out, int n_max) {
+	int32_t v[PW_N] = {};
+	v[PW_N_ST] = P.n_st; v[PW_N_TILES] = P.n_tiles; v[PW_S] = P.S; v[PW_CAPG] = P.capg; v[PW_GROUP] = P.group; v[PW_LG] = P.lg; v[PW_QT] = P.QT;
+	v[PW_N_STAGES] = P.n_stages;
+	v[PW_LADDER] = P.ladder ? 1 : 0; v[PW_LADDER_K2] = P.ladder ? P.ladder_k2 : 0; v[PW_LADDER_PERIOD] = LADDER_PERIOD;
+	v[PW_GMAX_OFF256] = (int32_t)(P.off_gmax / 256); v[PW_N_GROUPS] = P.n_groups; v[PW_PREPASS16] = (P.body16 && P.group == 16) ? 1 : 0; v[PW_S0] = P.S0;
+	for (int g = 0; g < P.n_stages; ++g) {
+		v[PW_STAGE_END + g] = P.stage_end[g]; v[PW_STAGE_FLUSH + g] = P.stage_flush[g]; v[PW_STAGE_TPS + g] = P.stage_tps[g];
+		v[PW_STAGE_BODY + g] = P.bodyef ? 6 : P.body16 ? 2 : P.bodyq16 ? 4 : P.stage_pred[g];
 	}
+	for (int i = 0; i < n_out && i < n_max; ++i) out[i] = v[i];
 }
 
 extern "C" int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, int32_t *out, int32_t n_out) {
-	ANNCUR_REQUIRE((flags & ~TOPK_FLAGS) == 0, ANNCUR_E_INVALID, "score_topk_plan_ex: unknown flags 0x%x", flags);
-	ANNCUR_REQUIRE(ring_flag_ok(flags), ANNCUR_E_UNSUPPORTED, "score_topk_plan_ex: ANNCUR_TOPK_RING (the tile-ring sweep body) is retired");
-	const FusedPlan P = plan_any(Q, I, Kp, k, flags);
+	PlanOpts opts;
+	if (const int rc = plan_opts_of_flags("score_topk_plan_ex", flags, opts)) return rc;
+	const FusedPlan P = plan_any(Q, I, Kp, k, opts);
 	ANNCUR_REQUIRE(P.ok && out && n_out >= 0, ANNCUR_E_UNSUPPORTED, "score_topk_plan_ex: unsupported shape");
-	int32_t v[27];
-	describe_plan(P, wide_kp(Kp), v);
-	for (int i = 0; i < n_out && i < 24; ++i) out[i] = v[i];
+	describe_plan(P, out, n_out, PW_N_EX);
 	return ANNCUR_OK;
 }
 
@@ -2363,12 +2356,10 @@ extern "C" int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32
  * every stage -- body 6): the 24 words of anncur_score_topk_plan_ex, then the tiles per item split of each stage [3].  Host code only. */
 extern "C" int anncur_eval_fused_plan(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t *out, int32_t n_out) {
 	ANNCUR_REQUIRE(Kp == 64 || Kp == 128 || Kp == 256, ANNCUR_E_UNSUPPORTED, "eval_fused_plan: Kp must be 64, 128 or 256 (got %d)", Kp);
-	const FusedPlan P = plan_fused(Q, I, Kp, k, false, false, false, false, true);
+	const FusedPlan P = plan_fused(Q, I, Kp, k, evalf_opts());
 	ANNCUR_REQUIRE(P.ok && out && n_out >= 0, ANNCUR_E_UNSUPPORTED, "eval_fused_plan: shape (Q=%lld, I=%lld, Kp=%d, k=%d) is outside the fused path",
 				   (long long)Q, (long long)I, Kp, k);
-	int32_t v[27];
-	describe_plan(P, false, v);
-	for (int i = 0; i < n_out && i < 27; ++i) out[i] = v[i];
+	describe_plan(P, out, n_out, PW_N);
 	return ANNCUR_OK;
 }
 
@@ -2376,10 +2367,12 @@ extern "C" int anncur_eval_fused_plan(int64_t Q, int64_t I, int32_t Kp, int32_t 
  * synchronises the stream).  What a threshold plan is judged by: k ln(I / k) is what an online threshold can reach. */
 extern "C" int anncur_score_topk_survivors(const void *workspace, int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, double *mean_per_query,
 										   void *stream) {
-	ANNCUR_REQUIRE((flags & ~TOPK_FLAGS) == 0 && workspace && mean_per_query, ANNCUR_E_INVALID, "score_topk_survivors: bad arguments");
-	const FusedPlan P = plan_any(Q, I, Kp, k, flags);
+	ANNCUR_REQUIRE(workspace && mean_per_query, ANNCUR_E_INVALID, "score_topk_survivors: bad arguments");
+	PlanOpts opts;
+	if (const int rc = plan_opts_of_flags("score_topk_survivors", flags, opts)) return rc;
+	const FusedPlan P = plan_any(Q, I, Kp, k, opts);
 	ANNCUR_REQUIRE(P.ok, ANNCUR_E_UNSUPPORTED, "score_topk_survivors: unsupported shape");
-	const size_t n = (size_t)Q * (wide_kp(Kp) ? 4 : P.lg) * P.S;
+	const size_t n = (size_t)Q * P.nseg;
 	std::vector<uint32_t> h(n);
 	ANNCUR_HIP_OK(hipMemcpyAsync(h.data(), (const unsigned char *)workspace + P.off_segcnt, n * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
 	ANNCUR_HIP_OK(hipStreamSynchronize((hipStream_t)stream));
@@ -2394,11 +2387,12 @@ extern "C" int anncur_score_topk_survivors(const void *workspace, int64_t Q, int
  * (levels[q][j - 1] <-> counts[q][j - 1]: the candidates counted with level j as the highest they reach). */
 extern "C" int anncur_score_topk_ladder_state(const void *workspace, int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, float *levels,
 											  uint32_t *counts, float *tau_final, float *tau0, void *stream) {
-	ANNCUR_REQUIRE((flags & ~TOPK_FLAGS) == 0 && workspace && levels && counts && tau_final, ANNCUR_E_INVALID, "score_topk_ladder_state: bad arguments");
-	ANNCUR_REQUIRE(ring_flag_ok(flags), ANNCUR_E_UNSUPPORTED, "score_topk_ladder_state: ANNCUR_TOPK_RING (the tile-ring sweep body) is retired");
-	const FusedPlan P = plan_any(Q, I, Kp, k, flags);
+	ANNCUR_REQUIRE(workspace && levels && counts && tau_final, ANNCUR_E_INVALID, "score_topk_ladder_state: bad arguments");
+	PlanOpts opts;
+	if (const int rc = plan_opts_of_flags("score_topk_ladder_state", flags, opts)) return rc;
+	const FusedPlan P = plan_any(Q, I, Kp, k, opts);
 	ANNCUR_REQUIRE(P.ok, ANNCUR_E_UNSUPPORTED, "score_topk_ladder_state: unsupported shape");
-	ANNCUR_REQUIRE(!wide_kp(Kp) && P.ladder, ANNCUR_E_UNSUPPORTED, "score_topk_ladder_state: the plan of (Q=%lld, I=%lld, Kp=%d, k=%d, flags 0x%x) has no threshold ladder",
+	ANNCUR_REQUIRE(P.ladder, ANNCUR_E_UNSUPPORTED, "score_topk_ladder_state: the plan of (Q=%lld, I=%lld, Kp=%d, k=%d, flags 0x%x) has no threshold ladder",
 				   (long long)Q, (long long)I, Kp, k, flags);
 	const unsigned char *ws = (const unsigned char *)workspace;
 	hipStream_t st = (hipStream_t)stream;
@@ -2481,8 +2475,3 @@ extern "C" int anncur_approx_error_packed(const void *X, int64_t ldx, const void
 	ANNCUR_LAUNCH_OK();
 	return ANNCUR_OK;
 }
-
-
-
-
-

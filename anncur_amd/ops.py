@@ -875,21 +875,35 @@ def fused_ladder_state(workspace, Q, I, Kp, k, leading_sample=False, mfma16=Fals
 	return {"levels": levels, "counts": counts, "tau_final": tau_final, "tau0": tau0}
 
 
+_PLAN_HEAD = ("n_sample_tiles", "n_tiles", "splits", "segment_capacity", "group", "lg", "QT", "n_stages")   # plan words 0..7
+
+
+def _plan_words(out):
+	"""The words of anncur_score_topk_plan_ex / anncur_eval_fused_plan by name, in the positions include/anncur_hip.h lists (enum PlanWord in
+	csrc/score_fused.hip); words the call was not asked for read 0.  The per-stage arrays [3] are cut to the plan's stages."""
+	v = [int(x) for x in out] + [0] * (27 - len(out))
+	w = dict(zip(_PLAN_HEAD, v[:8]))
+	n = w["n_stages"]
+	w["stage_end"], w["stage_pred"], w["stage_flush"], w["stage_tiles_per_split"] = v[8:8 + n], v[11:11 + n], v[14:14 + n], v[24:24 + n]
+	w["ladder"], w["ladder_top_rank"] = bool(v[17]), v[18]   # the sweep raises its thresholds in-launch (csrc/score16.hpp; staged=True switches it off)
+	w["ladder_period"] = v[19]   # tiles between two fetches of a wave's ladder counters (LADDER_PERIOD)
+	w["gmax_offset"], w["n_groups"] = v[20] * 256, v[21]   # the prepass' group maxima: byte offset in the workspace, row pitch
+	w["prepass16"], w["prepass_splits"] = bool(v[22]), v[23]
+	return w
+
+
 def fused_plan(Q, I, Kp, k, leading_sample=False, mfma16=False, qt1=False, mfma32=False, ring=False, staged=False):
 	"""The plan a fused call with these flags runs.  "lg": candidate segments per (query, item split) -- 2 = the 32x32x16 body (per-lane
 	rings; the default above k = 1024 -- above 384 under staged=True --, and for Kp = 512), 1 = the 16x16x32 body (one queue per wave; the default for Kp <= 256, k <= 1024),
 	4 = the wide kernel (Kp > 512); "QT": 32-query sub-tiles per wave (1 = qt1 honoured, or Kp = 512);
 	"stage_pred": body of each sweep stage -- 0 / 1 = 32x32x16 with the ballot / exec-mask filter, 2 = 16x16x32 (4-wave workgroups, barrier per
-	tile), 4 = Kp = 512 with the wave queue on 16x16x32.  ring=True (the retired tile-ring body) raises."""
+	tile), 4 = Kp = 512 with the wave queue on 16x16x32.  staged=True (ANNCUR_TOPK_STAGED) switches the ladder off; for Kp <= 256 and k in
+	385..1024 it thereby also switches the body from 16x16x32 to 32x32x16 ("lg" 2), not the same body without the ladder.
+	ring=True (the retired tile-ring body) raises."""
 	out = (ctypes.c_int32 * 20)()
 	check(_lib.load().anncur_score_topk_plan_ex(Q, I, Kp, k, _topk_flags(leading_sample, mfma16, qt1, mfma32, ring, staged), out, 20), "score_topk_plan_ex")
-	v = [int(x) for x in out]
-	plan = dict(zip(("n_sample_tiles", "n_tiles", "splits", "segment_capacity", "group", "lg", "QT", "n_stages"), v[:8]))
-	n = plan["n_stages"]
-	plan["stage_end"], plan["stage_pred"], plan["stage_flush"] = v[8:8 + n], v[11:11 + n], v[14:14 + n]
-	plan["ladder"], plan["ladder_top_rank"] = bool(v[17]), v[18]   # the sweep raises its thresholds in-launch (csrc/score16.hpp; staged=True switches it off)
-	plan["ladder_period"] = v[19]   # tiles between two fetches of a wave's ladder counters (LADDER_PERIOD)
-	return plan
+	w = _plan_words(out)
+	return {key: w[key] for key in _PLAN_HEAD + ("stage_end", "stage_pred", "stage_flush", "ladder", "ladder_top_rank", "ladder_period")}
 
 
 def eval_fused_plan(Q, I, Kp, k):
@@ -898,11 +912,8 @@ def eval_fused_plan(Q, I, Kp, k):
 	previous stage's end: static contiguous shares in item order.  The exact matrix' error terms come from the first I // 32 tiles only."""
 	out = (ctypes.c_int32 * 27)()
 	check(_lib.load().anncur_eval_fused_plan(Q, I, Kp, k, out, 27), "eval_fused_plan")
-	v = [int(x) for x in out]
-	plan = dict(zip(("n_sample_tiles", "n_tiles", "splits", "segment_capacity", "group", "lg", "QT", "n_stages"), v[:8]))
-	n = plan["n_stages"]
-	plan["stage_end"], plan["stage_pred"], plan["stage_flush"], plan["stage_tiles_per_split"] = v[8:8 + n], v[11:11 + n], v[14:14 + n], v[24:24 + n]
-	return plan
+	w = _plan_words(out)
+	return {key: w[key] for key in _PLAN_HEAD + ("stage_end", "stage_pred", "stage_flush", "stage_tiles_per_split")}
 
 
 def fused_group_maxima(workspace, Q, I, Kp, k, leading_sample=False, mfma16=False, qt1=False, mfma32=False, ring=False, staged=False):
@@ -911,9 +922,10 @@ def fused_group_maxima(workspace, Q, I, Kp, k, leading_sample=False, mfma16=Fals
 	(r >> 2) & 1 == g, and {"prepass16": the prepass ran on the sweep's 16x16x32 body, "prepass_splits", "n_groups"}."""
 	out = (ctypes.c_int32 * 24)()
 	check(_lib.load().anncur_score_topk_plan_ex(Q, I, Kp, k, _topk_flags(leading_sample, mfma16, qt1, mfma32, ring, staged), out, 24), "score_topk_plan_ex")
-	off, n_groups = int(out[20]) * 256, int(out[21])
+	w = _plan_words(out)
+	off, n_groups = w["gmax_offset"], w["n_groups"]
 	gmax = workspace[off:off + Q * n_groups * 4].view(torch.float32).view(Q, n_groups)
-	return gmax, {"prepass16": bool(out[22]), "prepass_splits": int(out[23]), "n_groups": n_groups}
+	return gmax, {key: w[key] for key in ("prepass16", "prepass_splits", "n_groups")}
 
 
 def _dense_scores(X, Et):

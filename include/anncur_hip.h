@@ -217,10 +217,11 @@ int anncur_score_topk(const void *X, int64_t ldx, const void *Et, int64_t lde,
  *    which measured 3-4 % slower than the default at every size tried.  The body is gone; a call that sets the flag fails with
  *    ANNCUR_E_UNSUPPORTED. */
 #define ANNCUR_TOPK_RING 16
-/*  ANNCUR_TOPK_STAGED: the default sweep WITHOUT its threshold ladder -- the sweep in stages with a refinement launch between them, as
- *    rounds 1-4 ran it (A/B and parity reference; the default since round 5 is ONE sweep launch whose waves move their thresholds up a
- *    ladder of levels from device-wide counts of the candidates kept so far: csrc/score16.hpp).  For Kp <= 256 and k <= 384 the same
- *    16x16x32 body runs staged; for k in 385..1024 the flag also switches the body, to the staged 32x32x16 one.  Same result. */
+/*  ANNCUR_TOPK_STAGED: no threshold ladder -- the sweep in stages with a refinement launch between them, as rounds 1-4 ran it (A/B and
+ *    parity reference; the default since round 5 is ONE sweep launch whose waves move their thresholds up a ladder of levels from
+ *    device-wide counts of the candidates kept so far: csrc/score16.hpp).  Kp <= 256: for k <= 384 this is the default 16x16x32 body
+ *    without its ladder; for k in 385..1024 the flag ALSO switches the body, to 32x32x16 with per-lane rings (the 16x16x32 body is the
+ *    default there only because of the ladder), so an A/B in that range compares two kernels, not the ladder alone.  Same result. */
 #define ANNCUR_TOPK_STAGED 32
 int anncur_score_topk_ex(const void *X, int64_t ldx, const void *Et, int64_t lde,
                          int64_t Q, int64_t I, int32_t Kp, int32_t k,

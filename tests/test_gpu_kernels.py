@@ -548,6 +548,27 @@ def test_eval_topk_equals_the_two_separate_calls(ops, Q, I, K, k, kr, dt):
 		assert torch.equal(a.values, want_a.values) and torch.equal(a.indices, want_a.indices)
 
 
+@pytest.mark.parametrize("Q,I,K,k,kw", [(300, 40000, 64, 10, {}),                     # the ladder route: one sweep launch
+										(3300, 50007, 256, 100, {"staged": True}),     # two sweep stages with a refinement launch between them
+										(500, 20000, 1024, 50, {})])                   # the wide route
+def test_timed_call_returns_the_untimed_result_and_one_time_per_sweep_launch(ops, Q, I, K, k, kw):
+	"""anncur_score_topk_timed runs the launch sequence of anncur_score_topk_ex with event points around its steps (one driver for every route:
+	run_pipeline in csrc/score_fused.hip): the same result bit for bit, the number of sweep launches of the plan, one positive duration per
+	sweep launch and 0 behind them, no negative boundary time."""
+	X, E, Xp, Etp = _fused_case(ops, Q, I, K, k, seed=Q + I + K + k)
+	plan = ops.fused_plan(Q, I, Xp.shape[1], k, **kw)
+	if kw.get("staged"):
+		assert plan["n_stages"] >= 2 and not plan["ladder"]
+	want = ops.score_topk_fused(Xp, Etp, I, k, **kw)
+	got, ms = ops.score_topk_fused_timed(Xp, Etp, I, k, **kw)
+	torch.cuda.synchronize()
+	assert torch.equal(got.values, want.values) and torch.equal(got.indices, want.indices)
+	assert len(ms) == 9 and ms[5] == plan["n_stages"], (ms, plan)
+	n = plan["n_stages"]
+	assert all(t > 0 for t in ms[6:6 + n]) and all(t == 0 for t in ms[6 + n:9]), (ms, n)
+	assert all(t >= 0 for t in ms[0:5]), ms
+
+
 def test_fused_unsupported_shapes_raise(ops):
 	from anncur_amd._lib import AnncurHipError
 	assert not ops.fused_supported(1000, 5000, 64, 10)          # too few items for a sampled threshold
