@@ -20,6 +20,8 @@ TOPK_MFMA32 = 8
 TOPK_RING = 16
 TOPK_STAGED = 32
 MAX_TOPK = 2048
+LSTSQ_MAX_KQ = 4096   # ANNCUR_LSTSQ_MAX_KQ
+LSTSQ_MAX_G = 512     # ANNCUR_LSTSQ_MAX_G
 
 _p32 = POINTER(c_int32)
 
@@ -74,6 +76,12 @@ SIGNATURES = {
 	"anncur_rerank": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
 	"anncur_rerank_scored": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
 	"anncur_gather_pairs": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p]),
+	"anncur_lstsq_rows_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+	"anncur_lstsq_rows": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, ctypes.c_double, c_void_p, c_int64,
+								  c_void_p, c_void_p, c_size_t, c_void_p]),
+	"anncur_lstsq_rows_timed": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, ctypes.c_double, c_void_p, c_int64,
+										c_void_p, c_void_p, c_size_t, c_void_p, POINTER(ctypes.c_float)]),
+	"anncur_sort_id_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 	"anncur_overlap_counts": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, _p32, _p32, c_int32, c_void_p, c_void_p]),
 	"anncur_copy_bytes": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
 	"anncur_ivf_build_lists": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

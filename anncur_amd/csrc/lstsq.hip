@@ -1,0 +1,387 @@
+// Batched per-query least squares on the fp64 matrix cores: the weights of the adaptive multi-round search.
+//
+//   w_q = argmin_w || w R_S - c ||^2 + lambda ||w||^2,   R_S = the columns Rt[ids[q, j], :]^T of query q's scored items, kq x n_q
+//
+// by normal equations on the smaller side, in fp64, by Cholesky (include/anncur_hip.h has the contract and the pivot rule).  Three kernels:
+//   lstsq_gram_kernel    G_q = R_S^T R_S (item side, n x n) or R_S R_S^T (query side, kq x kq): 64 x 64 tiles of the lower triangle, the rows
+//                        of Rt gathered by ids[q, .], widened to fp64 and accumulated on v_mfma_f64_16x16x4_f64 (fragment maps: gemm64.hip);
+//   lstsq_matvec_kernel  out[a] = sum_j Rt[ids[q, j], a] v[j]: the right-hand side R_S c^T of the query side (before the factorisation) and
+//                        the result w = R_S y of the item side (after it; rounded to fp32 once, at the store);
+//   lstsq_factor_kernel  one workgroup per query: left-looking Cholesky by 16-column panels in place in the workspace, then the back
+//                        substitution.  The right-hand side is carried as ONE EXTRA ROW of the matrix (row gp): the panel update and the
+//                        triangular solve that every row below the diagonal block gets are, for that row, exactly the forward substitution.
+// Workspace of one query: (gp + 1) x gp doubles, gp = ceil16(g): rows 0..gp-1 hold G, then L (lower triangle), row gp the right-hand
+// side, then z = L^-1 rhs, then (item side) y.  Every cell that is read is written here first: the caller pre-fills nothing.
+#include "common.hpp"
+
+namespace {
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int GT = 64, GK = 32;   // Gram tile: 64 x 64 outputs, 32-deep steps of the summed index
+constexpr int GPITCH = 80;        // doubles per LDS row (gemm64.hip: the four k-rows of a fragment read do not collide)
+constexpr int PB = 16;            // panel width of the factorisation = the MFMA tile
+constexpr int PPITCH = 17;        // doubles per row of the LDS panel: a thread per row walks its 16 entries without bank conflicts
+constexpr int MAXBLK = 9;         // row blocks per wave and panel: ceil((512 / 16 + 1) / 4)
+
+__device__ __forceinline__ float nan_f32() { return __uint_as_float(0x7fc00000u); }
+
+// SIDE 0 (item side): index space of G = positions j of the id list, summed index = the kq anchor queries.
+// SIDE 1 (query side): index space of G = the kq anchor queries, summed index = positions j of the id list.
+// A hole (id < 0 or >= m_items), a row at or beyond g and a summed index beyond its range all read as zero: the pitch pad of Rt and rows
+// that no id names never enter a sum.
+template <int SIDE>
+__global__ __launch_bounds__(256) void lstsq_gram_kernel(const float *__restrict__ Rt, int64_t ldr, int64_t m_items, const int32_t *__restrict__ ids,
+															  int64_t ld_ids, int n, int kq, int gp, int ntp, double *__restrict__ ws, int64_t ws_stride) {
+	__shared__ double As[GK][GPITCH], Bs[GK][GPITCH];
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+	const int64_t q = blockIdx.x / ntp;
+	int t = (int)(blockIdx.x % ntp), ti = 0;
+	while (t > ti) { t -= ti + 1; ++ti; }   // tile pair (ti >= tj) of the lower triangle
+	const int tj = t;
+	const int32_t *qi = ids + q * ld_ids;
+	const int Kd = SIDE == 0 ? kq : n;
+	auto fetch = [&](int row, int k) -> double {
+		if (SIDE == 0) {
+			if (row >= n || k >= kq) return 0.0;
+			const int64_t id = qi[row];
+			return (id >= 0 && id < m_items) ? (double)Rt[id * ldr + k] : 0.0;
+		}
+		if (row >= kq || k >= n) return 0.0;
+		const int64_t id = qi[k];
+		return (id >= 0 && id < m_items) ? (double)Rt[id * ldr + row] : 0.0;
+	};
+	f64x4 acc[2][2];
+#pragma unroll
+	for (int i = 0; i < 2; ++i)
+#pragma unroll
+		for (int j = 0; j < 2; ++j) acc[i][j] = (f64x4){0.0, 0.0, 0.0, 0.0};
+	constexpr int PER = GT * GK / 256;
+	double ra[PER], rb[PER];
+	// consecutive threads run along the index that is contiguous in Rt: k on the item side (one item's kq values), the row on the query side
+	auto load = [&](int k0) {
+#pragma unroll
+		for (int i = 0; i < PER; ++i) {
+			const int e = tid + 256 * i;
+			const int r = SIDE == 0 ? e / GK : e % GT, k = SIDE == 0 ? e % GK : e / GT;
+			ra[i] = fetch(ti * GT + r, k0 + k);
+			rb[i] = fetch(tj * GT + r, k0 + k);
+		}
+	};
+	auto stash = [&]() {
+#pragma unroll
+		for (int i = 0; i < PER; ++i) {
+			const int e = tid + 256 * i;
+			const int r = SIDE == 0 ? e / GK : e % GT, k = SIDE == 0 ? e % GK : e / GT;
+			As[k][r] = ra[i];
+			Bs[k][r] = rb[i];
+		}
+	};
+	load(0);
+	for (int k0 = 0; k0 < Kd; k0 += GK) {
+		stash();
+		__syncthreads();
+		if (k0 + GK < Kd) load(k0 + GK);   // in flight during the MFMAs below
+#pragma unroll
+		for (int ks = 0; ks < GK / 4; ++ks) {
+			double a[2], b[2];
+#pragma unroll
+			for (int i = 0; i < 2; ++i) a[i] = As[ks * 4 + (lane >> 4)][wm * 32 + i * 16 + (lane & 15)];
+#pragma unroll
+			for (int j = 0; j < 2; ++j) b[j] = Bs[ks * 4 + (lane >> 4)][wn * 32 + j * 16 + (lane & 15)];
+#pragma unroll
+			for (int i = 0; i < 2; ++i)
+#pragma unroll
+				for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
+		}
+		__syncthreads();
+	}
+	double *G = ws + q * ws_stride;
+#pragma unroll
+	for (int i = 0; i < 2; ++i)
+#pragma unroll
+		for (int j = 0; j < 2; ++j)
+#pragma unroll
+			for (int r = 0; r < 4; ++r) {
+				const int row = ti * GT + wm * 32 + i * 16 + (lane >> 4) + 4 * r, col = tj * GT + wn * 32 + j * 16 + (lane & 15);
+				if (row < gp && col < gp) G[(int64_t)row * gp + col] = acc[i][j][r];
+			}
+}
+
+// out[a] = sum_j Rt[ids[q, j], a] v[j] over the non-hole entries, in fp64, in a fixed order: a workgroup = 64 values of a (one per lane:
+// a coalesced read of each gathered row), its four waves take every fourth j and their sums are added in wave order.
+// SIDE 0: v = y (row gp of the workspace) -> W[q, a] as fp32, NaN for a query whose factorisation failed.
+// SIDE 1: v = C[q, .] -> row gp of the workspace (the right-hand side b), zero for kq <= a < gp.
+template <int SIDE>
+__global__ __launch_bounds__(256) void lstsq_matvec_kernel(const float *__restrict__ Rt, int64_t ldr, int64_t m_items, const int32_t *__restrict__ ids,
+																int64_t ld_ids, const float *__restrict__ C, int64_t ldc, int n, int kq, int gp, int nchunk,
+																double *ws, int64_t ws_stride, float *__restrict__ W, int64_t ldw,
+																const int32_t *__restrict__ status) {
+	__shared__ double part[4][64];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int64_t q = blockIdx.x / nchunk;
+	const int a = (int)(blockIdx.x % nchunk) * 64 + lane;
+	if (SIDE == 0 && status[q] != 0) {
+		if (wave == 0 && a < kq) W[q * ldw + a] = nan_f32();
+		return;
+	}
+	const int32_t *qi = ids + q * ld_ids;
+	double *row = ws + q * ws_stride + (int64_t)gp * gp;
+	double acc = 0.0;
+#pragma unroll 4
+	for (int j = wave; j < n; j += 4) {
+		const int64_t id = qi[j];
+		if (id < 0 || id >= m_items) continue;   // (wave-uniform)
+		const double v = SIDE == 0 ? row[j] : (double)C[q * ldc + j];
+		if (a < kq) acc += (double)Rt[id * ldr + a] * v;
+	}
+	part[wave][lane] = acc;
+	__syncthreads();
+	if (wave != 0) return;
+	const double s = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+	if (SIDE == 0) {
+		if (a < kq) W[q * ldw + a] = (float)s;   // the one rounding to fp32
+	} else if (a < gp) {
+		row[a] = a < kq ? s : 0.0;
+	}
+}
+
+// One workgroup per query.  G (rows 0..gp-1 of the query's workspace, lower triangle) is overwritten by its Cholesky factor L, panel by
+// panel: for panel p (columns c0 = 16 p ...) every 16-row block b >= p -- and the block that holds the right-hand-side row gp -- becomes
+//   P_b = G[b][p] - sum_{k < p} L[b][k] L[p][k]^T          (MFMA, the earlier panels read back from the workspace: L2)
+// in LDS; the 16 x 16 diagonal block is factored there (16 steps, one barrier each), and a thread per row solves x L_pp^T = P_row.
+// Each entry of L is written once.  Index i is "padding" if it is a hole of the id list (item side) or lies in [g, gp): its row and column
+// of G are zero, its diagonal is set to 1 and its right-hand side to 0, so it decouples.  lambda is added to the other diagonals as the
+// panel is formed; the pivot threshold 2^-40 max_i G_ii is taken from the diagonal as the Gram kernel wrote it, before lambda.
+template <int SIDE>
+__global__ __launch_bounds__(256) void lstsq_factor_kernel(const int32_t *__restrict__ ids, int64_t ld_ids, int64_t m_items, const float *__restrict__ C,
+																int64_t ldc, int n, int kq, int g, int gp, double ridge, double *ws, int64_t ws_stride,
+																float *__restrict__ W, int64_t ldw, int32_t *__restrict__ status) {
+	extern __shared__ __attribute__((aligned(16))) double sm[];
+	double *Pn = sm;                          // [(gp + 1) x PPITCH]: the panel, rows c0 .. gp (local row = row - c0)
+	double *Ld = Pn + (gp + 1) * PPITCH;      // [16 x PPITCH]: the factored diagonal block
+	double *yv = Ld + PB * PPITCH;            // [gp]: the solution of the back substitution
+	double *red = yv + gp;                    // [256]
+	int *padf = (int *)(red + 256);           // [gp]
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int64_t q = blockIdx.x;
+	double *G = ws + q * ws_stride;
+	double *rhs = G + (int64_t)gp * gp;
+	const int nb = gp / PB;
+
+	double dmax = 0.0;
+	for (int i = tid; i < gp; i += 256) {
+		bool pad = i >= g;
+		if (SIDE == 0 && !pad) {
+			const int64_t id = ids[q * ld_ids + i];
+			pad = id < 0 || id >= m_items;
+		}
+		padf[i] = pad ? 1 : 0;
+		if (SIDE == 0) rhs[i] = pad ? 0.0 : (double)C[q * ldc + i];
+		if (!pad) dmax = fmax(dmax, G[(int64_t)i * gp + i]);   // (fmax drops a NaN: the pivot test below catches it)
+	}
+	red[tid] = dmax;
+	__syncthreads();
+	for (int s = 128; s > 0; s >>= 1) {
+		if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
+		__syncthreads();
+	}
+	const double thr = red[0] * 0x1p-40;
+	__syncthreads();
+
+	bool bad = false;
+	for (int p = 0; p < nb && !bad; ++p) {
+		const int c0 = p * PB;
+		f64x4 acc[MAXBLK];
+#pragma unroll
+		for (int i = 0; i < MAXBLK; ++i) acc[i] = (f64x4){0.0, 0.0, 0.0, 0.0};
+		for (int k = 0; k < c0; k += 4) {
+			const int col = k + (lane >> 4);
+			const double bf = G[(int64_t)(c0 + (lane & 15)) * gp + col];
+#pragma unroll
+			for (int i = 0; i < MAXBLK; ++i) {
+				const int b = p + wave + 4 * i;   // (wave-uniform)
+				if (b <= nb) {
+					const int row = b * PB + (lane & 15);
+					const double af = row <= gp ? G[(int64_t)row * gp + col] : 0.0;
+					acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc[i], 0, 0, 0);
+				}
+			}
+		}
+#pragma unroll
+		for (int i = 0; i < MAXBLK; ++i) {
+			const int b = p + wave + 4 * i;
+			if (b <= nb) {
+#pragma unroll
+				for (int r = 0; r < 4; ++r) {
+					const int row = b * PB + (lane >> 4) + 4 * r, col = lane & 15;
+					if (row <= gp) {
+						double v = G[(int64_t)row * gp + c0 + col] - acc[i][r];
+						if (row == c0 + col) v = padf[row] ? 1.0 : v + ridge;
+						Pn[(row - c0) * PPITCH + col] = v;
+					}
+				}
+			}
+		}
+		__syncthreads();
+		{   // the diagonal block: right-looking, thread (i, k) owns entry (i, k) of the lower triangle
+			const int i = tid >> 4, k = tid & 15;
+			for (int j = 0; j < PB; ++j) {
+				const double d = Pn[j * PPITCH + j];
+				if (!padf[c0 + j] && !(d > thr)) { bad = true; break; }   // (the same d in every thread: a uniform exit)
+				const double l = sqrt(d);
+				if (k == j && i >= j) Ld[i * PPITCH + j] = i == j ? l : Pn[i * PPITCH + j] / l;
+				if (k > j && i >= k) Pn[i * PPITCH + k] -= (Pn[i * PPITCH + j] / l) * (Pn[k * PPITCH + j] / l);
+				__syncthreads();
+			}
+		}
+		if (bad) break;
+		{
+			const int i = tid >> 4, k = tid & 15;
+			if (i >= k) G[(int64_t)(c0 + i) * gp + c0 + k] = Ld[i * PPITCH + k];
+		}
+		for (int il = PB + tid; il <= gp - c0; il += 256) {   // rows below the block, the right-hand-side row (il = gp - c0) the last
+			double x[PB];
+#pragma unroll
+			for (int j = 0; j < PB; ++j) {
+				double s = Pn[il * PPITCH + j];
+#pragma unroll
+				for (int u = 0; u < j; ++u) s -= x[u] * Ld[j * PPITCH + u];
+				x[j] = s / Ld[j * PPITCH + j];
+			}
+#pragma unroll
+			for (int j = 0; j < PB; ++j) G[(int64_t)(c0 + il) * gp + c0 + j] = x[j];
+		}
+		__syncthreads();   // L's new panel is visible to the whole workgroup, and Pn / Ld are free again
+	}
+	if (bad) {
+		if (tid == 0) status[q] = 1;
+		if (SIDE == 1)
+			for (int a = tid; a < kq; a += 256) W[q * ldw + a] = nan_f32();
+		return;
+	}
+
+	// back substitution L^T y = z (z = row gp), panel by panel from the last
+	for (int p = nb - 1; p >= 0; --p) {
+		const int c0 = p * PB;
+		{
+			const int j = tid & 15, part = tid >> 4;
+			double s = 0.0;
+			for (int i = c0 + PB + part; i < gp; i += 16) s += G[(int64_t)i * gp + c0 + j] * yv[i];
+			red[part * 16 + j] = s;
+			Ld[part * PPITCH + j] = G[(int64_t)(c0 + part) * gp + c0 + j];   // (only the lower triangle of the block is used)
+		}
+		__syncthreads();
+		if (wave == 0) {   // the 16 x 16 triangle: lane j holds column j of L_pp and its own partial right-hand side
+			const int j = lane & 15;
+			double s = rhs[c0 + j];
+			for (int part = 0; part < 16; ++part) s -= red[part * 16 + j];
+			double colj[PB];
+#pragma unroll
+			for (int u = 0; u < PB; ++u) colj[u] = Ld[u * PPITCH + j];
+#pragma unroll
+			for (int u = PB - 1; u >= 0; --u) {
+				const double yu = __shfl(s / colj[u], u);   // lane u holds L[u][u] in colj[u]
+				if (j < u) s -= colj[u] * yu;
+				if (lane == u) yv[c0 + u] = yu;
+			}
+		}
+		__syncthreads();
+	}
+	if (SIDE == 1) {
+		for (int a = tid; a < kq; a += 256) W[q * ldw + a] = (float)yv[a];   // the one rounding to fp32
+	} else {
+		for (int i = tid; i < gp; i += 256) rhs[i] = yv[i];
+	}
+	if (tid == 0) status[q] = 0;
+}
+
+int lstsq_gp(int n, int kq) { const int g = n < kq ? n : kq; return (g + PB - 1) / PB * PB; }
+size_t lstsq_factor_lds(int gp) { return (size_t)((gp + 1) * PPITCH + PB * PPITCH + gp + 256) * sizeof(double) + (size_t)gp * sizeof(int); }
+
+bool lstsq_shape_ok(int64_t Q, int64_t n, int64_t kq) {
+	return Q >= 0 && n >= 1 && n <= ANNCUR_MAX_TOPK && kq >= 1 && kq <= ANNCUR_LSTSQ_MAX_KQ && (n < kq ? n : kq) <= ANNCUR_LSTSQ_MAX_G;
+}
+
+template <int SIDE>
+int lstsq_launch(const float *Rt, int64_t ldr, int64_t m_items, int kq, const int32_t *ids, int64_t ld_ids, const float *C, int64_t ldc, int64_t Q, int n,
+				 double ridge, float *W, int64_t ldw, int32_t *status, double *ws, hipStream_t st, hipEvent_t *ev) {
+	const int g = n < kq ? n : kq, gp = lstsq_gp(n, kq);
+	const int64_t stride = (int64_t)(gp + 1) * gp;
+	const int nt = (gp + GT - 1) / GT, ntp = nt * (nt + 1) / 2;
+	const size_t lds = lstsq_factor_lds(gp);
+	const int rc = anncur_ensure_dyn_lds((const void *)lstsq_factor_kernel<SIDE>, (int)lds);
+	if (rc != ANNCUR_OK) return rc;
+	if (ev) ANNCUR_HIP_OK(hipEventRecord(ev[0], st));
+	hipLaunchKernelGGL((lstsq_gram_kernel<SIDE>), dim3((unsigned)(Q * ntp)), dim3(256), 0, st, Rt, ldr, m_items, ids, ld_ids, n, kq, gp, ntp, ws, stride);
+	if (SIDE == 1) {
+		const int nchunk = (gp + 63) / 64;
+		hipLaunchKernelGGL((lstsq_matvec_kernel<1>), dim3((unsigned)(Q * nchunk)), dim3(256), 0, st, Rt, ldr, m_items, ids, ld_ids, C, ldc, n, kq, gp, nchunk, ws,
+						   stride, W, ldw, (const int32_t *)status);
+	}
+	if (ev) ANNCUR_HIP_OK(hipEventRecord(ev[1], st));
+	hipLaunchKernelGGL((lstsq_factor_kernel<SIDE>), dim3((unsigned)Q), dim3(256), lds, st, ids, ld_ids, m_items, C, ldc, n, kq, g, gp, ridge, ws, stride, W, ldw,
+					   status);
+	if (ev) ANNCUR_HIP_OK(hipEventRecord(ev[2], st));
+	if (SIDE == 0) {
+		const int nchunk = (kq + 63) / 64;
+		hipLaunchKernelGGL((lstsq_matvec_kernel<0>), dim3((unsigned)(Q * nchunk)), dim3(256), 0, st, Rt, ldr, m_items, ids, ld_ids, C, ldc, n, kq, gp, nchunk, ws,
+						   stride, W, ldw, (const int32_t *)status);
+	}
+	if (ev) ANNCUR_HIP_OK(hipEventRecord(ev[3], st));
+	return ANNCUR_OK;
+}
+
+int lstsq_rows(const float *Rt, int64_t ldr, int64_t m_items, int32_t kq, const int32_t *ids, int64_t ld_ids, const float *C, int64_t ldc, int64_t Q, int32_t n,
+			   double ridge, float *W, int64_t ldw, int32_t *status, void *workspace, size_t workspace_bytes, void *stream, float *ms3) {
+	ANNCUR_REQUIRE(lstsq_shape_ok(Q, n, kq), ANNCUR_E_INVALID,
+				   "lstsq_rows: need Q >= 0, 1 <= n <= %d, 1 <= kq <= %d and min(n, kq) <= %d (got Q = %lld, n = %d, kq = %d)", ANNCUR_MAX_TOPK,
+				   ANNCUR_LSTSQ_MAX_KQ, ANNCUR_LSTSQ_MAX_G, (long long)Q, (int)n, (int)kq);
+	ANNCUR_REQUIRE(ridge >= 0.0, ANNCUR_E_INVALID, "lstsq_rows: need ridge >= 0 (got %g)", ridge);   // (a NaN fails too)
+	ANNCUR_REQUIRE(m_items >= 1 && ldr >= kq && ld_ids >= n && ldc >= n && ldw >= kq, ANNCUR_E_INVALID,
+				   "lstsq_rows: need m >= 1 and row pitches ldr >= kq, ld_ids >= n, ldc >= n, ldw >= kq");
+	if (Q == 0) return ANNCUR_OK;
+	ANNCUR_REQUIRE(Rt && ids && C && W && status, ANNCUR_E_INVALID, "lstsq_rows: null pointer");
+	const size_t need = anncur_lstsq_rows_workspace_bytes(Q, n, kq);
+	ANNCUR_REQUIRE(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 255) == 0, ANNCUR_E_WORKSPACE,
+				   "lstsq_rows: workspace missing, misaligned (256 bytes) or too small (%zu < %zu bytes)", workspace_bytes, need);
+	const int gp = lstsq_gp(n, kq), nt = (gp + GT - 1) / GT;
+	ANNCUR_REQUIRE(Q * (nt * (nt + 1) / 2) < (int64_t)0x7fffffff && Q * ((kq + 63) / 64 + 1) < (int64_t)0x7fffffff, ANNCUR_E_INVALID,
+				   "lstsq_rows: Q = %lld is too many queries for one launch at this size: split them", (long long)Q);
+	hipStream_t st = (hipStream_t)stream;
+	hipEvent_t evs[4], *ev = nullptr;
+	if (ms3) {
+		for (int i = 0; i < 4; ++i) ANNCUR_HIP_OK(hipEventCreate(&evs[i]));
+		ev = evs;
+	}
+	const int rc = n <= kq ? lstsq_launch<0>(Rt, ldr, m_items, kq, ids, ld_ids, C, ldc, Q, n, ridge, W, ldw, status, (double *)workspace, st, ev)
+						   : lstsq_launch<1>(Rt, ldr, m_items, kq, ids, ld_ids, C, ldc, Q, n, ridge, W, ldw, status, (double *)workspace, st, ev);
+	if (rc != ANNCUR_OK) return rc;
+	ANNCUR_LAUNCH_OK();
+	if (ms3) {
+		ANNCUR_HIP_OK(hipEventSynchronize(ev[3]));
+		for (int i = 0; i < 3; ++i) ANNCUR_HIP_OK(hipEventElapsedTime(&ms3[i], ev[i], ev[i + 1]));
+		for (int i = 0; i < 4; ++i) ANNCUR_HIP_OK(hipEventDestroy(evs[i]));
+	}
+	return ANNCUR_OK;
+}
+
+}  // namespace
+
+extern "C" size_t anncur_lstsq_rows_workspace_bytes(int64_t Q, int32_t n, int32_t kq) {
+	if (!lstsq_shape_ok(Q, n, kq)) return 0;
+	const int64_t gp = lstsq_gp(n, kq);
+	return (size_t)Q * (size_t)((gp + 1) * gp) * sizeof(double);
+}
+
+extern "C" int anncur_lstsq_rows(const float *Rt, int64_t ldr, int64_t m, int32_t kq, const int32_t *ids, int64_t ld_ids, const float *C, int64_t ldc, int64_t Q,
+								 int32_t n, double ridge, float *W, int64_t ldw, int32_t *status, void *workspace, size_t workspace_bytes, void *stream) {
+	return lstsq_rows(Rt, ldr, m, kq, ids, ld_ids, C, ldc, Q, n, ridge, W, ldw, status, workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int anncur_lstsq_rows_timed(const float *Rt, int64_t ldr, int64_t m, int32_t kq, const int32_t *ids, int64_t ld_ids, const float *C, int64_t ldc,
+									   int64_t Q, int32_t n, double ridge, float *W, int64_t ldw, int32_t *status, void *workspace, size_t workspace_bytes,
+									   void *stream, float *ms3) {
+	ANNCUR_REQUIRE(ms3, ANNCUR_E_INVALID, "lstsq_rows_timed: ms3 is NULL");
+	return lstsq_rows(Rt, ldr, m, kq, ids, ld_ids, C, ldc, Q, n, ridge, W, ldw, status, workspace, workspace_bytes, stream, ms3);
+}

@@ -88,3 +88,67 @@ extern "C" int anncur_device_info(int *n_cu, int *wave_size, char *arch_name, in
 	}
 	return ANNCUR_OK;
 }
+
+// ---- anncur_sort_id_rows: the scored set S_q of the adaptive search, kept sorted on the device ---------------------------
+// One workgroup per row: a bitonic sort in LDS of 64-bit keys (id key, position in the row) -- distinct, so the order is total and equal
+// ids (a contract violation, and the holes) keep their order.  An id < 0 sorts behind every id, the padding up to the power of two behind
+// those.  The scores are staged in LDS as well, so the call may sort a row in place.
+namespace {
+__global__ __launch_bounds__(256) void sort_id_rows_kernel(const int32_t *in_ids, const float *in_val, int64_t ld_in, int w, int P, int32_t *out_ids, float *out_val,
+															int64_t ld_out, int32_t *__restrict__ counts) {   // (out may alias in: no __restrict__ on the rows)
+	extern __shared__ __attribute__((aligned(16))) unsigned char sort_smem[];
+	uint64_t *key = (uint64_t *)sort_smem;                 // [P]
+	int32_t *ids = (int32_t *)(key + P);                   // [w]
+	float *val = (float *)(ids + w);                       // [w]
+	__shared__ int n_valid;
+	const int tid = threadIdx.x;
+	const int64_t q = blockIdx.x;
+	if (tid == 0) n_valid = 0;
+	__syncthreads();
+	int mine = 0;
+	for (int j = tid; j < P; j += 256) {
+		uint64_t k = ~0ull;
+		if (j < w) {
+			const int32_t id = in_ids[q * ld_in + j];
+			ids[j] = id;
+			val[j] = in_val[q * ld_in + j];
+			k = ((uint64_t)(id < 0 ? 0xffffffffu : (uint32_t)id) << 32) | (uint32_t)j;
+			mine += id >= 0;
+		}
+		key[j] = k;
+	}
+	if (mine) atomicAdd(&n_valid, mine);
+	__syncthreads();
+	for (int len = 2; len <= P; len <<= 1)
+		for (int s = len >> 1; s > 0; s >>= 1) {
+			for (int t = tid; t < P / 2; t += 256) {
+				const int lo = ((t & ~(s - 1)) << 1) | (t & (s - 1)), hi = lo + s;
+				const bool up = (lo & len) == 0;
+				const uint64_t a = key[lo], b = key[hi];
+				if ((a > b) == up) { key[lo] = b; key[hi] = a; }
+			}
+			__syncthreads();
+		}
+	for (int j = tid; j < w; j += 256) {
+		const int src = (int)(uint32_t)key[j];
+		out_ids[q * ld_out + j] = ids[src];
+		out_val[q * ld_out + j] = val[src];
+	}
+	if (tid == 0) counts[q] = n_valid;
+}
+}  // namespace
+
+extern "C" int anncur_sort_id_rows(const int32_t *in_ids, const float *in_val, int64_t ld_in, int64_t Q, int32_t w, int32_t *out_ids, float *out_val,
+								   int64_t ld_out, int32_t *counts, void *stream) {
+	ANNCUR_REQUIRE(Q >= 0 && Q < (int64_t)0x7fffffff && w >= 1 && w <= ANNCUR_MAX_TOPK && ld_in >= w && ld_out >= w, ANNCUR_E_INVALID,
+				   "sort_id_rows: need 0 <= Q < 2^31, 1 <= w <= %d and row pitches >= w (got Q = %lld, w = %d)", ANNCUR_MAX_TOPK, (long long)Q, (int)w);
+	if (Q == 0) return ANNCUR_OK;
+	ANNCUR_REQUIRE(in_ids && in_val && out_ids && out_val && counts, ANNCUR_E_INVALID, "sort_id_rows: null pointer");
+	int P = 2;
+	while (P < w) P <<= 1;
+	const size_t lds = (size_t)P * 8 + (size_t)w * 8;   // at most 32 KiB
+	hipLaunchKernelGGL(sort_id_rows_kernel, dim3((unsigned)Q), dim3(256), lds, (hipStream_t)stream, in_ids, in_val, ld_in, (int)w, P, out_ids, out_val, ld_out,
+					   counts);
+	ANNCUR_LAUNCH_OK();
+	return ANNCUR_OK;
+}

@@ -335,6 +335,53 @@ class _SplitOperands(object):
 		return ops.approx_error_packed(ops.pack_split_bf16(X, 0, self.kp), self._item_order, A, Et.shape[0])
 
 
+def _route_name(op, Q, k, excl=None):
+	"""Which of the three top-k routes `op` (a CURRowIndex or an _ItemOperand) takes for Q queries and k results: "bf16x3" (split
+	operands + fp32 rescore), "bf16" (fused sweep) or "dense" (fp32 / bf16 GEMM + exact scan)."""
+	kc = k + (excl.e_max if excl is not None else 0)
+	if op._split is not None and op._split.takes(Q, op.m, k, excl):
+		return "bf16x3"
+	if op._Etp is not None and kc <= min(op.m, ops._lib.MAX_TOPK) and ops.fused_supported(Q, op.m, op._Etp.shape[1], kc):
+		return "bf16"
+	return "dense"
+
+
+def _route_topk(op, X, k, exclude=None):
+	"""Top-k of X . Et^T over the item operand of `op` (CURRowIndex: E^T; _ItemOperand: any item-major matrix), routed by op.compute_dtype
+	and by what the fused kernels take; exclude as for CURApprox.topk_in_row_device."""
+	Q = X.shape[0]
+	excl, kc = _exclusion_arg(exclude, Q, op.m, k, X.device)
+	if op._split is not None and op._split.takes(Q, op.m, k, excl):
+		return op._split.topk(X, op._Et, k, excl)
+	if op._Etp is not None and ops.fused_supported(Q, op.m, op._Etp.shape[1], kc):
+		return _filtered(ops.score_topk_fused(ops.pack_bf16(X, op._Etp.shape[1]), op._Etp_sorted, op.m, kc, leading_sample=True, item_ids=op._item_ids), excl, k)
+	Et = op._Et if op.compute_dtype != "bf16" or op._Etp is None else op._Etp[:op.m, :X.shape[1]]
+	if op.compute_dtype == "bf16" and X.dtype != torch.bfloat16:
+		X = ops.convert(X, torch.bfloat16)
+	return _filtered(ops.score_topk_dense(X, Et, kc), excl, k)
+
+
+class _ItemOperand(object):
+	"""An item-major fp32 matrix Et [m x K] prepared for _route_topk the way CURRowIndex prepares E^T: "bf16" packs it (item order and
+	descending-norm order with the id map), "bf16x3" builds the split operands, "fp32" keeps it as it is."""
+
+	def __init__(self, Et, compute_dtype):
+		self._Et, self.m, self.compute_dtype = Et, Et.shape[0], compute_dtype
+		kp = ops.padded_k(Et.shape[1])
+		self._Etp = self._Etp_sorted = self._item_ids = None
+		if compute_dtype == "bf16" and kp is not None:
+			self._Etp = ops.pack_bf16(Et, kp, row_multiple=32)
+			self._Etp_sorted, self._item_ids = _norm_sorted_pack(Et, kp)
+		self._split = _SplitOperands.build(Et) if compute_dtype == "bf16x3" else None
+
+	def topk(self, X, k, exclude=None):
+		return _route_topk(self, X, k, exclude)
+
+	def route(self, Q, k, exclude=None):
+		excl, _ = _exclusion_arg(exclude, Q, self.m, k, self._Et.device)
+		return _route_name(self, Q, k, excl)
+
+
 class CURRowIndex(object):
 	"""The "rows"-preference index alone: built from the anchor rows R [kr x m] and the anchor columns' ids, without the
 	(n x kc) matrix of every query's anchor scores.  This is what a rank of a row-sharded evaluation holds: R assembled by one
@@ -359,21 +406,21 @@ class CURRowIndex(object):
 			self._Etp = ops.pack_bf16(self._Et, kp, row_multiple=32)
 			self._Etp_sorted, self._item_ids = _norm_sorted_pack(self._Et, kp)
 		self._split = _SplitOperands.build(self._Et) if compute_dtype == "bf16x3" else None
+		self._adaptive = None   # adaptive_operand(), built at the first adaptive search
 
 	def topk(self, X, k, exclude=None):
 		"""X [q x kc]: the queries' exact scores against the anchor items -> (values f32, indices int32) on the GPU.
 		exclude: items left out of the result, as for CURApprox.topk_in_row_device (e.g. ops.exclusion(self.col_idxs, ...), built once:
 		the anchor items, whose exact scores the caller holds already)."""
-		Q = X.shape[0]
-		excl, kc = _exclusion_arg(exclude, Q, self.m, k, X.device)
-		if self._split is not None and self._split.takes(Q, self.m, k, excl):
-			return self._split.topk(X, self._Et, k, excl)
-		if self._Etp is not None and ops.fused_supported(Q, self.m, self._Etp.shape[1], kc):
-			return _filtered(ops.score_topk_fused(ops.pack_bf16(X, self._Etp.shape[1]), self._Etp_sorted, self.m, kc, leading_sample=True, item_ids=self._item_ids), excl, k)
-		Et = self._Et if self.compute_dtype != "bf16" or self._Etp is None else self._Etp[:self.m, :X.shape[1]]
-		if self.compute_dtype == "bf16" and X.dtype != torch.bfloat16:
-			X = ops.convert(X, torch.bfloat16)
-		return _filtered(ops.score_topk_dense(X, Et, kc), excl, k)
+		return _route_topk(self, X, k, exclude)
+
+	def adaptive_operand(self):
+		"""The operand of the adaptive search's retrieval, built at the first call: the anchor rows themselves as ITEM
+		embeddings -- Rt fp32 [m x kq], row i = item i's scores under the kq anchor queries -- behind the same three routes as E^T."""
+		if self._adaptive is None:
+			R = self.R if self.R.dtype == torch.float32 else ops.convert(self.R, torch.float32)
+			self._adaptive = _ItemOperand(R.t().contiguous(), self.compute_dtype)   # (a copy, no arithmetic)
+		return self._adaptive
 
 	def eval_topk(self, X, exact_rows, k, k_retvr):
 		"""(exact top-k of exact_rows, approximate top-k_retvr of X) -- the two rankings of the reference's per-query loop

@@ -260,12 +260,55 @@ def _sweep_pool_cells(A_test_dev, anc, retrieved_idx, exact, top_k_vals, top_k_r
 	return {cell: flatten_overlap(overlap_stats_from_counts(counts[j], cell[0]), prefix=POOL_PREFIX) for j, cell in enumerate(kept)}
 
 
+ADAPTIVE_PREFIX = "exact_vs_reranked_adaptive_retvr"   # --adaptive_rounds of entry point B
+
+
+def _sweep_adaptive_cells(A_test_dev, A_train_dev, anc, exact, top_k_vals, top_k_retr_vals, n_rounds, compute_dtype, pinv_backend):
+	"""The adaptive-search metrics (ADAPTIVE_PREFIX) of the (top_k, k_retvr) cells of one anchor set: the pool of a cell is the anchor items
+	+ n_rounds rounds of k_retvr / n_rounds NEW items each, scored through MatrixScorer(A_test) -- its own AdaptiveSearcher run per k_retvr,
+	because adaptive results are not prefixes of one another --, and recall is the closed form |exact[:k] & pool| (retrieval.overlap_pool_cells'
+	statement: one ops.overlap_counts call on the pool's id list).  Cells with k_retvr % n_rounds != 0 or outside search.adaptive_limits
+	are left out, with one log line for the anchor set that names the limit."""
+	from .search import AdaptiveSearcher, MatrixScorer, adaptive_limits
+	out, skipped = {}, []
+	if len(anc) == 0:
+		LOGGER.info("adaptive_rounds=%d: no anchor items: every cell left out of %s (the first round needs anchor scores)", n_rounds, ADAPTIVE_PREFIX)
+		return out
+	index = CURRowIndex(A_train_dev, np.asarray(anc), compute_dtype=compute_dtype, pinv_backend=pinv_backend)
+	searcher = AdaptiveSearcher(index, MatrixScorer(A_test_dev))
+	qids = torch.arange(A_test_dev.shape[0], dtype=torch.int64)
+	for kr in top_k_retr_vals:
+		ks = [k for k in top_k_vals if k <= kr and k <= exact.indices.shape[1]]
+		if kr <= 0 or not ks:
+			continue
+		if kr % n_rounds:
+			skipped.append((kr, f"k_retvr % {n_rounds} != 0"))
+			continue
+		try:
+			adaptive_limits(searcher.kc, searcher.kq, index.m, 1, kr // n_rounds, n_rounds)
+		except ValueError as e:
+			skipped.append((kr, str(e)))
+			continue
+		pool = searcher.search(qids, 1, kr // n_rounds, n_rounds, trace=True).trace[-1]["ids"]      # the final S_q: anchors + everything scored
+		counts = ops.overlap_counts(exact.indices, pool, [(k, pool.shape[1]) for k in ks]).cpu().numpy()
+		for j, k in enumerate(ks):
+			out[(k, kr)] = flatten_overlap(overlap_stats_from_counts(counts[j], k), prefix=ADAPTIVE_PREFIX)
+	if skipped:
+		LOGGER.info("adaptive_rounds=%d: %d k_retvr value(s) with %d anchor items left out of %s: %s", n_rounds, len(skipped), len(anc), ADAPTIVE_PREFIX,
+					"; ".join(f"k_retvr={kr}: {why}" for kr, why in skipped))
+	return out
+
+
 def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None, progress=None, key_n_m=None, pinv_backend="auto", rerank_pool="retrieved",
-						literal_rerank=False):
+						literal_rerank=False, adaptive_rounds=1):
 	"""eval_method == "cur" of entry point B for one seed (splits.py:286-303 + 399-429).
 	rerank_pool "retrieved+anchors": every cell also reports, under POOL_PREFIX, the metrics of the pool anchor items + k_retvr NEW items (a
-	second retrieval per anchor count, with the anchor items excluded, at the largest k_retvr with k_retvr + n_anc <= pool_cell_limit)."""
+	second retrieval per anchor count, with the anchor items excluded, at the largest k_retvr with k_retvr + n_anc <= pool_cell_limit).
+	adaptive_rounds N >= 2: every cell with k_retvr divisible by N also reports, under ADAPTIVE_PREFIX, the metrics of the adaptive search's
+	pool at the same budget (_sweep_adaptive_cells); 1 is today's code path."""
 	with_pool = _check_rerank_pool(rerank_pool)
+	if adaptive_rounds < 1:
+		raise ValueError(f"adaptive_rounds = {adaptive_rounds}: need adaptive_rounds >= 1")
 	n_train, n_ent = A_train_dev.shape
 	top_k_vals, retr_vals, anc_vals = grids["top_k_vals"], grids["top_k_retr_vals"], grids["n_ent_anchors_vals"]
 	kr_max = max([kr for kr in retr_vals if kr <= min(n_ent, ops._lib.MAX_TOPK)] or [0])
@@ -302,6 +345,9 @@ def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None
 			for (k, kr), metrics in _sweep_pool_cells(A_test_dev, anc, new_items, exact, top_k_vals, retr_vals, n_ent, literal_rerank).items():
 				res[f"top_k={k}"][f"k_retvr={kr}"][f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}"].update(metrics)
 			del new_items
+		if adaptive_rounds >= 2:
+			for (k, kr), metrics in _sweep_adaptive_cells(A_test_dev, A_train_dev, anc, exact, top_k_vals, retr_vals, adaptive_rounds, compute_dtype, pinv_backend).items():
+				res[f"top_k={k}"][f"k_retvr={kr}"][f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}"].update(metrics)
 		del cur, approx
 	return {a: {b: dict(c) for b, c in d.items()} for a, d in res.items()}
 

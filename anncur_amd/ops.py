@@ -1066,6 +1066,118 @@ def rerank_scored(k, cand=None, cand_scores=None, shared_ids=None, shared_scores
 	return TopK(val, idx)
 
 
+# ------------------------------------------------------------------ adaptive multi-round search
+LSTSQ_WS_LIMIT_BYTES = 2 << 30   # default cap of lstsq_rows' workspace: more queries than fit run in chunks
+
+
+def _lstsq_check(Q, n, kq, ridge):
+	"""The limits of anncur_lstsq_rows, as ValueErrors that name them (nothing needs a GPU here)."""
+	if n < 1 or n > _lib.MAX_TOPK:
+		raise ValueError(f"lstsq_rows: {n} scored items per query, outside 1..ANNCUR_MAX_TOPK = {_lib.MAX_TOPK}")
+	if kq < 1 or kq > _lib.LSTSQ_MAX_KQ:
+		raise ValueError(f"lstsq_rows: kq = {kq} anchor queries, outside 1..ANNCUR_LSTSQ_MAX_KQ = {_lib.LSTSQ_MAX_KQ}")
+	if min(n, kq) > _lib.LSTSQ_MAX_G:
+		raise ValueError(f"lstsq_rows: g = min(n, kq) = min({n}, {kq}) = {min(n, kq)}, above ANNCUR_LSTSQ_MAX_G = {_lib.LSTSQ_MAX_G}")
+	if not ridge >= 0.0:
+		raise ValueError(f"lstsq_rows: ridge = {ridge}, need ridge >= 0")
+
+
+def lstsq_workspace_bytes(Q, n, kq):
+	return _lib.load().anncur_lstsq_rows_workspace_bytes(Q, n, kq)
+
+
+@_on_device
+def lstsq_rows(Rt, ids, C, ridge=0.0, max_bytes=LSTSQ_WS_LIMIT_BYTES, out=None, timings=None):
+	"""Per-query least squares (anncur_lstsq_rows): row q of W = argmin_w ||w R_S - C[q]||^2 + ridge ||w||^2 with R_S the columns
+	Rt[ids[q, j], :]^T, j over the non-holes -- at ridge = 0 and full rank, C[q] . pinv(R_S).  Rt [m x kq] fp32 (rows may be padded),
+	ids int32 [Q x n] (-1 = hole, distinct within a row), C fp32 [Q x n].  -> (W fp32 [Q x kq], status int32 [Q]); status[q] = 1 and a NaN
+	row where a Cholesky pivot fell to 2^-40 max diag(G) or below (the pivot rule of include/anncur_hip.h).
+	The workspace is one grow-only buffer per device; above max_bytes the queries run in chunks (at least one query per chunk).
+	out: (W, status) to fill.  timings: a list that receives one (gram_ms, factor_ms, matvec_ms) tuple per chunk (synchronises)."""
+	_dev(Rt, ids, C)
+	if Rt.dtype != torch.float32 or C.dtype != torch.float32:
+		raise TypeError("lstsq_rows takes float32 Rt and C")
+	if ids.dim() != 2 or C.dim() != 2 or tuple(ids.shape) != tuple(C.shape) or Rt.dim() != 2:
+		raise ValueError("lstsq_rows: Rt [m x kq], ids and C [Q x n] of one shape")
+	if ids.dtype != torch.int32:
+		raise ValueError(f"lstsq_rows: ids must be int32 (got {ids.dtype})")
+	Rt, ids, C = _rowmajor(Rt), _rowmajor(ids), _rowmajor(C)
+	(m, kq), (Q, n) = Rt.shape, ids.shape
+	ridge = float(ridge)
+	_lstsq_check(Q, n, kq, ridge)
+	if out is None:
+		W = torch.empty((Q, kq), dtype=torch.float32, device=Rt.device)
+		status = torch.empty((Q,), dtype=torch.int32, device=Rt.device)
+	else:
+		W, status = out
+		if tuple(W.shape) != (Q, kq) or W.dtype != torch.float32 or (kq > 1 and W.stride(1) != 1) or tuple(status.shape) != (Q,) or status.dtype != torch.int32 \
+				or not status.is_contiguous() or W.device != Rt.device or status.device != Rt.device:
+			raise ValueError("lstsq_rows: out = (W fp32 [Q x kq] with unit column stride, status int32 [Q] contiguous) on Rt's device")
+	if Q == 0:
+		return W, status
+	lib = _lib.load()
+	per_query = lib.anncur_lstsq_rows_workspace_bytes(1, n, kq)
+	g = min(n, kq)
+	nt = -(-g // 64)
+	qc = max(1, min(Q, int(max_bytes) // per_query, (0x7fffffff - 1) // max(nt * (nt + 1) // 2, -(-kq // 64) + 1)))
+	ws = _Workspace.get(lib.anncur_lstsq_rows_workspace_bytes(qc, n, kq), Rt.device)
+	for q0 in range(0, Q, qc):
+		q1 = min(Q, q0 + qc)
+		args = (_p(Rt), _ld(Rt), m, kq, _p(ids[q0:q1]), _ld(ids), _p(C[q0:q1]), _ld(C), q1 - q0, n, ridge, _p(W[q0:q1]), _ld(W) if Q > 1 else kq,
+				_p(status[q0:q1]), _p(ws), ws.numel(), _stream())
+		if timings is None:
+			check(lib.anncur_lstsq_rows(*args), "lstsq_rows")
+		else:
+			ms = (ctypes.c_float * 3)()
+			check(lib.anncur_lstsq_rows_timed(*args, ms), "lstsq_rows_timed")
+			timings.append(tuple(ms))
+	return W, status
+
+
+@_on_device
+def sort_id_rows(ids, scores, out=None):
+	"""Rows of (id int32, score fp32) pairs [Q x w] sorted ascending by id, holes (id < 0) last, scores carried along, equal ids in their
+	input order (anncur_sort_id_rows).  -> (ids, scores, counts int32 [Q] = non-holes per row).  out = (ids, scores) to fill; may be the
+	inputs."""
+	_dev(ids, scores)
+	if ids.dim() != 2 or tuple(ids.shape) != tuple(scores.shape):
+		raise ValueError("sort_id_rows: ids and scores must be 2-D tensors [Q x w] of one shape")
+	if ids.dtype != torch.int32 or scores.dtype != torch.float32:
+		raise ValueError(f"sort_id_rows: ids int32 and scores float32 (got {ids.dtype}, {scores.dtype})")
+	Q, w = ids.shape
+	if w < 1 or w > _lib.MAX_TOPK:
+		raise ValueError(f"sort_id_rows: rows of {w} pairs, outside 1..ANNCUR_MAX_TOPK = {_lib.MAX_TOPK}")
+	ids, scores = _rowmajor(ids), _rowmajor(scores)
+	if _ld(ids) != _ld(scores):
+		ids, scores = ids.contiguous(), scores.contiguous()
+	if out is None:
+		out = (torch.empty((Q, w), dtype=torch.int32, device=ids.device), torch.empty((Q, w), dtype=torch.float32, device=ids.device))
+	o_ids, o_sc = out
+	if tuple(o_ids.shape) != (Q, w) or tuple(o_sc.shape) != (Q, w) or o_ids.dtype != torch.int32 or o_sc.dtype != torch.float32 or _ld(o_ids) != _ld(o_sc) \
+			or (w > 1 and (o_ids.stride(1) != 1 or o_sc.stride(1) != 1)):
+		raise ValueError("sort_id_rows: out = (ids int32, scores float32), both [Q x w] with unit column stride and one row pitch")
+	counts = torch.empty((Q,), dtype=torch.int32, device=ids.device)
+	check(_lib.load().anncur_sort_id_rows(_p(ids), _p(scores), _ld(ids), Q, w, _p(o_ids), _p(o_sc), _ld(o_ids), _p(counts), _stream()), "sort_id_rows")
+	return o_ids, o_sc, counts
+
+
+def exclusion_from_sorted_rows(ids_sorted, counts=None):
+	"""Exclusion(off, ids, e_max) of exclusion() from rows that sort_id_rows sorted and that are FULL (no hole): row q is query q's list,
+	off = arange(Q + 1) w, e_max = w -- built on the device, where exclusion() would copy the rows to the host and numpy.unique each.
+	Rows with a hole are refused (ValueError): the one host look is a single flag, from `counts` (sort_id_rows' third result) or, without
+	it, from the last id of each row (holes sort last).  The ids must be distinct within a row; that is the caller's contract."""
+	_dev(ids_sorted)
+	if ids_sorted.dim() != 2 or ids_sorted.dtype != torch.int32:
+		raise ValueError("exclusion_from_sorted_rows: ids_sorted must be an int32 tensor [Q x w]")
+	Q, w = ids_sorted.shape
+	if Q and w:
+		holes = (counts != w).any() if counts is not None else (ids_sorted[:, -1] < 0).any()
+		if bool(holes.item()):
+			raise ValueError(f"exclusion_from_sorted_rows: a row holds fewer than w = {w} ids (a hole); exclusion() takes padded rows")
+	off = torch.arange(Q + 1, dtype=torch.int64, device=ids_sorted.device) * w
+	return Exclusion(off, ids_sorted.contiguous().view(-1), int(w) if Q else 0)
+
+
 @_on_device
 def gather_pairs(A, idx):
 	"""out[q, j] = A[q, idx[q, j]] as float32 [Q x n]; an id outside [0, I) (a hole) gives NaN (reference: ..._splits.py:91-96 reads

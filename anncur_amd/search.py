@@ -16,6 +16,9 @@ Scorer protocol -- any callable:
                  or int32 [Q x n]  per query, -1 = hole      -> scores [Q x n]  (holes: any value)
 
 MatrixScorer answers from a stored matrix: the evaluation stand-in for a model.
+
+AdaptiveSearcher spends the same budget in several rounds: steps 2 and 3 repeat, and from the second round on the weights of
+the retrieval are re-fitted per query on everything that query has scored so far (ops.lstsq_rows).
 """
 from collections import namedtuple
 
@@ -26,6 +29,7 @@ from . import ops
 from .cur import _is_full_range
 
 SearchResult = namedtuple("SearchResult", ["values", "indices", "n_scored"])
+AdaptiveResult = namedtuple("AdaptiveResult", ["values", "indices", "n_scored", "n_fallback", "trace"])
 
 
 class MatrixScorer(object):
@@ -83,3 +87,113 @@ class CrossEncoderSearcher(object):
 			return SearchResult(res.values, res.indices, self.kc + k_retvr)
 		res = ops.rerank_scored(k, cand, scores)
 		return SearchResult(res.values, res.indices, k_retvr)
+
+
+def adaptive_limits(kc, kq, m, k, k_step, n_rounds):
+	"""The host checks of AdaptiveSearcher.search, on plain integers (kc anchor items, kq anchor queries, m items): a ValueError that
+	names the limit, or None.  The evaluation harness asks the same question per grid cell."""
+	max_topk, max_g = ops._lib.MAX_TOPK, ops._lib.LSTSQ_MAX_G
+	if n_rounds < 1 or k_step < 1:
+		raise ValueError(f"adaptive search: need n_rounds >= 1 and k_step >= 1 (got n_rounds = {n_rounds}, k_step = {k_step})")
+	pool = kc + n_rounds * k_step
+	if pool > min(m, max_topk):
+		raise ValueError(f"adaptive search: kc + n_rounds * k_step = {kc} + {n_rounds} * {k_step} = {pool} scored items per query, above the limit of "
+						 f"min(items, ANNCUR_MAX_TOPK) = min({m}, {max_topk}) = {min(m, max_topk)} of the last round's filtered retrieval")
+	g = min(kc + (n_rounds - 1) * k_step, kq)
+	if n_rounds >= 2 and g > max_g:
+		raise ValueError(f"adaptive search: min(kc + (n_rounds - 1) * k_step, kq) = min({kc + (n_rounds - 1) * k_step}, {kq}) = {g}, above "
+						 f"ANNCUR_LSTSQ_MAX_G = {max_g} of the per-query solve")
+	if n_rounds >= 2 and kq > ops._lib.LSTSQ_MAX_KQ:
+		raise ValueError(f"adaptive search: kq = {kq} anchor queries, above ANNCUR_LSTSQ_MAX_KQ = {ops._lib.LSTSQ_MAX_KQ}")
+	if k < 1 or k > min(pool, max_topk):
+		raise ValueError(f"adaptive search: need 1 <= k <= min(pool size, ANNCUR_MAX_TOPK) = min({pool}, {max_topk}) = {min(pool, max_topk)} (got k = {k})")
+
+
+class AdaptiveSearcher(object):
+	"""The multi-round search of DESIGN 4.4d ("Adaptive Selection of Anchor Items for CUR-based k-NN search with Cross-Encoders"): the
+	budget of kc + n_rounds * k_step scorer cells per query is spent in rounds, and the items scored in round r become additional anchor
+	items of THAT query in round r + 1:
+
+	    s_hat_q = c_q . pinv(R[:, S_q]) . R        R = the index' anchor-query rows [kq x m], S_q = the items scored so far, c_q their scores
+
+	round 0   X = scorer(query_ids, anchors); S_q = the anchor items
+	round 1   index.topk(X, k_step, exclude=anchors) -- CrossEncoderSearcher's call, so n_rounds = 1 IS CrossEncoderSearcher.search
+	round r   W = ops.lstsq_rows(Rt, S_q, c_q, ridge); the k_step best of W . R outside S_q (the index' routes on Rt as item operand,
+	          exclude = the id-sorted S_q); score them; append and ops.sort_id_rows
+	end       ops.rerank_scored(k, every item scored in rounds 1..n, anchors with X)
+	Queries whose solve reports status != 0 (rank-deficient R[:, S_q]) -- and only they -- get w_q from numpy.linalg.pinv in fp64 on the host,
+	the policy of cur._pinv for ill-conditioned blocks; n_fallback is the number of such queries.  The scorer is never asked for a
+	(query, item) pair twice.  One host look per round r >= 2: the solve's status flags."""
+
+	def __init__(self, index, scorer, ridge=0.0):
+		self.index, self.scorer, self.ridge = index, scorer, float(ridge)
+		if not self.ridge >= 0.0:
+			raise ValueError(f"AdaptiveSearcher: ridge = {ridge}, need ridge >= 0")
+		dev = index.R.device
+		anc = np.asarray(index.col_idxs.detach().cpu().numpy() if torch.is_tensor(index.col_idxs) else index.col_idxs, dtype=np.int64).reshape(-1)
+		self.kc, self.kq = int(anc.size), int(index.R.shape[0])
+		self._anchor_ids = ops.as_index(anc, dev, index.m)
+		self._shared = ops.shared_id_list(anc, dev)
+		self._excl = ops.exclusion(anc, 0, index.m, dev)
+
+	def _fallback(self, Rt, ids, scores, W, status):
+		"""w_q = c_q . pinv(R_S) (ridge: the regularised normal equations) in fp64 on the host for the rows with status != 0 -> their row
+		numbers (the round's one host look: an empty tensor almost always)."""
+		bad = torch.nonzero(status).view(-1)
+		if bad.numel() == 0:
+			return bad
+		Rt_h = Rt.detach().cpu().numpy().astype(np.float64)
+		ids_h, sc_h = ids[bad].cpu().numpy(), scores[bad].cpu().numpy().astype(np.float64)
+		rows = np.empty((bad.numel(), Rt_h.shape[1]), dtype=np.float32)
+		for r in range(bad.numel()):
+			keep = ids_h[r] >= 0
+			Rs = Rt_h[ids_h[r][keep]].T                                   # kq x n_q
+			if self.ridge > 0.0:
+				w = np.linalg.solve(Rs @ Rs.T + self.ridge * np.eye(Rs.shape[0]), Rs @ sc_h[r][keep])
+			else:
+				w = sc_h[r][keep] @ np.linalg.pinv(Rs)
+			rows[r] = w.astype(np.float32)
+		W[bad] = torch.from_numpy(rows).to(W.device)
+		return bad
+
+	def search(self, query_ids, k, k_step, n_rounds, trace=False):
+		"""-> AdaptiveResult(values f32 [Q x k], indices int32 [Q x k], n_scored = kc + n_rounds * k_step, n_fallback, trace): the k best by
+		exact score among the anchors and everything the rounds scored, descending, ties by the smaller id.  ValueError (adaptive_limits,
+		before the first scorer call) names the limit.  trace=True: a list with one dict per round r >= 2 -- "ids", "scores" (the id-sorted
+		S_q and its scores the round solved on), "W" (after the host fallback), "status", "candidates" (the TopK retrieved), "route" --
+		all tensors on the device."""
+		adaptive_limits(self.kc, self.kq, self.index.m, k, k_step, n_rounds)
+		X = self.scorer(query_ids, self._anchor_ids)
+		cand = self.index.topk(X, k_step, exclude=self._excl)
+		scores = self.scorer(query_ids, cand.indices)
+		if scores.dtype != torch.float32:
+			scores = ops.convert(scores, torch.float32)
+		n_scored, log = self.kc + n_rounds * k_step, ([] if trace else None)
+		if n_rounds == 1:
+			res = ops.rerank_scored(k, cand, scores, self._shared, X)
+			return AdaptiveResult(res.values, res.indices, n_scored, 0, log)
+		Q = X.shape[0]
+		fell_back = set()                                                   # queries solved on the host in any round
+		operand = self.index.adaptive_operand()
+		Rt = operand._Et
+		Xf = X if X.dtype == torch.float32 else ops.convert(X, torch.float32)
+		new_ids, new_scores = cand.indices, scores                        # every item scored in rounds 1.., in retrieval order
+		S_ids = torch.cat([self._anchor_ids.view(1, -1).expand(Q, -1), new_ids], dim=1)
+		S_ids, S_sc, counts = ops.sort_id_rows(S_ids, torch.cat([Xf, scores], dim=1))
+		for r in range(2, n_rounds + 1):
+			W, status = ops.lstsq_rows(Rt, S_ids, S_sc, self.ridge)
+			fell_back.update(self._fallback(Rt, S_ids, S_sc, W, status).tolist())
+			excl = ops.exclusion_from_sorted_rows(S_ids, counts)
+			cand = operand.topk(W, k_step, excl)
+			scores = self.scorer(query_ids, cand.indices)
+			if scores.dtype != torch.float32:
+				scores = ops.convert(scores, torch.float32)
+			if trace:
+				log.append({"ids": S_ids, "scores": S_sc, "W": W, "status": status, "candidates": cand, "route": operand.route(Q, k_step, excl)})
+			new_ids, new_scores = torch.cat([new_ids, cand.indices], dim=1), torch.cat([new_scores, scores], dim=1)
+			if r < n_rounds or trace:
+				S_ids, S_sc, counts = ops.sort_id_rows(torch.cat([S_ids, cand.indices], dim=1), torch.cat([S_sc, scores], dim=1))
+		if trace:
+			log.append({"ids": S_ids, "scores": S_sc})                      # the final S_q
+		res = ops.rerank_scored(k, new_ids, new_scores, self._shared, X)
+		return AdaptiveResult(res.values, res.indices, n_scored, len(fell_back), log)

@@ -33,6 +33,13 @@ def _ints(s):
 	return [int(x) for x in s.split(",") if x != ""]
 
 
+def _rounds(s):
+	n = int(s)
+	if n < 1:
+		raise argparse.ArgumentTypeError("--adaptive_rounds needs an integer >= 1")
+	return n
+
+
 def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, device):
 	from anncur_amd import harness, ops
 	LOGGER.info("Loading precomputed ment_to_ent scores")
@@ -50,6 +57,8 @@ def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, de
 			grids[key] = sorted(set(getattr(args, key)))
 	A_test_dev = harness.to_device_matrix(A_test, device, args.dtype)
 	pool_kw = {} if args.rerank_pool == "retrieved" else {"rerank_pool": args.rerank_pool}   # (non-CUR methods ignore the flag)
+	if args.adaptive_rounds >= 2 and curr_method == "cur":
+		pool_kw = dict(pool_kw, adaptive_rounds=args.adaptive_rounds)   # (1 = today's call; the other methods ignore the flag)
 	LOGGER.info(f"Computing approximate test mention-to-entity scores using method={curr_method}")
 	if curr_method == "cur":
 		A_train_dev = harness.to_device_matrix(A_train, device, args.dtype)
@@ -75,7 +84,8 @@ def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, de
 			ment = ops.gather_cols(A_test_dev, anc, out_dtype=torch.float32)
 			res = harness.run_eval_method_embeds(A_test_dev, ment, full[:, :args.n_fixed_anc_ent].contiguous(), n_train, grids)
 		else:
-			res = harness.run_eval_method_fixed_anc_ent_cur(A_test_dev, full, args.n_fixed_anc_ent, grids, key_n_m=n_train, **pool_kw)
+			res = harness.run_eval_method_fixed_anc_ent_cur(A_test_dev, full, args.n_fixed_anc_ent, grids, key_n_m=n_train,
+															**({} if args.rerank_pool == "retrieved" else {"rerank_pool": args.rerank_pool}))
 	else:
 		raise NotImplementedError(f"Method = {curr_method} not supported")
 	params = {"top_k_retr_vals": grids["top_k_retr_vals"], "top_k_vals": grids["top_k_vals"], "n_ent_anchors_vals": grids["n_ent_anchors_vals"]}
@@ -96,6 +106,8 @@ def run(args, device):
 	arg_dict = dict(args.__dict__)
 	if args.rerank_pool == "retrieved":
 		del arg_dict["rerank_pool"]   # the default run writes the output it wrote before the flag existed, byte for byte
+	if args.adaptive_rounds == 1:
+		del arg_dict["adaptive_rounds"]   # (the same rule)
 	eval_res["other_args"] = arg_dict
 	eval_res["other_args"]["retriever_params"] = retvr_params
 	res_file = f"{args.res_dir}/method={eval_method}_{args.misc}.json"
@@ -140,6 +152,10 @@ def build_parser(worlds=None):
 						help="items the exact re-rank of a CUR cell chooses from: retrieved = the k_retvr retrieved items (the reference's cell); retrieved+anchors = "
 							 "additionally report, under exact_vs_reranked_approx_retvr_w_anchors~..., the pool of the anchor items (whose exact scores every query has "
 							 "paid for) plus k_retvr NEW items, a budget of n_anc + k_retvr exact scores per query (cur, fixed_anc_ent_cur; other methods ignore it)")
+	parser.add_argument("--adaptive_rounds", type=_rounds, default=1,
+						help="N >= 2 (eval_method cur): every cell with k_retvr divisible by N additionally reports, under exact_vs_reranked_adaptive_retvr~..., the pool "
+							 "of the adaptive multi-round search -- the anchor items plus N rounds of k_retvr / N new items, each round's weights solved per query from "
+							 "everything scored so far -- at the same budget of n_anc + k_retvr exact scores per query; 1 (default) = today's run and output")
 	parser.add_argument("--compute_dtype", type=str, default="auto", choices=["auto", "fp32", "bf16", "bf16x3"],
 						help="arithmetic of the CUR retrieval: auto = by --dtype (fp32 matrix -> dense fp32 route, bf16 -> fused bf16 kernel); bf16x3 = for --dtype fp32: "
 							 "operands split into bf16 hi + lo parts on the fused kernel, candidates rescored in fp32 (the fp32 route's values, S_hat never written)")

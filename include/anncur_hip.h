@@ -367,6 +367,46 @@ int anncur_rerank_scored(const int32_t *sh_ids, const void *sh_val, int sh_dtype
 int anncur_gather_pairs(const void *A, int dtype, int64_t Q, int64_t I, int64_t lda, const int32_t *idx, int64_t ld_idx, int32_t n,
                         float *out, int64_t ldo, void *stream);
 
+/* adaptive multi-round search: per-query least squares on the fp64 matrix cores --------------------------------------
+ *   w_q = c_q . pinv(R[:, S_q])        replaces numpy.linalg.pinv of eval/matrix_approx_zeshel.py:47,49 called once PER QUERY AND ROUND
+ *                                      (the index' own pseudo-inverse, anncur_amd/pinv.py, is one matrix: ~28 dependent products)
+ * Rt float[m x kq], pitch ldr >= kq, item-major: row i = item i's scores under the kq anchor queries (the pitch pad is never read into a
+ * sum).  ids int32[Q x n] (pitch ld_ids), an id < 0 (or >= m) marks a hole; the ids of a row are distinct (a contract, as for
+ * anncur_rerank).  C float[Q x n] (pitch ldc): C[q, j] = the exact score of query q on item ids[q, j], ignored at holes.  ridge = lambda >= 0.
+ * Row q of W float[Q x kq] (pitch ldw) becomes
+ *     w_q = argmin_w || w R_S - c ||^2 + lambda ||w||^2,      R_S = the columns Rt[ids[q, j], :]^T of the non-hole entries, kq x n_q,
+ * at lambda = 0 the minimum-norm minimiser c . pinv(R_S) wherever R_S has full rank.  Normal equations on the smaller side, in fp64,
+ * by Cholesky; the side is chosen per call:
+ *   item side,  n <= kq:  G = R_S^T R_S + lambda I [n x n], G y = c^T, w = (R_S y)^T; a hole is a zero row and column with its diagonal
+ *                         set to 1 and its right-hand side to 0 (y = 0 there);
+ *   query side, n >  kq:  G = R_S R_S^T + lambda I [kq x kq], b = R_S c^T, G w^T = b; holes contribute nothing.
+ * W is rounded to fp32 once, at the store.
+ * PIVOT RULE (part of the contract): status[q] = 1 and row q of W = NaN if a Cholesky pivot is <= 2^-40 max_i G_ii, the diagonal taken
+ * BEFORE lambda is added (the 1s of holes take no part); otherwise status[q] = 0.  The fp64 factorisation's backward error is of order
+ * g 2^-53 ||G|| <= 2^-44 ||G|| at g = 512, so 2^-40 is 16 times the noise floor; it corresponds to cond_2(R_S) ~ 10^6, past which fp32
+ * score data carries no information.  (A row whose entries are all holes: W = 0 on the item side, status 1 on the query side at lambda = 0.)
+ * Limits: 1 <= n <= ANNCUR_MAX_TOPK, 1 <= kq <= ANNCUR_LSTSQ_MAX_KQ, g = min(n, kq) <= ANNCUR_LSTSQ_MAX_G, Q G-tiles < 2^31 per call
+ * (split the queries); anything else is ANNCUR_E_INVALID and nothing is written.  Workspace: caller-owned, 256-byte aligned,
+ * anncur_lstsq_rows_workspace_bytes(Q, n, kq) = Q (gp + 1) gp doubles, gp = ceil16(g) (0 for a shape outside the limits); nothing in it is
+ * pre-filled by the caller.  anncur_lstsq_rows_timed: the same call, synchronised, with ms3 = HIP-event times of (Gram [+ right-hand
+ * side on the query side], factor-and-solve, w = R_S y [item side; 0 on the query side]). */
+#define ANNCUR_LSTSQ_MAX_KQ 4096
+#define ANNCUR_LSTSQ_MAX_G  512
+size_t anncur_lstsq_rows_workspace_bytes(int64_t Q, int32_t n, int32_t kq);
+int anncur_lstsq_rows(const float *Rt, int64_t ldr, int64_t m, int32_t kq, const int32_t *ids, int64_t ld_ids, const float *C, int64_t ldc,
+                      int64_t Q, int32_t n, double ridge, float *W, int64_t ldw, int32_t *status, void *workspace, size_t workspace_bytes,
+                      void *stream);
+int anncur_lstsq_rows_timed(const float *Rt, int64_t ldr, int64_t m, int32_t kq, const int32_t *ids, int64_t ld_ids, const float *C, int64_t ldc,
+                            int64_t Q, int32_t n, double ridge, float *W, int64_t ldw, int32_t *status, void *workspace, size_t workspace_bytes,
+                            void *stream, float *ms3);
+/* Rows of (id, score) pairs sorted ascending by id, holes (id < 0) last, scores carried along; equal keys keep their order.
+ *   replaces the per-query numpy.unique of ops.exclusion (one host pass and one synchronisation per call) where a searcher re-sorts its
+ *   scored set every round: the sorted full rows ARE the per-query exclusion lists of anncur_filter_topk (off[q] = q w).
+ * in_ids int32 / in_val float [Q x w] (pitch ld_in), out_ids / out_val [Q x w] (pitch ld_out; may be the inputs), counts int32[Q] = the
+ * non-holes of each row.  1 <= w <= ANNCUR_MAX_TOPK.  One workgroup per row, a bitonic sort in LDS. */
+int anncur_sort_id_rows(const int32_t *in_ids, const float *in_val, int64_t ld_in, int64_t Q, int32_t w, int32_t *out_ids, float *out_val,
+                        int64_t ld_out, int32_t *counts, void *stream);
+
 /* f3: IVF-flat inner-product index (the branch of build_flat_or_ivff_index above 11 000 vectors) -------------------------------
  *   faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT).train / .add / .search     models/nearest_nbr.py:40-52
  * FAISS is not vendored nor pinned by the reference (parity unpinned): restated from the published algorithm, judged on recall
