@@ -81,6 +81,11 @@ SIGNATURES = {
 								  c_void_p, c_void_p, c_size_t, c_void_p]),
 	"anncur_lstsq_rows_timed": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, ctypes.c_double, c_void_p, c_int64,
 										c_void_p, c_void_p, c_size_t, c_void_p, POINTER(ctypes.c_float)]),
+	"anncur_lstsq_state_bytes": (c_size_t, [c_int64, c_int32]),
+	"anncur_lstsq_extend": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, ctypes.c_double, c_void_p,
+									c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+	"anncur_lstsq_extend_timed": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, ctypes.c_double, c_void_p,
+										  c_int64, c_void_p, c_void_p, c_size_t, c_void_p, POINTER(ctypes.c_float)]),
 	"anncur_sort_id_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 	"anncur_overlap_counts": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, _p32, _p32, c_int32, c_void_p, c_void_p]),
 	"anncur_copy_bytes": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),

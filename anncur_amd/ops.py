@@ -1134,6 +1134,97 @@ def lstsq_rows(Rt, ids, C, ridge=0.0, max_bytes=LSTSQ_WS_LIMIT_BYTES, out=None, 
 	return W, status
 
 
+LSTSQ_STATE_LIMIT_BYTES = 32 << 30   # default cap of one LstsqState: a policy, not a measurement (10 000 queries at cap = 456 take 17 GB)
+
+
+def lstsq_state_bytes(Q, cap):
+	"""Bytes of the persistent state of anncur_lstsq_extend for Q queries of up to cap scored items (0 outside its limits)."""
+	return _lib.load().anncur_lstsq_state_bytes(Q, cap)
+
+
+class LstsqState(object):
+	"""lstsq_rows for id lists that only grow at the end (anncur_lstsq_extend, item side): the Gram matrix, its Cholesky factor and the
+	forward-substituted right-hand side of every query stay in one device buffer that this object owns (not the shared grow-only
+	workspace, which other calls overwrite), and extend() pays for the appended positions only.  Rt [m x kq] fp32, Q queries, at most
+	cap <= ANNCUR_LSTSQ_MAX_G positions per query; ridge is fixed for the state's life.  After every extend(ids, C) the result equals
+	lstsq_rows(Rt, ids, C, ridge) bit for bit, status included; a query that failed once (status 1, NaN row) stays failed.
+	.n = the positions absorbed so far, .cap.  Every limit is a ValueError that names it, raised before any launch."""
+
+	def __init__(self, Rt, Q, cap, ridge=0.0, max_bytes=LSTSQ_STATE_LIMIT_BYTES):
+		if not torch.is_tensor(Rt) or Rt.dim() != 2 or Rt.dtype != torch.float32:
+			raise ValueError("LstsqState: Rt must be a float32 tensor [m x kq]")
+		Q, cap, ridge = int(Q), int(cap), float(ridge)
+		kq = Rt.shape[1]
+		if cap < 1 or cap > _lib.LSTSQ_MAX_G:
+			raise ValueError(f"LstsqState: cap = {cap} scored items per query, outside 1..ANNCUR_LSTSQ_MAX_G = {_lib.LSTSQ_MAX_G}")
+		if kq < 1 or kq > _lib.LSTSQ_MAX_KQ:
+			raise ValueError(f"LstsqState: kq = {kq} anchor queries, outside 1..ANNCUR_LSTSQ_MAX_KQ = {_lib.LSTSQ_MAX_KQ}")
+		if Q < 0:
+			raise ValueError(f"LstsqState: Q = {Q} queries")
+		if not ridge >= 0.0:
+			raise ValueError(f"LstsqState: ridge = {ridge}, need ridge >= 0")
+		self.nbytes = _lib.load().anncur_lstsq_state_bytes(Q, cap)
+		if self.nbytes > int(max_bytes):
+			raise ValueError(f"LstsqState: {Q} queries at cap = {cap} need {self.nbytes} bytes of state, above max_bytes = {int(max_bytes)}: "
+							 f"search the queries in batches")
+		self.Rt, self.Q, self.cap, self.kq, self.ridge, self.n = Rt, Q, cap, kq, ridge, 0
+		self._buf = None      # allocated by the first extend
+
+	def _state(self):
+		if self._buf is None:
+			self._buf = torch.empty(self.nbytes + 256, dtype=torch.uint8, device=self.Rt.device)
+		off = (-self._buf.data_ptr()) % 256
+		return self._buf[off:off + self.nbytes]
+
+	def extend(self, ids, C, out=None, timings=None):
+		"""ids int32 / C fp32 [Q x n], n > .n: the FULL rows in insertion order, whose first .n positions are what the last call saw (the
+		caller's contract).  -> (W fp32 [Q x kq], status int32 [Q]) as lstsq_rows returns them for these rows.  out: (W, status) to fill.
+		timings: a list that receives one (gram_ms, factor_ms, matvec_ms) tuple (synchronises)."""
+		if not (torch.is_tensor(ids) and torch.is_tensor(C)) or ids.dim() != 2 or C.dim() != 2 or tuple(ids.shape) != tuple(C.shape) \
+				or ids.shape[0] != self.Q or ids.dtype != torch.int32 or C.dtype != torch.float32:
+			raise ValueError(f"LstsqState.extend: ids int32 and C float32, both [Q x n] of one shape with Q = {self.Q}")
+		n = ids.shape[1]
+		if n <= self.n:
+			raise ValueError(f"LstsqState.extend: rows of {n} positions, but {self.n} are absorbed already: a call appends at least one (the lists never shrink)")
+		if n > self.cap:
+			raise ValueError(f"LstsqState.extend: rows of {n} positions, above this state's cap = {self.cap}")
+		if n > self.kq:
+			raise ValueError(f"LstsqState.extend: rows of {n} positions, above kq = {self.kq} anchor queries: the query side has no incremental form "
+							 f"(lstsq_rows solves it)")
+		if ids.device != self.Rt.device or C.device != self.Rt.device:
+			raise _lib.AnncurHipError(f"LstsqState.extend: operands live on different devices (Rt on {self.Rt.device}, ids on {ids.device}, C on {C.device})")
+		return self._extend(ids, C, n, out, timings)
+
+	@_on_device
+	def _extend(self, ids, C, n, out, timings):
+		_dev(self.Rt, ids, C)
+		Rt, ids, C = _rowmajor(self.Rt), _rowmajor(ids), _rowmajor(C)
+		Q, kq = self.Q, self.kq
+		if out is None:
+			W = torch.empty((Q, kq), dtype=torch.float32, device=Rt.device)
+			status = torch.empty((Q,), dtype=torch.int32, device=Rt.device)
+		else:
+			W, status = out
+			if tuple(W.shape) != (Q, kq) or W.dtype != torch.float32 or (kq > 1 and W.stride(1) != 1) or tuple(status.shape) != (Q,) or status.dtype != torch.int32 \
+					or not status.is_contiguous() or W.device != Rt.device or status.device != Rt.device:
+				raise ValueError("LstsqState.extend: out = (W fp32 [Q x kq] with unit column stride, status int32 [Q] contiguous) on Rt's device")
+		if Q:
+			nt = -(-n // 64)
+			if Q * max(nt * (nt + 1) // 2, -(-kq // 64)) >= 0x7fffffff:
+				raise ValueError(f"LstsqState.extend: Q = {Q} queries are too many for one launch at this size: search the queries in batches")
+			lib, st = _lib.load(), self._state()
+			args = (_p(Rt), _ld(Rt), Rt.shape[0], kq, _p(ids), _ld(ids), _p(C), _ld(C), Q, self.n, n, self.cap, self.ridge, _p(W), _ld(W), _p(status),
+					_p(st), st.numel(), _stream())
+			if timings is None:
+				check(lib.anncur_lstsq_extend(*args), "lstsq_extend")
+			else:
+				ms = (ctypes.c_float * 3)()
+				check(lib.anncur_lstsq_extend_timed(*args, ms), "lstsq_extend_timed")
+				timings.append(tuple(ms))
+		self.n = n
+		return W, status
+
+
 @_on_device
 def sort_id_rows(ids, scores, out=None):
 	"""Rows of (id int32, score fp32) pairs [Q x w] sorted ascending by id, holes (id < 0) last, scores carried along, equal ids in their

@@ -89,9 +89,10 @@ class CrossEncoderSearcher(object):
 		return SearchResult(res.values, res.indices, k_retvr)
 
 
-def adaptive_limits(kc, kq, m, k, k_step, n_rounds):
+def adaptive_limits(kc, kq, m, k, k_step, n_rounds, incremental=False):
 	"""The host checks of AdaptiveSearcher.search, on plain integers (kc anchor items, kq anchor queries, m items): a ValueError that
-	names the limit, or None.  The evaluation harness asks the same question per grid cell."""
+	names the limit, or None.  The evaluation harness asks the same question per grid cell.  incremental: the checks of
+	AdaptiveSearcher(incremental=True) on top -- its solver state has the item side only."""
 	max_topk, max_g = ops._lib.MAX_TOPK, ops._lib.LSTSQ_MAX_G
 	if n_rounds < 1 or k_step < 1:
 		raise ValueError(f"adaptive search: need n_rounds >= 1 and k_step >= 1 (got n_rounds = {n_rounds}, k_step = {k_step})")
@@ -105,6 +106,10 @@ def adaptive_limits(kc, kq, m, k, k_step, n_rounds):
 						 f"ANNCUR_LSTSQ_MAX_G = {max_g} of the per-query solve")
 	if n_rounds >= 2 and kq > ops._lib.LSTSQ_MAX_KQ:
 		raise ValueError(f"adaptive search: kq = {kq} anchor queries, above ANNCUR_LSTSQ_MAX_KQ = {ops._lib.LSTSQ_MAX_KQ}")
+	if incremental and n_rounds >= 2 and kc + (n_rounds - 1) * k_step > kq:
+		raise ValueError(f"adaptive search: incremental=True keeps a per-query factorisation of kc + (n_rounds - 1) * k_step = {kc} + {n_rounds - 1} * {k_step} = "
+						 f"{kc + (n_rounds - 1) * k_step} scored items, above kq = {kq} anchor queries: the query side of the solve has no incremental form "
+						 f"(use incremental=False)")
 	if k < 1 or k > min(pool, max_topk):
 		raise ValueError(f"adaptive search: need 1 <= k <= min(pool size, ANNCUR_MAX_TOPK) = min({pool}, {max_topk}) = {min(pool, max_topk)} (got k = {k})")
 
@@ -123,10 +128,17 @@ class AdaptiveSearcher(object):
 	end       ops.rerank_scored(k, every item scored in rounds 1..n, anchors with X)
 	Queries whose solve reports status != 0 (rank-deficient R[:, S_q]) -- and only they -- get w_q from numpy.linalg.pinv in fp64 on the host,
 	the policy of cur._pinv for ill-conditioned blocks; n_fallback is the number of such queries.  The scorer is never asked for a
-	(query, item) pair twice.  One host look per round r >= 2: the solve's status flags."""
+	(query, item) pair twice.  One host look per round r >= 2: the solve's status flags.
 
-	def __init__(self, index, scorer, ridge=0.0):
-		self.index, self.scorer, self.ridge = index, scorer, float(ridge)
+	incremental=True (opt-in; needs kc + (n_rounds - 1) k_step <= kq): the rounds r >= 2 keep S_q and c_q in INSERTION order -- the anchors
+	in the index' order, then every round's candidates in retrieval order -- and solve on one ops.LstsqState of capacity
+	kc + (n_rounds - 1) k_step, which factors only the positions a round appends (kc + k_step in round 2, k_step afterwards).  W is,
+	bit for bit, ops.lstsq_rows on the same ordered rows; against incremental=False the unknowns are permuted, so the weights agree to
+	rounding only.  The id-sorted copy is kept for the exclusion alone.  A failed query stays failed in the state: it takes the host
+	fallback in every later round and is counted once."""
+
+	def __init__(self, index, scorer, ridge=0.0, incremental=False):
+		self.index, self.scorer, self.ridge, self.incremental = index, scorer, float(ridge), bool(incremental)
 		if not self.ridge >= 0.0:
 			raise ValueError(f"AdaptiveSearcher: ridge = {ridge}, need ridge >= 0")
 		dev = index.R.device
@@ -161,8 +173,9 @@ class AdaptiveSearcher(object):
 		exact score among the anchors and everything the rounds scored, descending, ties by the smaller id.  ValueError (adaptive_limits,
 		before the first scorer call) names the limit.  trace=True: a list with one dict per round r >= 2 -- "ids", "scores" (the id-sorted
 		S_q and its scores the round solved on), "W" (after the host fallback), "status", "candidates" (the TopK retrieved), "route" --
-		all tensors on the device."""
-		adaptive_limits(self.kc, self.kq, self.index.m, k, k_step, n_rounds)
+		all tensors on the device; with incremental=True also "order_ids" and "order_scores", the rows in insertion order that the solve
+		was given ("ids" / "scores" then hold the same pairs sorted, as the exclusion takes them)."""
+		adaptive_limits(self.kc, self.kq, self.index.m, k, k_step, n_rounds, self.incremental)
 		X = self.scorer(query_ids, self._anchor_ids)
 		cand = self.index.topk(X, k_step, exclude=self._excl)
 		scores = self.scorer(query_ids, cand.indices)
@@ -179,9 +192,16 @@ class AdaptiveSearcher(object):
 		Xf = X if X.dtype == torch.float32 else ops.convert(X, torch.float32)
 		new_ids, new_scores = cand.indices, scores                        # every item scored in rounds 1.., in retrieval order
 		S_ids = torch.cat([self._anchor_ids.view(1, -1).expand(Q, -1), new_ids], dim=1)
+		state = O_ids = O_sc = None
+		if self.incremental:
+			O_ids, O_sc = S_ids.contiguous(), torch.cat([Xf, scores], dim=1)   # insertion order: what the state absorbs
+			state = ops.LstsqState(Rt, Q, self.kc + (n_rounds - 1) * k_step, self.ridge)
 		S_ids, S_sc, counts = ops.sort_id_rows(S_ids, torch.cat([Xf, scores], dim=1))
 		for r in range(2, n_rounds + 1):
-			W, status = ops.lstsq_rows(Rt, S_ids, S_sc, self.ridge)
+			if state is None:
+				W, status = ops.lstsq_rows(Rt, S_ids, S_sc, self.ridge)
+			else:
+				W, status = state.extend(O_ids, O_sc)
 			fell_back.update(self._fallback(Rt, S_ids, S_sc, W, status).tolist())
 			excl = ops.exclusion_from_sorted_rows(S_ids, counts)
 			cand = operand.topk(W, k_step, excl)
@@ -190,7 +210,11 @@ class AdaptiveSearcher(object):
 				scores = ops.convert(scores, torch.float32)
 			if trace:
 				log.append({"ids": S_ids, "scores": S_sc, "W": W, "status": status, "candidates": cand, "route": operand.route(Q, k_step, excl)})
+				if state is not None:
+					log[-1].update({"order_ids": O_ids, "order_scores": O_sc})
 			new_ids, new_scores = torch.cat([new_ids, cand.indices], dim=1), torch.cat([new_scores, scores], dim=1)
+			if state is not None and r < n_rounds:
+				O_ids, O_sc = torch.cat([O_ids, cand.indices], dim=1), torch.cat([O_sc, scores], dim=1)
 			if r < n_rounds or trace:
 				S_ids, S_sc, counts = ops.sort_id_rows(torch.cat([S_ids, cand.indices], dim=1), torch.cat([S_sc, scores], dim=1))
 		if trace:

@@ -59,6 +59,8 @@ def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, de
 	pool_kw = {} if args.rerank_pool == "retrieved" else {"rerank_pool": args.rerank_pool}   # (non-CUR methods ignore the flag)
 	if args.adaptive_rounds >= 2 and curr_method == "cur":
 		pool_kw = dict(pool_kw, adaptive_rounds=args.adaptive_rounds)   # (1 = today's call; the other methods ignore the flag)
+		if args.adaptive_incremental:
+			pool_kw = dict(pool_kw, adaptive_incremental=True)
 	LOGGER.info(f"Computing approximate test mention-to-entity scores using method={curr_method}")
 	if curr_method == "cur":
 		A_train_dev = harness.to_device_matrix(A_train, device, args.dtype)
@@ -108,6 +110,8 @@ def run(args, device):
 		del arg_dict["rerank_pool"]   # the default run writes the output it wrote before the flag existed, byte for byte
 	if args.adaptive_rounds == 1:
 		del arg_dict["adaptive_rounds"]   # (the same rule)
+	if not args.adaptive_incremental:
+		del arg_dict["adaptive_incremental"]   # (the same rule)
 	eval_res["other_args"] = arg_dict
 	eval_res["other_args"]["retriever_params"] = retvr_params
 	res_file = f"{args.res_dir}/method={eval_method}_{args.misc}.json"
@@ -156,6 +160,10 @@ def build_parser(worlds=None):
 						help="N >= 2 (eval_method cur): every cell with k_retvr divisible by N additionally reports, under exact_vs_reranked_adaptive_retvr~..., the pool "
 							 "of the adaptive multi-round search -- the anchor items plus N rounds of k_retvr / N new items, each round's weights solved per query from "
 							 "everything scored so far -- at the same budget of n_anc + k_retvr exact scores per query; 1 (default) = today's run and output")
+	parser.add_argument("--adaptive_incremental", action="store_true",
+						help="with --adaptive_rounds N >= 2: extend each query's Cholesky factorisation round by round instead of solving from scratch (the same "
+							 "output keys; needs n_anc + (N - 1) k_retvr / N <= the number of training queries, cells beyond that are left out and logged); "
+							 "without --adaptive_rounds N >= 2, and for the other methods, it has no effect")
 	parser.add_argument("--compute_dtype", type=str, default="auto", choices=["auto", "fp32", "bf16", "bf16x3"],
 						help="arithmetic of the CUR retrieval: auto = by --dtype (fp32 matrix -> dense fp32 route, bf16 -> fused bf16 kernel); bf16x3 = for --dtype fp32: "
 							 "operands split into bf16 hi + lo parts on the fused kernel, candidates rescored in fp32 (the fp32 route's values, S_hat never written)")

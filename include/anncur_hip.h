@@ -399,6 +399,37 @@ int anncur_lstsq_rows(const float *Rt, int64_t ldr, int64_t m, int32_t kq, const
 int anncur_lstsq_rows_timed(const float *Rt, int64_t ldr, int64_t m, int32_t kq, const int32_t *ids, int64_t ld_ids, const float *C, int64_t ldc,
                             int64_t Q, int32_t n, double ridge, float *W, int64_t ldw, int32_t *status, void *workspace, size_t workspace_bytes,
                             void *stream, float *ms3);
+/* The same solve, item side only, on a per-query STATE that persists from call to call: a caller whose id lists only grow at the end
+ * (the rounds of the adaptive search) pays for the new rows alone.
+ *   replaces anncur_lstsq_rows called once per round on the whole scored set: n^2 (kq + n / 3) there, about k n (kq + n) here for k new items
+ * ids int32[Q x n_new] and C float[Q x n_new] are the FULL rows in insertion order; the positions < n_old must be what the previous call
+ * on this state saw (the caller's contract, not checked).  Holes are allowed anywhere and decouple as above.  n_old = 0 initialises the
+ * state: the caller pre-fills nothing, every cell that is ever read is written by this or an earlier call.  ridge must be the same in
+ * every call on one state (the caller's contract).
+ * RESULT: W and status after the call equal, bit for bit, what anncur_lstsq_rows returns for (ids[:, :n_new], C[:, :n_new], ridge).  Both
+ * run the same kernels, which take the row pitch, the place of the right-hand side and the first row / panel to compute at run time:
+ * anncur_lstsq_rows starts them at 0, this call at panel p0 = n_old / 16 (the partial 16-block's padding becomes real, so that panel is
+ * formed again).  For panels < p0 only the row blocks from p0 down are computed (the same sum over the earlier panels, then the
+ * triangular solve against the stored diagonal block), z is recomputed from 16 p0 on, the back substitution and w = R_S y run in full.
+ * PIVOT RULE: the one above.  max_i G_ii grows as items arrive, so the smallest pivot accepted so far is tested against the new threshold
+ * too: an old pivot that falls under it fails the query, as it does in anncur_lstsq_rows.  A failed query is STICKY: every later call on
+ * that state returns status 1 and a NaN row for it at the cost of reading its header, and leaves its state as it is (pivots do not change
+ * and the threshold never falls, so anncur_lstsq_rows fails it too).
+ * State: caller-owned, 256-byte aligned, anncur_lstsq_state_bytes(Q, cap) bytes (0 outside 1 <= cap <= ANNCUR_LSTSQ_MAX_G, Q >= 0); per
+ * query, in doubles at the row pitch capp = ceil16(cap): capp rows of G's lower triangle, which turns into L; a row of z = L^-1 c; a row
+ * of y (z is never overwritten); a header of 16 (the largest Gram diagonal so far, the smallest accepted pivot so far, the status).
+ * Rows at or beyond ceil16(n_new) are neither read nor written.  The layout is this library's: anncur_lstsq_state_bytes is its only
+ * authority.
+ * Limits: 0 <= n_old < n_new <= min(cap, kq), 1 <= kq <= ANNCUR_LSTSQ_MAX_KQ; n_new > kq (the query side has no incremental form) and
+ * anything else outside them is ANNCUR_E_INVALID and nothing is written; a missing, misaligned or short state is ANNCUR_E_WORKSPACE.
+ * anncur_lstsq_extend_timed: the same call, synchronised, with ms3 = HIP-event times of (Gram, factor-and-solve, w = R_S y). */
+size_t anncur_lstsq_state_bytes(int64_t Q, int32_t cap);
+int anncur_lstsq_extend(const float *Rt, int64_t ldr, int64_t m, int32_t kq, const int32_t *ids, int64_t ld_ids, const float *C, int64_t ldc,
+                        int64_t Q, int32_t n_old, int32_t n_new, int32_t cap, double ridge, float *W, int64_t ldw, int32_t *status,
+                        void *state, size_t state_bytes, void *stream);
+int anncur_lstsq_extend_timed(const float *Rt, int64_t ldr, int64_t m, int32_t kq, const int32_t *ids, int64_t ld_ids, const float *C,
+                              int64_t ldc, int64_t Q, int32_t n_old, int32_t n_new, int32_t cap, double ridge, float *W, int64_t ldw,
+                              int32_t *status, void *state, size_t state_bytes, void *stream, float *ms3);
 /* Rows of (id, score) pairs sorted ascending by id, holes (id < 0) last, scores carried along; equal keys keep their order.
  *   replaces the per-query numpy.unique of ops.exclusion (one host pass and one synchronisation per call) where a searcher re-sorts its
  *   scored set every round: the sorted full rows ARE the per-query exclusion lists of anncur_filter_topk (off[q] = q w).
