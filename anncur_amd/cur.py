@@ -361,6 +361,20 @@ def _route_topk(op, X, k, exclude=None):
 	return _filtered(ops.score_topk_dense(X, Et, kc), excl, k)
 
 
+SAMPLE_ROUTE = "sample-dense"   # the one route of _route_sample, as the adaptive search's trace names it
+
+
+def _route_sample(op, X, k, temperature=1.0, seed=0, stream=0, row_keys=None, exclude=None):
+	"""k items per query drawn without replacement with probability proportional to softmax(X . Et^T / temperature) over the item operand
+	of `op` (ops.sample_topk_dense: the noise contract, row_keys and exclude are ops.sample_topk's).  ONE route, whatever op.compute_dtype is:
+	the fp32 item operand, a dense fp32 GEMM per row chunk and the sampler on it.  Sampling has no fused route -- the noise differs per
+	(query, item) pair, so it cannot ride in the MFMA operands, and a sample inside an over-fetched head is not a sample of the softmax
+	(DESIGN 4.4e)."""
+	if X.dtype != torch.float32:
+		X = ops.convert(X, torch.float32)
+	return ops.sample_topk_dense(X, op._Et, k, temperature, seed, stream, row_keys, exclude)
+
+
 class _ItemOperand(object):
 	"""An item-major fp32 matrix Et [m x K] prepared for _route_topk the way CURRowIndex prepares E^T: "bf16" packs it (item order and
 	descending-norm order with the id map), "bf16x3" builds the split operands, "fp32" keeps it as it is."""
@@ -380,6 +394,9 @@ class _ItemOperand(object):
 	def route(self, Q, k, exclude=None):
 		excl, _ = _exclusion_arg(exclude, Q, self.m, k, self._Et.device)
 		return _route_name(self, Q, k, excl)
+
+	def sample(self, X, k, temperature=1.0, seed=0, stream=0, row_keys=None, exclude=None):
+		return _route_sample(self, X, k, temperature, seed, stream, row_keys, exclude)
 
 
 class CURRowIndex(object):
@@ -413,6 +430,13 @@ class CURRowIndex(object):
 		exclude: items left out of the result, as for CURApprox.topk_in_row_device (e.g. ops.exclusion(self.col_idxs, ...), built once:
 		the anchor items, whose exact scores the caller holds already)."""
 		return _route_topk(self, X, k, exclude)
+
+	def sample(self, X, k, temperature=1.0, seed=0, stream=0, row_keys=None, exclude=None):
+		"""X [q x kc] -> TopK(perturbed keys f32, indices int32) on the GPU: k items per query drawn without replacement with probability
+		proportional to softmax(S_hat / temperature), S_hat = X . E (ops.sample_topk: Gumbel top-k, reproducible from seed, stream and
+		row_keys; exclude as for topk).  Always on the fp32 item operand, whatever compute_dtype is: sampling has no fused route
+		(_route_sample says why)."""
+		return _route_sample(self, X, k, temperature, seed, stream, row_keys, exclude)
 
 	def adaptive_operand(self):
 		"""The operand of the adaptive search's retrieval, built at the first call: the anchor rows themselves as ITEM

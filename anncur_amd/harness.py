@@ -261,22 +261,26 @@ def _sweep_pool_cells(A_test_dev, anc, retrieved_idx, exact, top_k_vals, top_k_r
 
 
 ADAPTIVE_PREFIX = "exact_vs_reranked_adaptive_retvr"   # --adaptive_rounds of entry point B
+ADAPTIVE_SOFTMAX_PREFIX = "exact_vs_reranked_adaptive_softmax_retvr"   # ... with --adaptive_strategy softmax
 
 
-def _sweep_adaptive_cells(A_test_dev, A_train_dev, anc, exact, top_k_vals, top_k_retr_vals, n_rounds, compute_dtype, pinv_backend, incremental=False):
+def _sweep_adaptive_cells(A_test_dev, A_train_dev, anc, exact, top_k_vals, top_k_retr_vals, n_rounds, compute_dtype, pinv_backend, incremental=False,
+						  strategy="topk", temperature=1.0, seed=0):
 	"""The adaptive-search metrics (ADAPTIVE_PREFIX) of the (top_k, k_retvr) cells of one anchor set: the pool of a cell is the anchor items
 	+ n_rounds rounds of k_retvr / n_rounds NEW items each, scored through MatrixScorer(A_test) -- its own AdaptiveSearcher run per k_retvr,
 	because adaptive results are not prefixes of one another --, and recall is the closed form |exact[:k] & pool| (retrieval.overlap_pool_cells'
 	statement: one ops.overlap_counts call on the pool's id list).  Cells with k_retvr % n_rounds != 0 or outside search.adaptive_limits
 	are left out, with one log line for the anchor set that names the limit.  incremental: AdaptiveSearcher's switch (the per-query factorisation
-	extended round by round), with its own limit kc + (n_rounds - 1) k_step <= kq among those."""
+	extended round by round), with its own limit kc + (n_rounds - 1) k_step <= kq among those.  strategy / temperature / seed: AdaptiveSearcher's
+	(DESIGN 4.4e); "softmax" cells report under ADAPTIVE_SOFTMAX_PREFIX, so the two strategies' files can be merged."""
 	from .search import AdaptiveSearcher, MatrixScorer, adaptive_limits
+	prefix = ADAPTIVE_SOFTMAX_PREFIX if strategy == "softmax" else ADAPTIVE_PREFIX
 	out, skipped = {}, []
 	if len(anc) == 0:
-		LOGGER.info("adaptive_rounds=%d: no anchor items: every cell left out of %s (the first round needs anchor scores)", n_rounds, ADAPTIVE_PREFIX)
+		LOGGER.info("adaptive_rounds=%d: no anchor items: every cell left out of %s (the first round needs anchor scores)", n_rounds, prefix)
 		return out
 	index = CURRowIndex(A_train_dev, np.asarray(anc), compute_dtype=compute_dtype, pinv_backend=pinv_backend)
-	searcher = AdaptiveSearcher(index, MatrixScorer(A_test_dev), incremental=incremental)
+	searcher = AdaptiveSearcher(index, MatrixScorer(A_test_dev), incremental=incremental, strategy=strategy, temperature=temperature, seed=seed)
 	qids = torch.arange(A_test_dev.shape[0], dtype=torch.int64)
 	for kr in top_k_retr_vals:
 		ks = [k for k in top_k_vals if k <= kr and k <= exact.indices.shape[1]]
@@ -293,21 +297,22 @@ def _sweep_adaptive_cells(A_test_dev, A_train_dev, anc, exact, top_k_vals, top_k
 		pool = searcher.search(qids, 1, kr // n_rounds, n_rounds, trace=True).trace[-1]["ids"]      # the final S_q: anchors + everything scored
 		counts = ops.overlap_counts(exact.indices, pool, [(k, pool.shape[1]) for k in ks]).cpu().numpy()
 		for j, k in enumerate(ks):
-			out[(k, kr)] = flatten_overlap(overlap_stats_from_counts(counts[j], k), prefix=ADAPTIVE_PREFIX)
+			out[(k, kr)] = flatten_overlap(overlap_stats_from_counts(counts[j], k), prefix=prefix)
 	if skipped:
-		LOGGER.info("adaptive_rounds=%d: %d k_retvr value(s) with %d anchor items left out of %s: %s", n_rounds, len(skipped), len(anc), ADAPTIVE_PREFIX,
+		LOGGER.info("adaptive_rounds=%d: %d k_retvr value(s) with %d anchor items left out of %s: %s", n_rounds, len(skipped), len(anc), prefix,
 					"; ".join(f"k_retvr={kr}: {why}" for kr, why in skipped))
 	return out
 
 
 def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None, progress=None, key_n_m=None, pinv_backend="auto", rerank_pool="retrieved",
-						literal_rerank=False, adaptive_rounds=1, adaptive_incremental=False):
+						literal_rerank=False, adaptive_rounds=1, adaptive_incremental=False, adaptive_strategy="topk", adaptive_temperature=1.0, adaptive_seed=0):
 	"""eval_method == "cur" of entry point B for one seed (splits.py:286-303 + 399-429).
 	rerank_pool "retrieved+anchors": every cell also reports, under POOL_PREFIX, the metrics of the pool anchor items + k_retvr NEW items (a
 	second retrieval per anchor count, with the anchor items excluded, at the largest k_retvr with k_retvr + n_anc <= pool_cell_limit).
 	adaptive_rounds N >= 2: every cell with k_retvr divisible by N also reports, under ADAPTIVE_PREFIX, the metrics of the adaptive search's
 	pool at the same budget (_sweep_adaptive_cells); 1 is today's code path.  adaptive_incremental: that search with AdaptiveSearcher(incremental=True);
-	the output keys are the same."""
+	the output keys are the same.  adaptive_strategy "softmax" (with adaptive_temperature, adaptive_seed): that search with sampled rounds
+	(DESIGN 4.4e), reported under ADAPTIVE_SOFTMAX_PREFIX instead."""
 	with_pool = _check_rerank_pool(rerank_pool)
 	if adaptive_rounds < 1:
 		raise ValueError(f"adaptive_rounds = {adaptive_rounds}: need adaptive_rounds >= 1")
@@ -349,7 +354,7 @@ def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None
 			del new_items
 		if adaptive_rounds >= 2:
 			for (k, kr), metrics in _sweep_adaptive_cells(A_test_dev, A_train_dev, anc, exact, top_k_vals, retr_vals, adaptive_rounds, compute_dtype, pinv_backend,
-																  adaptive_incremental).items():
+																  adaptive_incremental, adaptive_strategy, adaptive_temperature, adaptive_seed).items():
 				res[f"top_k={k}"][f"k_retvr={kr}"][f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}"].update(metrics)
 		del cur, approx
 	return {a: {b: dict(c) for b, c in d.items()} for a, d in res.items()}

@@ -952,6 +952,129 @@ def score_topk_dense(X, Et, k, max_bytes=2 << 30):
 	return TopK(val, idx)
 
 
+# ------------------------------------------------------------------ SoftMax item sampling
+def _temperature_arg(temperature, what):
+	if isinstance(temperature, bool) or not isinstance(temperature, (int, float, np.integer, np.floating)) or not np.isfinite(temperature) or not temperature > 0:
+		raise ValueError(f"{what}: temperature = {temperature!r}, need a finite temperature > 0")
+	return float(temperature)
+
+
+def _noise_args(seed, stream, what):
+	"""(seed, stream) as Python ints inside the counter's fields, or a ValueError that names the limit."""
+	for name, v, bits in (("seed", seed, 64), ("stream", stream, 32)):
+		if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+			raise ValueError(f"{what}: {name} must be an integer in [0, 2^{bits}) (got {v!r})")
+		if not 0 <= int(v) < (1 << bits):
+			raise ValueError(f"{what}: {name} = {int(v)} outside [0, 2^{bits})")
+	return int(seed), int(stream)
+
+
+def _row_keys(row_keys, Q, device, what):
+	"""row_keys= -> None (the row numbers) or int32 [Q] on `device` holding the low 32 bits of every key (the kernels read them as uint32)."""
+	if row_keys is None:
+		return None
+	t = row_keys if torch.is_tensor(row_keys) else torch.as_tensor(np.asarray(row_keys))
+	if t.dim() != 1 or t.numel() != Q:
+		raise ValueError(f"{what}: row_keys must hold one key per row: {Q} (got shape {tuple(t.shape)})")
+	if t.dtype.is_floating_point or t.dtype == torch.bool:
+		raise ValueError(f"{what}: row_keys must be integers (got {t.dtype})")
+	t = t.to(torch.int64)
+	return ((((t & 0xffffffff) ^ 0x80000000) - 0x80000000).to(torch.int32)).to(device).contiguous()   # low 32 bits, as the int32 of the same bit pattern
+
+
+def _sample_args(Q, I, k, temperature, seed, stream, row_keys):
+	"""Host-side validation of sample_topk, before any tensor has to be on the GPU: -> (inv_T as numpy.float32, seed, stream)."""
+	with np.errstate(over="ignore", under="ignore"):
+		inv_T = np.float32(1.0 / _temperature_arg(temperature, "sample_topk"))
+	if not (np.isfinite(inv_T) and inv_T > 0):
+		raise ValueError(f"sample_topk: temperature = {temperature!r}: 1 / temperature = {inv_T} is not a finite fp32 number > 0")
+	seed, stream = _noise_args(seed, stream, "sample_topk")
+	if I >= 1 << 31:
+		raise ValueError(f"sample_topk: {I} items, need fewer than 2^31")
+	limit = min(I, _lib.MAX_TOPK)
+	if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or k > limit:
+		raise ValueError(f"sample_topk: k = {k!r} outside 1..min(items, ANNCUR_MAX_TOPK) = min({I}, {_lib.MAX_TOPK}) = {limit}")
+	if row_keys is not None:
+		n = row_keys.numel() if torch.is_tensor(row_keys) else np.asarray(row_keys).size
+		if n != Q:
+			raise ValueError(f"sample_topk: row_keys must hold one key per row: {Q} (got {n})")
+	return inv_T, seed, stream
+
+
+@_on_device
+def gumbel_noise(seed, stream, rows, I):
+	"""g [Q x I] fp32: the standard Gumbel noise the sampler adds to row key r, item i (anncur_gumbel_noise; the contract is in
+	include/anncur_hip.h).  rows: an int (the keys 0..rows-1) or a 1-D integer tensor / array of keys (their low 32 bits count).  For tests
+	and for auditing a draw: sample_topk never materialises it.  On the device of `rows` if that is a GPU tensor, else on the current one."""
+	seed, stream = _noise_args(seed, stream, "gumbel_noise")
+	if isinstance(rows, (int, np.integer)) and not isinstance(rows, bool):
+		Q, keys = int(rows), None
+		if Q < 0:
+			raise ValueError(f"gumbel_noise: rows = {Q}, need rows >= 0")
+	else:
+		Q, keys = (rows.numel() if torch.is_tensor(rows) else np.asarray(rows).size), rows
+	if not 1 <= I <= 1 << 31:
+		raise ValueError(f"gumbel_noise: I = {I} outside 1..2^31 (item ids are 31-bit)")
+	device = rows.device if torch.is_tensor(rows) and rows.is_cuda else torch.device("cuda", torch.cuda.current_device())
+	keys = _row_keys(keys, Q, device, "gumbel_noise")
+	with torch.cuda.device(device):
+		out = torch.empty((Q, I), dtype=torch.float32, device=device)
+		check(_lib.load().anncur_gumbel_noise(seed, stream, _p(keys) if keys is not None else None, Q, I, _p(out), I, _stream()), "gumbel_noise")
+	return out
+
+
+@_on_device
+def sample_topk(S, k, temperature=1.0, seed=0, stream=0, row_keys=None, exclude=None):
+	"""k items per row of S (fp32 [Q x I], rows may be padded) drawn WITHOUT replacement with probability proportional to
+	softmax(S / temperature): Gumbel top-k (anncur_sample_topk) -> TopK(keys f32 [Q x k], indices int32 [Q x k]), the perturbed keys
+	S / temperature + g descending, ties by the smaller id, (-inf, -1) where a row has fewer than k allowed non-NaN items.  The noise g is a
+	pure function of (seed, stream, row key, item id): row_keys (one integer per row, low 32 bits; default the row numbers) name the rows, so
+	a row draws the same items wherever it stands in a call.  exclude: anything exclusion() takes; an Exclusion passes through.
+	ValueError (before any device call): temperature not finite or <= 0, seed outside [0, 2^64), stream outside [0, 2^32), k outside
+	1..min(I, ANNCUR_MAX_TOPK), row_keys of the wrong length."""
+	if not torch.is_tensor(S) or S.dim() != 2:
+		raise ValueError("sample_topk: S must be a 2-D tensor [Q x I]")
+	Q, I = S.shape
+	inv_T, seed, stream = _sample_args(Q, I, k, temperature, seed, stream, row_keys)
+	_dev(S)
+	if S.dtype != torch.float32:
+		raise TypeError(f"sample_topk takes float32 scores (got {S.dtype})")
+	S = _rowmajor(S)
+	keys = _row_keys(row_keys, Q, S.device, "sample_topk")
+	ex = exclusion(exclude, Q, I, S.device)
+	n_ids = ex.ids.numel() if ex.ids is not None else 0
+	val = torch.empty((Q, k), dtype=torch.float32, device=S.device)
+	idx = torch.empty((Q, k), dtype=torch.int32, device=S.device)
+	check(_lib.load().anncur_sample_topk(_p(S), _ld(S), Q, I, float(inv_T), seed, stream, _p(keys) if keys is not None else None,
+										 _p(ex.off) if ex.off is not None else None, _p(ex.ids) if n_ids else None, n_ids if ex.off is None else 0, int(k),
+										 _p(val), _p(idx), _stream()), "sample_topk")
+	return TopK(val, idx)
+
+
+@_on_device
+def sample_topk_dense(X, Et, k, temperature=1.0, seed=0, stream=0, row_keys=None, exclude=None, max_bytes=2 << 30):
+	"""sample_topk on S = X @ Et^T without holding S: score_topk_dense's loop over row chunks -- the fp32 GEMM of a chunk, then the sampler
+	on it, with the chunk's row keys and the chunk's slice of the exclusion's offsets (they are absolute: a view suffices).  The noise
+	belongs to (row key, item), so the result does not depend on max_bytes."""
+	Q, I = X.shape[0], Et.shape[0]
+	_sample_args(Q, I, k, temperature, seed, stream, row_keys)
+	_dev(X, Et)
+	keys = _row_keys(row_keys, Q, X.device, "sample_topk_dense")
+	if keys is None:
+		keys = torch.arange(Q, dtype=torch.int32, device=X.device)   # (a chunk's row numbers start at 0: name the rows explicitly)
+	ex = exclusion(exclude, Q, I, X.device)
+	val = torch.empty((Q, k), dtype=torch.float32, device=X.device)
+	idx = torch.empty((Q, k), dtype=torch.int32, device=X.device)
+	rows = max(1, min(Q, max_bytes // max(4 * I, 1)))
+	for q0 in range(0, Q, rows):
+		q1 = min(Q, q0 + rows)
+		S = _dense_scores(X[q0:q1], Et)
+		ex_c = ex if ex.off is None else Exclusion(ex.off[q0:q1 + 1], ex.ids, ex.e_max)
+		v, i = sample_topk(S, k, temperature, seed, stream, keys[q0:q1], ex_c)
+		val[q0:q1], idx[q0:q1] = v, i
+	return TopK(val, idx)
+
+
 @_on_device
 def rerank(A, approx_idx, k_retvr, k_out):
 	"""The k_out best of approx_idx[:, :k_retvr] by exact score A (reference: ..._splits.py:93-96)."""

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .cur import _is_full_range
+from .cur import SAMPLE_ROUTE, _is_full_range
 
 SearchResult = namedtuple("SearchResult", ["values", "indices", "n_scored"])
 AdaptiveResult = namedtuple("AdaptiveResult", ["values", "indices", "n_scored", "n_fallback", "trace"])
@@ -114,6 +114,9 @@ def adaptive_limits(kc, kq, m, k, k_step, n_rounds, incremental=False):
 		raise ValueError(f"adaptive search: need 1 <= k <= min(pool size, ANNCUR_MAX_TOPK) = min({pool}, {max_topk}) = {min(pool, max_topk)} (got k = {k})")
 
 
+STRATEGIES = ("topk", "softmax")   # how a round of the adaptive search picks its new items
+
+
 class AdaptiveSearcher(object):
 	"""The multi-round search of DESIGN 4.4d ("Adaptive Selection of Anchor Items for CUR-based k-NN search with Cross-Encoders"): the
 	budget of kc + n_rounds * k_step scorer cells per query is spent in rounds, and the items scored in round r become additional anchor
@@ -135,9 +138,22 @@ class AdaptiveSearcher(object):
 	kc + (n_rounds - 1) k_step, which factors only the positions a round appends (kc + k_step in round 2, k_step afterwards).  W is,
 	bit for bit, ops.lstsq_rows on the same ordered rows; against incremental=False the unknowns are permuted, so the weights agree to
 	rounding only.  The id-sorted copy is kept for the exclusion alone.  A failed query stays failed in the state: it takes the host
-	fallback in every later round and is counted once."""
+	fallback in every later round and is counted once.
 
-	def __init__(self, index, scorer, ridge=0.0, incremental=False):
+	strategy: how a round picks its k_step new items (the paper names both).  "topk" (default): the k_step best of s_hat_q outside S_q --
+	everything above, bit for bit.  "softmax": k_step items drawn without replacement with probability proportional to
+	softmax(s_hat_q / temperature) outside S_q -- EVERY round, the first included: index.sample on X . E in round 1, the operand's sample on
+	W . R afterwards (Gumbel top-k on the fp32 item operand, one dense route whatever compute_dtype is).  The noise of round r
+	is drawn from (seed, stream = r, row key = the low 32 bits of the query's id, item id): a search is reproducible, and a query draws the
+	same items wherever it stands in query_ids.  n_rounds = 1 with "softmax" is a sampled single round, no longer
+	CrossEncoderSearcher.search.  The exclusion, the limits (adaptive_limits; the sampler takes k_step directly, so no k + e retrieval and no
+	ops.filtered_k), the solves and the final re-rank are the same; it works with and without incremental=True."""
+
+	def __init__(self, index, scorer, ridge=0.0, incremental=False, strategy="topk", temperature=1.0, seed=0):
+		if strategy not in STRATEGIES:
+			raise ValueError(f"AdaptiveSearcher: strategy = {strategy!r}, need one of {STRATEGIES}")
+		self.strategy, self.temperature = strategy, ops._temperature_arg(temperature, "AdaptiveSearcher")
+		self.seed = ops._noise_args(seed, 0, "AdaptiveSearcher")[0]
 		self.index, self.scorer, self.ridge, self.incremental = index, scorer, float(ridge), bool(incremental)
 		if not self.ridge >= 0.0:
 			raise ValueError(f"AdaptiveSearcher: ridge = {ridge}, need ridge >= 0")
@@ -168,16 +184,25 @@ class AdaptiveSearcher(object):
 		W[bad] = torch.from_numpy(rows).to(W.device)
 		return bad
 
+	def _candidates(self, op, X, k_step, excl, r, row_keys):
+		"""Round r's k_step new items from `op` (the index in round 1, its adaptive operand afterwards) by the searcher's strategy."""
+		if self.strategy == "softmax":
+			return op.sample(X, k_step, self.temperature, self.seed, r, row_keys, excl)
+		return op.topk(X, k_step, exclude=excl)
+
 	def search(self, query_ids, k, k_step, n_rounds, trace=False):
 		"""-> AdaptiveResult(values f32 [Q x k], indices int32 [Q x k], n_scored = kc + n_rounds * k_step, n_fallback, trace): the k best by
 		exact score among the anchors and everything the rounds scored, descending, ties by the smaller id.  ValueError (adaptive_limits,
 		before the first scorer call) names the limit.  trace=True: a list with one dict per round r >= 2 -- "ids", "scores" (the id-sorted
-		S_q and its scores the round solved on), "W" (after the host fallback), "status", "candidates" (the TopK retrieved), "route" --
+		S_q and its scores the round solved on), "W" (after the host fallback), "status", "candidates" (the TopK retrieved, or the sampler's
+		perturbed keys and items), "route" ("sample-dense" for a sampled round) --
 		all tensors on the device; with incremental=True also "order_ids" and "order_scores", the rows in insertion order that the solve
 		was given ("ids" / "scores" then hold the same pairs sorted, as the exclusion takes them)."""
 		adaptive_limits(self.kc, self.kq, self.index.m, k, k_step, n_rounds, self.incremental)
+		soft = self.strategy == "softmax"
+		row_keys = ops._row_keys(query_ids, len(query_ids), self._anchor_ids.device, "adaptive search") if soft else None
 		X = self.scorer(query_ids, self._anchor_ids)
-		cand = self.index.topk(X, k_step, exclude=self._excl)
+		cand = self._candidates(self.index, X, k_step, self._excl, 1, row_keys)
 		scores = self.scorer(query_ids, cand.indices)
 		if scores.dtype != torch.float32:
 			scores = ops.convert(scores, torch.float32)
@@ -204,12 +229,12 @@ class AdaptiveSearcher(object):
 				W, status = state.extend(O_ids, O_sc)
 			fell_back.update(self._fallback(Rt, S_ids, S_sc, W, status).tolist())
 			excl = ops.exclusion_from_sorted_rows(S_ids, counts)
-			cand = operand.topk(W, k_step, excl)
+			cand = self._candidates(operand, W, k_step, excl, r, row_keys)
 			scores = self.scorer(query_ids, cand.indices)
 			if scores.dtype != torch.float32:
 				scores = ops.convert(scores, torch.float32)
 			if trace:
-				log.append({"ids": S_ids, "scores": S_sc, "W": W, "status": status, "candidates": cand, "route": operand.route(Q, k_step, excl)})
+				log.append({"ids": S_ids, "scores": S_sc, "W": W, "status": status, "candidates": cand, "route": SAMPLE_ROUTE if soft else operand.route(Q, k_step, excl)})
 				if state is not None:
 					log[-1].update({"order_ids": O_ids, "order_scores": O_sc})
 			new_ids, new_scores = torch.cat([new_ids, cand.indices], dim=1), torch.cat([new_scores, scores], dim=1)

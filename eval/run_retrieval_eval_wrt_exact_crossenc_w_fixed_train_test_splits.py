@@ -40,6 +40,20 @@ def _rounds(s):
 	return n
 
 
+def _temperature(s):
+	t = float(s)
+	if not (t > 0 and t < float("inf")):
+		raise argparse.ArgumentTypeError("--adaptive_temperature needs a finite number > 0")
+	return t
+
+
+def _seed(s):
+	n = int(s)
+	if not 0 <= n < 1 << 64:
+		raise argparse.ArgumentTypeError("--adaptive_seed needs an integer in [0, 2^64)")
+	return n
+
+
 def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, device):
 	from anncur_amd import harness, ops
 	LOGGER.info("Loading precomputed ment_to_ent scores")
@@ -61,6 +75,12 @@ def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, de
 		pool_kw = dict(pool_kw, adaptive_rounds=args.adaptive_rounds)   # (1 = today's call; the other methods ignore the flag)
 		if args.adaptive_incremental:
 			pool_kw = dict(pool_kw, adaptive_incremental=True)
+		if args.adaptive_strategy != "topk":
+			pool_kw = dict(pool_kw, adaptive_strategy=args.adaptive_strategy)
+		if args.adaptive_temperature != 1.0:
+			pool_kw = dict(pool_kw, adaptive_temperature=args.adaptive_temperature)
+		if args.adaptive_seed != 0:
+			pool_kw = dict(pool_kw, adaptive_seed=args.adaptive_seed)
 	LOGGER.info(f"Computing approximate test mention-to-entity scores using method={curr_method}")
 	if curr_method == "cur":
 		A_train_dev = harness.to_device_matrix(A_train, device, args.dtype)
@@ -112,6 +132,9 @@ def run(args, device):
 		del arg_dict["adaptive_rounds"]   # (the same rule)
 	if not args.adaptive_incremental:
 		del arg_dict["adaptive_incremental"]   # (the same rule)
+	for key, default in (("adaptive_strategy", "topk"), ("adaptive_temperature", 1.0), ("adaptive_seed", 0)):
+		if getattr(args, key) == default:
+			del arg_dict[key]   # (the same rule)
 	eval_res["other_args"] = arg_dict
 	eval_res["other_args"]["retriever_params"] = retvr_params
 	res_file = f"{args.res_dir}/method={eval_method}_{args.misc}.json"
@@ -164,6 +187,13 @@ def build_parser(worlds=None):
 						help="with --adaptive_rounds N >= 2: extend each query's Cholesky factorisation round by round instead of solving from scratch (the same "
 							 "output keys; needs n_anc + (N - 1) k_retvr / N <= the number of training queries, cells beyond that are left out and logged); "
 							 "without --adaptive_rounds N >= 2, and for the other methods, it has no effect")
+	parser.add_argument("--adaptive_strategy", type=str, default="topk", choices=["topk", "softmax"],
+						help="with --adaptive_rounds N >= 2: how a round picks its new items: topk = the k_retvr / N best of the round's approximate scores (today's run "
+							 "and output); softmax = that many items drawn without replacement with probability proportional to softmax(scores / temperature), every "
+							 "round, reported under exact_vs_reranked_adaptive_softmax_retvr~... instead; without --adaptive_rounds N >= 2 it has no effect")
+	parser.add_argument("--adaptive_temperature", type=_temperature, default=1.0, help="temperature of --adaptive_strategy softmax (finite, > 0; default 1)")
+	parser.add_argument("--adaptive_seed", type=_seed, default=0,
+						help="seed of --adaptive_strategy softmax's noise, in [0, 2^64) (default 0); round r draws from stream r, a query from its row number")
 	parser.add_argument("--compute_dtype", type=str, default="auto", choices=["auto", "fp32", "bf16", "bf16x3"],
 						help="arithmetic of the CUR retrieval: auto = by --dtype (fp32 matrix -> dense fp32 route, bf16 -> fused bf16 kernel); bf16x3 = for --dtype fp32: "
 							 "operands split into bf16 hi + lo parts on the fused kernel, candidates rescored in fp32 (the fp32 route's values, S_hat never written)")

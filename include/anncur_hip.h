@@ -438,6 +438,37 @@ int anncur_lstsq_extend_timed(const float *Rt, int64_t ldr, int64_t m, int32_t k
 int anncur_sort_id_rows(const int32_t *in_ids, const float *in_val, int64_t ld_in, int64_t Q, int32_t w, int32_t *out_ids, float *out_val,
                         int64_t ld_out, int32_t *counts, void *stream);
 
+/* SoftMax item sampling: k items per row drawn WITHOUT replacement with probability proportional to softmax(S / T) ------
+ *   the paper's second strategy for a round's new items, next to TopK ("Adaptive Selection of Anchor Items for CUR-based k-NN search
+ *   with Cross-Encoders"); negatives for distillation sampled from the approximate score distribution   utils/data_process.py:343-365
+ * Sampling without replacement is Gumbel top-k: the k largest of key(q, i) = S[q, i] / T + g(q, i) with g i.i.d. standard Gumbel.
+ * THE NOISE (a contract): g is a pure function of (seed, stream_id, row key, item id) -- not of the launch shape, the row chunking or the
+ * row's position in the call --, so a draw is reproducible and can be restated on the host:
+ *   mix64(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31        (uint64, wrapping)
+ *   base = mix64(seed + 0x9E3779B97F4A7C15 * ((uint64)stream_id + 1))
+ *   z    = mix64(base ^ ((uint64)row_key << 32 | (uint64)item))
+ *   u    = ((z >> 41) + 0.5) * 2^-23          23 bits: exactly representable in fp32, strictly inside (0, 1)
+ *   g    = -logf(-logf(u))                    the accurate logf, no fast intrinsic; g lies in [-2.82, 16.64], always finite
+ *   key  = __fadd_rn(__fmul_rn(s, inv_T), g)  two separately rounded fp32 operations, never contracted to an fma
+ * so key equals numpy.float32(numpy.float32(s * inv_T) + g) for the device's g.
+ *
+ * anncur_sample_topk: S float[Q x I] with row pitch lds >= I (the pad is never read; S is read once and never written).  row_keys
+ *   int32[Q], read as uint32; NULL = the row number.  The exclusion arguments are anncur_filter_topk's: excl_off != NULL: query q never
+ *   draws excl_ids[excl_off[q] .. excl_off[q+1]) (int64[Q + 1]); excl_off == NULL: no query draws excl_ids[0 .. n_excl_shared); segments
+ *   STRICTLY ASCENDING, trusted; excl_ids may be NULL when there is nothing to exclude.
+ *   out_key float[Q x k], out_idx int32[Q x k], contiguous: the k allowed items with the largest keys, key descending, ties by the
+ *   smaller id; out_key holds the perturbed keys.  A NaN score is never selected, -inf is an ordinary candidate (its key is -inf),
+ *   (-inf, -1) pads a row with fewer than k allowed non-NaN items.
+ *   1 <= k <= min(I, ANNCUR_MAX_TOPK), I < 2^31, inv_T = 1 / T finite and > 0, 0 <= Q < 2^31 (Q == 0 returns OK); anything else is
+ *   ANNCUR_E_INVALID and nothing is written.  One workgroup per query, no workspace.
+ * anncur_gumbel_noise: out float[Q x I] (pitch ldo >= I) = g(q, i) alone, from the device function the sampler calls: for tests and for
+ *   auditing a draw; the sampler itself never materialises it.  1 <= I <= 2^31 (item ids are 31-bit), Q >= 0. */
+int anncur_sample_topk(const float *S, int64_t lds, int64_t Q, int64_t I, float inv_T, uint64_t seed, uint32_t stream_id,
+                       const int32_t *row_keys, const int64_t *excl_off, const int32_t *excl_ids, int64_t n_excl_shared, int32_t k,
+                       float *out_key, int32_t *out_idx, void *stream);
+int anncur_gumbel_noise(uint64_t seed, uint32_t stream_id, const int32_t *row_keys, int64_t Q, int64_t I, float *out, int64_t ldo,
+                        void *stream);
+
 /* f3: IVF-flat inner-product index (the branch of build_flat_or_ivff_index above 11 000 vectors) -------------------------------
  *   faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT).train / .add / .search     models/nearest_nbr.py:40-52
  * FAISS is not vendored nor pinned by the reference (parity unpinned): restated from the published algorithm, judged on recall
