@@ -90,6 +90,9 @@ SIGNATURES = {
 	"anncur_sample_topk": (c_int, [c_void_p, c_int64, c_int64, c_int64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
 								   c_void_p, c_void_p, c_void_p]),
 	"anncur_gumbel_noise": (c_int, [ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+	"anncur_select_pivoted_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+	"anncur_select_pivoted_slice_items": (c_int32, [c_int]),
+	"anncur_select_pivoted": (c_int, [c_void_p, c_int, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 	"anncur_overlap_counts": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, _p32, _p32, c_int32, c_void_p, c_void_p]),
 	"anncur_copy_bytes": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
 	"anncur_ivf_build_lists": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -399,6 +399,51 @@ class _ItemOperand(object):
 		return _route_sample(self, X, k, temperature, seed, stream, row_keys, exclude)
 
 
+ANCHOR_SELECTIONS = ("random", "pivoted")
+
+
+class AnchorSelection(object):
+	"""Anchor items in SELECTION order (select_anchor_items).  order: np.int64 [n_sel]; gains: np.float64 [n_sel], the squared residual norm
+	each item had when the pivoted selection took it (None for "random").  The pivoted selection is nested: sorted(n) is the anchor set of n
+	items for every n <= n_sel, in the sorted form CURApprox / CURRowIndex take as col_idxs."""
+
+	def __init__(self, order, gains=None):
+		self.order = np.asarray(order, dtype=np.int64).reshape(-1)
+		self.gains = None if gains is None else np.asarray(gains, dtype=np.float64).reshape(-1)
+
+	@property
+	def n_sel(self):
+		return int(self.order.shape[0])
+
+	def sorted(self, n=None):
+		n = self.n_sel if n is None else n
+		if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+			raise ValueError(f"AnchorSelection.sorted: n must be an integer >= 0 (got {n!r})")
+		if n > self.n_sel:
+			raise ValueError(f"AnchorSelection.sorted: n = {n} anchor items asked of a selection of n_sel = {self.n_sel}")
+		return sorted(int(i) for i in self.order[:n])
+
+
+def select_anchor_items(rows, n, method="pivoted", rng=None):
+	"""The index' choice of its n anchor items from the anchor rows `rows` [kq x m] -> AnchorSelection.
+	"pivoted": column-pivoted QR of rows on the device (ops.select_pivoted): deterministic, nested, and it stops at the numerical
+	  rank, so n_sel may be below n.  rows on the CPU are moved to the GPU.
+	"random": sorted(rng.choice(m, n, replace=False)), the reference's selection (..._splits.py:295) from the caller's generator `rng`."""
+	if method not in ANCHOR_SELECTIONS:
+		raise ValueError(f"select_anchor_items: method = {method!r}, need one of {ANCHOR_SELECTIONS}")
+	m = rows.shape[1]
+	if method == "random":
+		if rng is None:
+			raise ValueError("select_anchor_items: method 'random' needs rng= (a numpy Generator)")
+		return AnchorSelection(sorted(rng.choice(m, size=n, replace=False)))
+	if rng is not None:
+		raise ValueError("select_anchor_items: method 'pivoted' is deterministic and takes no rng")
+	if torch.is_tensor(rows) and not rows.is_cuda:
+		rows = rows.cuda()
+	ids, gains, n_sel = ops.select_pivoted(rows, n)
+	return AnchorSelection(ids[:n_sel].cpu().numpy(), gains[:n_sel].cpu().numpy())
+
+
 class CURRowIndex(object):
 	"""The "rows"-preference index alone: built from the anchor rows R [kr x m] and the anchor columns' ids, without the
 	(n x kc) matrix of every query's anchor scores.  This is what a rank of a row-sharded evaluation holds: R assembled by one

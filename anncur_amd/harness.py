@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .cur import CURApprox, CURRowIndex
+from .cur import ANCHOR_SELECTIONS, CURApprox, CURRowIndex, select_anchor_items
 from .eval_utils import flatten_overlap, overlap_stats_from_counts
 from .retrieval import POOL_PREFIX, overlap_pool_cells, pool_cell_limit, split_pool_cells
 
@@ -260,6 +260,22 @@ def _sweep_pool_cells(A_test_dev, anc, retrieved_idx, exact, top_k_vals, top_k_r
 	return {cell: flatten_overlap(overlap_stats_from_counts(counts[j], cell[0]), prefix=POOL_PREFIX) for j, cell in enumerate(kept)}
 
 
+def _pivoted_anchor_counts(A_train_dev, anc_vals):
+	"""anchor_selection "pivoted": ONE select_anchor_items call at the largest anchor count the selection can deliver -- n_anc <= the number
+	of training queries kq (a column of R has kq entries: no more directions exist), <= ANNCUR_MAX_TOPK and <= the numerical rank n_sel it
+	stops at -- serves every count (the selection is nested).  -> (AnchorSelection or None, the counts left out); those are logged once."""
+	kq, n_ent = A_train_dev.shape
+	lim = min(kq, n_ent, ops._lib.MAX_TOPK)
+	usable = [n for n in anc_vals if 0 < n <= lim]
+	sel = select_anchor_items(A_train_dev, max(usable), method="pivoted") if usable else None
+	skipped = sorted({n for n in anc_vals if n > 0 and (n > lim or n > sel.n_sel)})
+	if skipped:
+		LOGGER.info("anchor_selection=pivoted: %d anchor count(s) left out (n_ent_anchors %s): the selection delivers at most min(kq, n_ent, ANNCUR_MAX_TOPK) = "
+					"min(%d, %d, %d) = %d items and stopped at the numerical rank n_sel = %s", len(skipped), ",".join(str(n) for n in skipped), kq, n_ent,
+					ops._lib.MAX_TOPK, lim, "-" if sel is None else sel.n_sel)
+	return sel, skipped
+
+
 ADAPTIVE_PREFIX = "exact_vs_reranked_adaptive_retvr"   # --adaptive_rounds of entry point B (DESIGN 4.4d)
 ADAPTIVE_SOFTMAX_PREFIX = "exact_vs_reranked_adaptive_softmax_retvr"   # ... with --adaptive_strategy softmax (DESIGN 4.4e)
 
@@ -305,15 +321,22 @@ def _sweep_adaptive_cells(A_test_dev, A_train_dev, anc, exact, top_k_vals, top_k
 
 
 def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None, progress=None, key_n_m=None, pinv_backend="auto", rerank_pool="retrieved",
-						literal_rerank=False, adaptive_rounds=1, adaptive_incremental=False, adaptive_strategy="topk", adaptive_temperature=1.0, adaptive_seed=0):
+						literal_rerank=False, adaptive_rounds=1, adaptive_incremental=False, adaptive_strategy="topk", adaptive_temperature=1.0, adaptive_seed=0,
+						anchor_selection="random"):
 	"""eval_method == "cur" of entry point B for one seed (splits.py:286-303 + 399-429).
 	rerank_pool "retrieved+anchors": every cell also reports, under POOL_PREFIX, the metrics of the pool anchor items + k_retvr NEW items (a
 	second retrieval per anchor count, with the anchor items excluded, at the largest k_retvr with k_retvr + n_anc <= pool_cell_limit).
 	adaptive_rounds N >= 2: every cell with k_retvr divisible by N also reports, under ADAPTIVE_PREFIX, the metrics of the adaptive search's
 	pool at the same budget (_sweep_adaptive_cells); 1 is today's code path.  adaptive_incremental: that search with AdaptiveSearcher(incremental=True);
 	the output keys are the same.  adaptive_strategy "softmax" (with adaptive_temperature, adaptive_seed): that search with sampled rounds
-	(DESIGN 4.4e), reported under ADAPTIVE_SOFTMAX_PREFIX instead."""
+	(DESIGN 4.4e), reported under ADAPTIVE_SOFTMAX_PREFIX instead.
+	anchor_selection "random": the reference's sorted(rng.choice(...)) per anchor count, today's code path and rng stream.  "pivoted" (DESIGN
+	4.4f): the anchor items of every count are the sorted first n_anc of ONE column-pivoted QR selection from A_train; `seed` is not used,
+	counts the selection cannot deliver are left out and logged once (_pivoted_anchor_counts), n_anc = 0 keeps its branch; the pool and
+	adaptive modes see only the anchor list."""
 	with_pool = _check_rerank_pool(rerank_pool)
+	if anchor_selection not in ANCHOR_SELECTIONS:
+		raise ValueError(f"anchor_selection = {anchor_selection} not supported (one of {', '.join(ANCHOR_SELECTIONS)})")
 	if adaptive_rounds < 1:
 		raise ValueError(f"adaptive_rounds = {adaptive_rounds}: need adaptive_rounds >= 1")
 	n_train, n_ent = A_train_dev.shape
@@ -325,8 +348,11 @@ def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None
 	exact = ops.rowwise_topk(A_test_dev, k_max)
 	rng = np.random.default_rng(seed=seed)                     # ONE stream consumed across the whole anchor-count loop
 	res = defaultdict(lambda: defaultdict(dict))
+	pivoted, left_out = _pivoted_anchor_counts(A_train_dev, anc_vals) if anchor_selection == "pivoted" else (None, ())
 	for j, n_anc in enumerate(anc_vals):
-		anc = _select(rng, n_ent, n_anc)
+		if n_anc in left_out:
+			continue
+		anc = _select(rng, n_ent, n_anc) if anchor_selection == "random" else (pivoted.sorted(n_anc) if n_anc else [])
 		if progress:
 			progress(j, len(anc_vals))
 		if n_anc == 0:

@@ -1392,6 +1392,47 @@ def exclusion_from_sorted_rows(ids_sorted, counts=None):
 	return Exclusion(off, ids_sorted.contiguous().view(-1), int(w) if Q else 0)
 
 
+# ------------------------------------------------------------------ anchor item selection
+def _select_pivoted_check(kq, m, k):
+	"""The limits of anncur_select_pivoted, as ValueErrors that name them (nothing needs a GPU here)."""
+	if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+		raise ValueError(f"select_pivoted: k must be an integer (got {k!r})")
+	if kq < 1 or kq > _lib.LSTSQ_MAX_KQ:
+		raise ValueError(f"select_pivoted: kq = {kq} anchor queries, outside 1..ANNCUR_LSTSQ_MAX_KQ = {_lib.LSTSQ_MAX_KQ}")
+	if m >= 1 << 31:
+		raise ValueError(f"select_pivoted: m = {m} items, need m < 2^31")
+	lim = min(kq, m, _lib.MAX_TOPK)
+	if k < 1 or k > lim:
+		raise ValueError(f"select_pivoted: k = {k} outside 1..min(kq, items, ANNCUR_MAX_TOPK) = min({kq}, {m}, {_lib.MAX_TOPK}) = {lim}")
+
+
+def select_pivoted_slice_items(dtype):
+	"""Items per slice of anncur_select_pivoted's step kernel for a torch dtype (what one workgroup covers per turn): for tests of its edges."""
+	return int(_lib.load().anncur_select_pivoted_slice_items(_DT[dtype]))
+
+
+@_on_device
+def select_pivoted(R, k):
+	"""Column-pivoted QR selection of k items from the anchor rows R [kq x m] (fp32 or bf16, rows may be padded; anncur_select_pivoted,
+	whose contract is in include/anncur_hip.h): -> (ids int32 [k] in SELECTION order, gains float64 [k] = the squared residual norm each had
+	when taken, n_sel int).  Positions >= n_sel hold (-1, 0.0): the selection stopped at the numerical rank (lstsq_rows' pivot rule).  The
+	first k' entries are the result for k' < k.  One grow-only workspace per device; the one host look is n_sel."""
+	if not torch.is_tensor(R) or R.dim() != 2:
+		raise ValueError("select_pivoted: R must be a 2-D tensor [kq x m]")
+	kq, m = R.shape
+	_select_pivoted_check(kq, m, k)
+	_dev(R)
+	dt = _dt(R)
+	R = _rowmajor(R)
+	lib = _lib.load()
+	ids = torch.empty((k,), dtype=torch.int32, device=R.device)
+	gains = torch.empty((k,), dtype=torch.float64, device=R.device)
+	n_sel = torch.empty((1,), dtype=torch.int32, device=R.device)
+	ws = _Workspace.get(lib.anncur_select_pivoted_workspace_bytes(m, kq, k), R.device)
+	check(lib.anncur_select_pivoted(_p(R), dt, _ld(R), kq, m, int(k), _p(ids), _p(gains), _p(n_sel), _p(ws), ws.numel(), _stream()), "select_pivoted")
+	return ids, gains, int(n_sel.item())
+
+
 @_on_device
 def gather_pairs(A, idx):
 	"""out[q, j] = A[q, idx[q, j]] as float32 [Q x n]; an id outside [0, I) (a hole) gives NaN (reference: ..._splits.py:91-96 reads

@@ -81,6 +81,8 @@ def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, de
 			pool_kw = dict(pool_kw, adaptive_temperature=args.adaptive_temperature)
 		if args.adaptive_seed != 0:
 			pool_kw = dict(pool_kw, adaptive_seed=args.adaptive_seed)
+	if args.anchor_selection != "random" and curr_method == "cur":
+		pool_kw = dict(pool_kw, anchor_selection=args.anchor_selection)   # (random = today's call; the other methods ignore the flag)
 	LOGGER.info(f"Computing approximate test mention-to-entity scores using method={curr_method}")
 	if curr_method == "cur":
 		A_train_dev = harness.to_device_matrix(A_train, device, args.dtype)
@@ -132,7 +134,7 @@ def run(args, device):
 		del arg_dict["adaptive_rounds"]   # (the same rule)
 	if not args.adaptive_incremental:
 		del arg_dict["adaptive_incremental"]   # (the same rule)
-	for key, default in (("adaptive_strategy", "topk"), ("adaptive_temperature", 1.0), ("adaptive_seed", 0)):
+	for key, default in (("adaptive_strategy", "topk"), ("adaptive_temperature", 1.0), ("adaptive_seed", 0), ("anchor_selection", "random")):
 		if getattr(args, key) == default:
 			del arg_dict[key]   # (the same rule)
 	eval_res["other_args"] = arg_dict
@@ -145,9 +147,19 @@ def run(args, device):
 	return res_file
 
 
+class _Parser(argparse.ArgumentParser):
+	"""argparse with the one rule that spans two flags: a deterministic anchor selection has no seeds to average over."""
+
+	def parse_args(self, args=None, namespace=None):
+		ns = super().parse_args(args, namespace)
+		if ns.anchor_selection == "pivoted" and ns.n_seeds > 1:
+			self.error(f"--anchor_selection pivoted is deterministic: --n_seeds {ns.n_seeds} would repeat one result (use --n_seeds 1)")
+		return ns
+
+
 def build_parser(worlds=None):
 	worlds = get_zeshel_world_info() if worlds is None else worlds
-	parser = argparse.ArgumentParser(description="Run eval for various retrieval methods wrt exact crossencoder scores using a fixed train/test "
+	parser = _Parser(description="Run eval for various retrieval methods wrt exact crossencoder scores using a fixed train/test "
 												 "split. This evaluation does not use ground-truth entity information into account")
 	parser.add_argument("--data_name", type=str, choices=[w for _, w in worlds], help="Dataset name")
 	parser.add_argument("--eval_method", type=str, choices=["cur", "bienc", "fixed_anc_ent", "fixed_anc_ent_cur", "tfidf"], help="Eval method")
@@ -194,6 +206,11 @@ def build_parser(worlds=None):
 	parser.add_argument("--adaptive_temperature", type=_temperature, default=1.0, help="temperature of --adaptive_strategy softmax (finite, > 0; default 1)")
 	parser.add_argument("--adaptive_seed", type=_seed, default=0,
 						help="seed of --adaptive_strategy softmax's noise, in [0, 2^64) (default 0); round r draws from stream r, a query from its row number")
+	parser.add_argument("--anchor_selection", type=str, default="random", choices=["random", "pivoted"],
+						help="eval_method cur: how the index picks its anchor items: random = sorted(rng.choice(...)) per anchor count and seed (the reference's choice; "
+							 "today's run and output); pivoted = the sorted first n_anc items of one column-pivoted QR selection from the training matrix, on the "
+							 "device (deterministic: needs --n_seeds 1; anchor counts above the number of training queries, ANNCUR_MAX_TOPK or the numerical rank "
+							 "are left out and logged)")
 	parser.add_argument("--compute_dtype", type=str, default="auto", choices=["auto", "fp32", "bf16", "bf16x3"],
 						help="arithmetic of the CUR retrieval: auto = by --dtype (fp32 matrix -> dense fp32 route, bf16 -> fused bf16 kernel); bf16x3 = for --dtype fp32: "
 							 "operands split into bf16 hi + lo parts on the fused kernel, candidates rescored in fp32 (the fp32 route's values, S_hat never written)")

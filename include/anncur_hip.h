@@ -469,6 +469,40 @@ int anncur_sample_topk(const float *S, int64_t lds, int64_t Q, int64_t I, float 
 int anncur_gumbel_noise(uint64_t seed, uint32_t stream_id, const int32_t *row_keys, int64_t Q, int64_t I, float *out, int64_t ldo,
                         void *stream);
 
+/* anchor item selection by column-pivoted QR ---------------------------------------------------------------------------
+ *   replaces sorted(rng.choice(n_ent, n_anc, replace=False)), the index' choice of its anchor items        ..._splits.py:295
+ * Column-subset selection for CUR: greedily the item whose score column has the largest component outside the span of those taken so far.
+ * R [kq x m] row-major, dtype ANNCUR_F32 or ANNCUR_BF16 (widened exactly), row pitch ldr >= m (the pad is never read): the layout CURApprox
+ * and CURRowIndex hold their rows in.  Outputs (device): out_ids int32[k] = the selected items in SELECTION ORDER, out_gain double[k] = the
+ * squared residual norm each had when it was taken, n_sel int32[1]; positions >= n_sel hold (-1, 0.0).  The selection is nested: the call
+ * with k' < k returns the first k' entries of the call with k, bit for bit.
+ * THE ALGORITHM (a contract; all state is fp64):
+ *   d_i = sum_a R[a,i]^2                                    fma in ascending a
+ *   step t:  p = argmax_i d_i over the items not yet taken, ties -> the smaller id; an item whose d_i is NaN or +-inf is never taken
+ *            STOP (this and every later step does nothing) if there is no such item, d_p <= 0 or d_p <= 2^-40 d_first, d_first = step 0's d_p
+ *            ids[t] = p, gain[t] = d_p
+ *            q_t = R[:, p] orthogonalised against q_0 .. q_{t-1} TWICE (classical Gram-Schmidt: the t coefficients <q_j, v> from one vector,
+ *                  then v -= sum_j coef_j q_j; the whole pass a second time), then divided by its norm
+ *            c_i = sum_a R[a,i] q_t[a]                      fma in ascending a
+ *            d_i <- fma(-c_i, c_i, d_i);   item p is marked (its d becomes NaN) and cannot be taken again
+ * Every sum runs in an order fixed by kq alone -- never by m, the launch shape or the dispatch order --, so a result is bit-reproducible from
+ * call to call.  (A residual column whose computed norm is 0 or not finite would stop the selection too; it cannot arise while d tracks the
+ * residual to kq 2^-53 d_first.)
+ * STOP RULE = anncur_lstsq_rows' PIVOT RULE, on purpose: d_p is the Cholesky pivot of R_S^T R_S that the item-side solve meets on the selected
+ * block in selection order, so a set that passes here is one that solve accepts (status 0).
+ * Two launches per step on `stream`, the kernel boundary the only synchronisation: a step kernel over slices of
+ * anncur_select_pivoted_slice_items(dtype) items (each step reads R once: k kq m elements in all) and a one-workgroup pick kernel; no host
+ * synchronisation; after a stop the remaining launches read the flag and return.  16-byte loads where R and ldr are multiples of 16 bytes,
+ * element loads otherwise (same result).
+ * Limits: 1 <= k <= min(kq, m, ANNCUR_MAX_TOPK), 1 <= kq <= ANNCUR_LSTSQ_MAX_KQ, m < 2^31; anything else is ANNCUR_E_INVALID and nothing is
+ * written.  Workspace: caller-owned, 256-byte aligned, anncur_select_pivoted_workspace_bytes(m, kq, k) bytes (0 outside the limits) = a
+ * header, d[m], the basis [k x kq], one (value, id) per step-kernel workgroup; nothing in it is pre-filled; missing, short or misaligned:
+ * ANNCUR_E_WORKSPACE. */
+size_t anncur_select_pivoted_workspace_bytes(int64_t m, int32_t kq, int32_t k);
+int32_t anncur_select_pivoted_slice_items(int dtype);   /* items per slice of the step kernel (0 for an unknown dtype): for tests of its edges */
+int anncur_select_pivoted(const void *R, int dtype, int64_t ldr, int32_t kq, int64_t m, int32_t k, int32_t *out_ids, double *out_gain,
+                          int32_t *n_sel, void *workspace, size_t workspace_bytes, void *stream);
+
 /* f3: IVF-flat inner-product index (the branch of build_flat_or_ivff_index above 11 000 vectors) -------------------------------
  *   faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT).train / .add / .search     models/nearest_nbr.py:40-52
  * FAISS is not vendored nor pinned by the reference (parity unpinned): restated from the published algorithm, judged on recall
