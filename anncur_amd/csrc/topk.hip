@@ -173,8 +173,11 @@ template <> struct ScanPre<float> {  // fp32 rows: plain float compares
 	}
 	__device__ __forceinline__ uint32_t word_hits(uint32_t yw) const { return (all || __uint_as_float(yw) > pre) ? 1u : 0u; }  // one element per word
 	__device__ __forceinline__ bool elem_hit(uint32_t hw, int) const { return hw != 0u; }
-	static __device__ __forceinline__ uint32_t group_max_key(const u32x4 &c) {  // NaN-free maximum as a sortable key
-		return f32_sortable(fmaxf(fmaxf(fmaxf(__uint_as_float(c[0]), __uint_as_float(c[1])), __uint_as_float(c[2])), __uint_as_float(c[3])));
+	static __device__ __forceinline__ uint32_t group_max_key(const u32x4 &c) {  // maximum of the vector's numbers as a sortable key
+		// fmaxf skips a NaN next to a number, but four NaNs give NaN, and a NaN with the sign clear would key above every number:
+		// key 0 instead (never the bound), as in the bf16 version
+		const float m = fmaxf(fmaxf(fmaxf(__uint_as_float(c[0]), __uint_as_float(c[1])), __uint_as_float(c[2])), __uint_as_float(c[3]));
+		return m == m ? f32_sortable(m) : 0u;
 	}
 };
 template <> struct ScanPre<uint16_t> {  // bf16 rows: packed 16-bit integer compares on y = x ^ M
