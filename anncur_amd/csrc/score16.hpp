@@ -62,6 +62,38 @@ struct Fused16Cfg {
 	static_assert(LADDER_LEVELS == 8, "two 128-bit reads per query; eight 16-bit fields in four counter words");
 	static constexpr int BQ = 64 * NW;
 };
+// A-fragment addresses of the tile loop: NA base registers + immediates instead of one register per stagger step.
+// Step s = (k-step s >> 1, item half s & 1) reads row 16 (s & 1) + c16, 16-byte chunk 4 (s >> 1) + g4 of the swizzled tile image (c16 = lane & 15,
+// g4 = lane >> 4).  The swizzle term of that row is the same for both item halves (row & 15 = c16; at Kp = 64, (row >> 1) & 7 = (c16 >> 1) & 7: the
+// half's 16 >> 1 = 8 falls out of the mask), so the half only adds its rows' bytes; and the XOR touches the chunk's low four bits only, so with
+// 32 chunks per row (Kp = 256) k-steps ks and ks + 4 are 16 chunks = 256 bytes apart.  Hence
+//   address(s) = base[(s >> 1) % NA] + ((s >> 1) / NA) * 256 + (s & 1) * 16 rows,   base[j] = the address of row c16, chunk 4 j + g4:
+// four registers live across the tile loop at Kp = 256 instead of sixteen.  That is what takes score16_kernel<256, 4> from 252 VGPRs (256 allocated:
+// two workgroups per CU own the whole register file) to 240, so that a small kernel of another queue fits beside it; scripts/check_kernel_resources.py
+// holds the build to it.  The identity is proven below for every lane and step.
+template <int KP>
+struct Frag16Addr {
+	static constexpr int K = KP / 16, CPR = KP / 8;
+	static constexpr int NA = K / 2 < 4 ? K / 2 : 4;     // base registers
+	static constexpr int reg(int s) { return (s >> 1) % NA; }
+	static constexpr int imm(int s) { return ((s >> 1) / NA) * 256 + (s & 1) * 16 * CPR * 16; }
+	static constexpr uint32_t base(int c16, int g4, int j) { return (uint32_t)(c16 * CPR + swz<CPR>(c16, 4 * j + g4)) * 16u; }
+	// the address as the kernel computed it per step before (one register each)
+	static constexpr uint32_t direct(int c16, int g4, int s) {
+		const int row = 16 * (s & 1) + c16;
+		return (uint32_t)(row * CPR + swz<CPR>(row, 4 * (s >> 1) + g4)) * 16u;
+	}
+	static constexpr bool proven() {
+		for (int lane = 0; lane < 64; ++lane)
+			for (int s = 0; s < K; ++s)
+				if (direct(lane & 15, lane >> 4, s) != base(lane & 15, lane >> 4, reg(s)) + (uint32_t)imm(s)) return false;
+		return true;
+	}
+};
+static_assert(Frag16Addr<64>::proven() && Frag16Addr<128>::proven() && Frag16Addr<256>::proven(),
+			  "fragment address = base register + immediate, for all 64 lanes, every step, 8 / 16 / 32 chunks per row");
+static_assert(Frag16Addr<64>::NA == 2 && Frag16Addr<128>::NA == 4 && Frag16Addr<256>::NA == 4, "base registers");
+
 #ifndef ANNCUR_LADDER_PERIOD
 #define ANNCUR_LADDER_PERIOD 16
 #endif
@@ -179,16 +211,19 @@ __device__ __forceinline__ void ladder_refresh(uint32_t lcnt_lane, uint32_t lvl_
 
 // One 32-item tile.  accP = sub-tiles {2,3} of the previous tile (filtered here, then replaced by this tile's).
 template <int KP, int CUR>
-__device__ __forceinline__ void stagger16_tile(const uint32_t (&aoff)[Fused16Cfg<KP>::K], const bf16x8 (&xb)[4][Fused16Cfg<KP>::KS32], f32x4 (&accP)[2][2],
+__device__ __forceinline__ void stagger16_tile(const uint32_t (&aoff)[Frag16Addr<KP>::NA], const bf16x8 (&xb)[4][Fused16Cfg<KP>::KS32], f32x4 (&accP)[2][2],
 												const float (&tau)[4], const float (&tau_prev)[2], uint32_t item0, uint32_t item0_prev, const WaveQueue &w,
 												uint32_t &fill) {
 	using C = Fused16Cfg<KP>;
 	constexpr int K = C::K, AR = 5, DIST = 3, OFF = CUR * C::TILE_BYTES;
 	constexpr int EPS = 16 / K > 0 ? 16 / K : 1;  // filter elements per step (Kp = 64: 4, 128: 2, 256: 1)
 	static_assert(K <= 16 && 2 * K >= DIST, "staggered path: 4..16 steps per half");
+	using FA = Frag16Addr<KP>;
 	u32x4 ring[AR];
+	// fragment of step s: base register + immediate (Frag16Addr)
+#define F16_READ(slot, s) lds_read_frag_at(ring[slot], aoff[FA::reg((s) % K)], OFF + FA::imm((s) % K))
 #pragma unroll
-	for (int i = 0; i < DIST; ++i) lds_read_frag<OFF>(ring[i], aoff[i % K]);
+	for (int i = 0; i < DIST; ++i) F16_READ(i, i);
 	f32x4 accA[2][2], accB[2][2];
 #pragma unroll
 	for (int ih = 0; ih < 2; ++ih)
@@ -202,7 +237,7 @@ __device__ __forceinline__ void stagger16_tile(const uint32_t (&aoff)[Fused16Cfg
 #pragma unroll
 	for (int g = 0; g < 2 * K; ++g) {
 		const int nxt = g + DIST;
-		if (nxt < 2 * K) lds_read_frag<OFF>(ring[nxt % AR], aoff[nxt % K]);
+		if (nxt < 2 * K) F16_READ(nxt % AR, nxt);
 #if defined(__HIP_DEVICE_COMPILE__)
 		if (g >= 1) asm volatile("" ::"v"(ring[(g - 1) % AR]));
 #endif
@@ -230,6 +265,7 @@ __device__ __forceinline__ void stagger16_tile(const uint32_t (&aoff)[Fused16Cfg
 	for (int ih = 0; ih < 2; ++ih)
 #pragma unroll
 		for (int q = 0; q < 2; ++q) accP[ih][q] = accB[ih][q];
+#undef F16_READ
 }
 
 #define S16_SLICED (p.sliced)
@@ -364,13 +400,11 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 		for (int q = 0; q < 2; ++q) accP[ih][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
 	float tau_prev[2] = {INFINITY, INFINITY};  // no previous tile yet: the filter of accP never fires
 	uint32_t item0_prev = 0;
-	// A fragment of step s = (k-step s >> 1, item half s & 1): row 16 (s & 1) + (lane & 15), 16-byte chunk 4 (s >> 1) + (lane >> 4)
-	uint32_t aoff[K];
+	// A fragment of step s = (k-step s >> 1, item half s & 1): row 16 (s & 1) + (lane & 15), 16-byte chunk 4 (s >> 1) + (lane >> 4) -- as
+	// base register (s >> 1) % NA plus an immediate (Frag16Addr)
+	uint32_t aoff[Frag16Addr<KP>::NA];
 #pragma unroll
-	for (int s = 0; s < K; ++s) {
-		const int row = 16 * (s & 1) + c16;
-		aoff[s] = lds_addr(smem) + (uint32_t)(row * CPR + swz<CPR>(row, 4 * (s >> 1) + g4)) * 16u;
-	}
+	for (int j = 0; j < Frag16Addr<KP>::NA; ++j) aoff[j] = lds_addr(smem) + Frag16Addr<KP>::base(c16, g4, j);
 	const uint32_t lane_code = (uint32_t)c16 << WQ_ITEM_BITS;
 	__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): stagger16_tile() counts LDS reads
 	float tau_hi[2] = {tau[2], tau[3]};

@@ -69,7 +69,7 @@ struct FusedCfg {
 };
 
 template <int CPR>
-__device__ __forceinline__ int swz(int row, int c) {
+__host__ __device__ __forceinline__ constexpr int swz(int row, int c) {   // (constexpr: score16.hpp proves its fragment addresses with static_asserts)
 	if (CPR >= 16) return c ^ (row & 15);
 	return c ^ ((row >> 1) & 7);  // CPR == 8 (Kp = 64): 128-byte rows, two rows per 256-byte bank line
 }

@@ -1,4 +1,4 @@
-"""Shared helpers of the static ISA checks (check_mfma_hazards.py, check_lds_hazards.py): extract the gfx950 code objects of a built
+"""Shared helpers of the static ISA checks (check_mfma_hazards.py, check_lds_hazards.py, check_kernel_resources.py): extract the gfx950 code objects of a built
 library with llvm-objdump --offloading, disassemble them, split the listing into functions of (address, instruction, raw tail)."""
 import os, re, shutil, subprocess, sys, tempfile
 
@@ -7,16 +7,26 @@ SMEM = re.compile(r"^\s*(s_load_|s_buffer_load_|s_memtime|s_memrealtime|s_scratc
 KERNELS = re.compile(r"ivf_tile128_kernel|score_kernel|score16_kernel|prepass16_kernel|evalf_kernel|error_lds_kernel|scoreq16_kernel|wide_kernel|error_kernel")
 
 
+def _code_objects(lib: str, tmp: str):
+	"""Unbundle the library's gfx950 code objects into tmp; their file names, sorted."""
+	shutil.copy(lib, os.path.join(tmp, "lib.so"))
+	subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", "lib.so"], cwd=tmp, check=True, capture_output=True)
+	return [f for f in sorted(os.listdir(tmp)) if "amdgcn" in f and os.path.getsize(os.path.join(tmp, f)) > 0]
+
+
 def disassemble(lib: str):
 	tmp = tempfile.mkdtemp(prefix="anncur_co_")
 	try:
-		shutil.copy(lib, os.path.join(tmp, "lib.so"))
-		subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", "lib.so"], cwd=tmp, check=True, capture_output=True)
-		out = []
-		for f in sorted(os.listdir(tmp)):
-			if "amdgcn" in f and os.path.getsize(os.path.join(tmp, f)) > 0:
-				out.append(subprocess.run([f"{LLVM}/llvm-objdump", "-d", f], cwd=tmp, check=True, capture_output=True, text=True).stdout)
-		return out
+		return [subprocess.run([f"{LLVM}/llvm-objdump", "-d", f], cwd=tmp, check=True, capture_output=True, text=True).stdout for f in _code_objects(lib, tmp)]
+	finally:
+		shutil.rmtree(tmp, ignore_errors=True)
+
+
+def kernel_notes(lib: str):
+	"""The metadata notes (llvm-readelf --notes: the amdhsa.kernels list as text) of every code object of the library."""
+	tmp = tempfile.mkdtemp(prefix="anncur_co_")
+	try:
+		return [subprocess.run([f"{LLVM}/llvm-readelf", "--notes", f], cwd=tmp, check=True, capture_output=True, text=True).stdout for f in _code_objects(lib, tmp)]
 	finally:
 		shutil.rmtree(tmp, ignore_errors=True)
 
