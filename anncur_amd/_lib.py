@@ -86,6 +86,7 @@ SIGNATURES = {
 									c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
 	"anncur_lstsq_extend_timed": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, ctypes.c_double, c_void_p,
 										  c_int64, c_void_p, c_void_p, c_size_t, c_void_p, POINTER(ctypes.c_float)]),
+	"anncur_lstsq_seed_shared": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int32, c_int64, c_int32, ctypes.c_double, c_void_p, c_size_t, c_void_p]),
 	"anncur_sort_id_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 	"anncur_sample_topk": (c_int, [c_void_p, c_int64, c_int64, c_int64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
 								   c_void_p, c_void_p, c_void_p]),

@@ -18,6 +18,11 @@
 // pitch, the places of z and y and the first row / panel to compute as runtime arguments; anncur_lstsq_rows passes "pitch gp, z and
 // y in row gp, start at 0", the extension restarts at panel p0 = n_old / 16.  Every entry of G, L, z and y goes through the same
 // machine code and the same chain of fp64 operations on either way, so the two results are equal bit for bit.
+//
+// anncur_lstsq_seed_shared starts such a state from a prefix of ids that every query shares (the adaptive search's anchor items): the
+// Gram and factor kernels run ONCE, for one query, into slot 0 -- without a right-hand side, L does not depend on one --, and
+// lstsq_seed_broadcast_kernel copies L and the header to the other slots.  z is the one per-query part of the prefix; the first
+// extension computes it inside the factor kernel (the HDR_ZROWS rule there), so the result stays bit-equal.
 #include "common.hpp"
 
 namespace {
@@ -29,8 +34,9 @@ constexpr int GPITCH = 80;        // doubles per LDS row (gemm64.hip: the four k
 constexpr int PB = 16;            // panel width of the factorisation = the MFMA tile
 constexpr int PPITCH = 17;        // doubles per row of the LDS panel: a thread per row walks its 16 entries without bank conflicts
 constexpr int MAXBLK = 9;         // row blocks per wave and panel: ceil((512 / 16 + 1) / 4)
-// header of a persistent state (doubles): the largest Gram diagonal so far, the smallest accepted pivot so far, the sticky status
-constexpr int HDR_DMAX = 0, HDR_PMIN = 1, HDR_STATUS = 2, HDR_DOUBLES = 16;
+// header of a persistent state (doubles): the largest Gram diagonal so far, the smallest accepted pivot so far, the sticky status,
+// the number of leading entries of z that are valid (0 after anncur_lstsq_seed_shared, n_new after a successful factor call)
+constexpr int HDR_DMAX = 0, HDR_PMIN = 1, HDR_STATUS = 2, HDR_ZROWS = 3, HDR_DOUBLES = 16;
 
 __device__ __forceinline__ float nan_f32() { return __uint_as_float(0x7fc00000u); }
 
@@ -169,6 +175,15 @@ __global__ __launch_bounds__(256) void lstsq_matvec_kernel(const float *__restri
 // same left-looking sum over k < p) and solved against the STORED diagonal block; z keeps its entries below r0.  From p0 on the loop
 // is the full one.  The header carries what the overwritten rows no longer show: the largest diagonal of G (the threshold only
 // grows, so the smallest accepted pivot so far is tested against the new one) and the status, which is sticky.
+// A SEEDED state (anncur_lstsq_seed_shared) holds L of the shared prefix but no z: its header says HDR_ZROWS = 0.  A restart that finds
+// fewer valid entries of z than r0 (`zfull`, the same header word in every thread) carries the right-hand side through the old panels
+// as well: rhs is initialised from C at EVERY position, the old panels' block range includes the right-hand-side block (b1 = nb) and
+// their per-row solve against the stored diagonal block includes the right-hand-side row.  For that row this is the chain of the fresh
+// path, instruction for instruction: the same MFMA accumulation over k < c0, then the same thread-per-row solve against the same Ld
+// values (stored doubles instead of the ones just factored: equal bits).  It is this one kernel, not a copy of its source, so no
+// second compilation can contract the s -= x L chain differently, and z -- hence W -- equals anncur_lstsq_rows' bit for bit.
+// C == nullptr (item side; the seed's own call, Q = 1): no right-hand side at all.  L does not depend on one, so the right-hand-side
+// block, row and the back substitution are left out (wave-uniformly), z, y, W and status are not touched and HDR_ZROWS becomes 0.
 template <int SIDE>
 __global__ __launch_bounds__(256) void lstsq_factor_kernel(const int32_t *__restrict__ ids, int64_t ld_ids, int64_t m_items, const float *__restrict__ C,
 																int64_t ldc, int n, int kq, int g, int gp, int pitch, int p0, int n_old, double ridge, double *ws,
@@ -188,6 +203,8 @@ __global__ __launch_bounds__(256) void lstsq_factor_kernel(const int32_t *__rest
 	const int nb = gp / PB, r0 = p0 * PB;
 	auto at = [&](int row) -> double * { return row < gp ? G + (int64_t)row * pitch : rhs; };   // row gp = the right-hand side
 
+	const bool norhs = SIDE == 0 && C == nullptr;
+	bool zfull = false;
 	double dmax = 0.0, pmin = INFINITY;
 	if (hdr && n_old > 0) {   // (n_old = 0 initialises the state: nothing of it is read)
 		if (hdr[HDR_STATUS] != 0.0) {   // (the same word in every thread: a uniform exit)
@@ -196,6 +213,7 @@ __global__ __launch_bounds__(256) void lstsq_factor_kernel(const int32_t *__rest
 		}
 		dmax = hdr[HDR_DMAX];
 		pmin = hdr[HDR_PMIN];
+		zfull = hdr[HDR_ZROWS] < (double)r0;   // z is not valid below r0: a seeded state
 	}
 	for (int i = tid; i < gp; i += 256) {
 		bool pad = i >= g;
@@ -204,8 +222,8 @@ __global__ __launch_bounds__(256) void lstsq_factor_kernel(const int32_t *__rest
 			pad = id < 0 || id >= m_items;
 		}
 		padf[i] = pad ? 1 : 0;
-		if (i < r0) continue;   // (z and L's diagonal: kept)
-		if (SIDE == 0) rhs[i] = pad ? 0.0 : (double)C[q * ldc + i];
+		if (SIDE == 0 && !norhs && (i >= r0 || zfull)) rhs[i] = pad ? 0.0 : (double)C[q * ldc + i];
+		if (i < r0) continue;   // (L's diagonal, and z unless zfull: kept)
 		if (!pad) dmax = fmax(dmax, G[(int64_t)i * pitch + i]);   // (fmax drops a NaN: the pivot test below catches it)
 	}
 	red[tid] = dmax;
@@ -221,7 +239,8 @@ __global__ __launch_bounds__(256) void lstsq_factor_kernel(const int32_t *__rest
 	for (int p = 0; p < nb && !bad; ++p) {
 		const int c0 = p * PB;
 		const bool old = p < p0;
-		const int b0 = old ? p0 : p, b1 = old ? nb - 1 : nb;   // (the right-hand side, block nb, restarts at p0)
+		const bool with_rhs = !norhs && (!old || zfull);       // (the right-hand side, block nb, restarts at p0 unless zfull)
+		const int b0 = old ? p0 : p, b1 = with_rhs ? nb : nb - 1;
 		f64x4 acc[MAXBLK];
 #pragma unroll
 		for (int i = 0; i < MAXBLK; ++i) acc[i] = (f64x4){0.0, 0.0, 0.0, 0.0};
@@ -277,8 +296,8 @@ __global__ __launch_bounds__(256) void lstsq_factor_kernel(const int32_t *__rest
 			const int i = tid >> 4, k = tid & 15;
 			if (i >= k) G[(int64_t)(c0 + i) * pitch + c0 + k] = Ld[i * PPITCH + k];
 		}
-		// rows below the block, the right-hand-side row (il = gp - c0) the last; under an old panel the rows from r0 down, without it
-		for (int il = (old ? r0 - c0 : PB) + tid; il <= (old ? gp - 1 - c0 : gp - c0); il += 256) {
+		// rows below the block, the right-hand-side row (il = gp - c0) the last; under an old panel the rows from r0 down, without it unless zfull
+		for (int il = (old ? r0 - c0 : PB) + tid; il <= (with_rhs ? gp - c0 : gp - 1 - c0); il += 256) {
 			double x[PB];
 #pragma unroll
 			for (int j = 0; j < PB; ++j) {
@@ -294,7 +313,7 @@ __global__ __launch_bounds__(256) void lstsq_factor_kernel(const int32_t *__rest
 	}
 	if (bad) {
 		if (tid == 0) {
-			status[q] = 1;
+			if (!norhs) status[q] = 1;
 			if (hdr) hdr[HDR_STATUS] = 1.0;
 		}
 		if (SIDE == 1)
@@ -302,6 +321,15 @@ __global__ __launch_bounds__(256) void lstsq_factor_kernel(const int32_t *__rest
 		return;
 	}
 
+	if (norhs) {   // the seed: L and the header, nothing else
+		if (tid == 0 && hdr) {
+			hdr[HDR_DMAX] = dtot;
+			hdr[HDR_PMIN] = pmin;
+			hdr[HDR_STATUS] = 0.0;
+			hdr[HDR_ZROWS] = 0.0;
+		}
+		return;
+	}
 	// back substitution L^T y = z (z = row gp), panel by panel from the last
 	for (int p = nb - 1; p >= 0; --p) {
 		const int c0 = p * PB;
@@ -340,8 +368,30 @@ __global__ __launch_bounds__(256) void lstsq_factor_kernel(const int32_t *__rest
 			hdr[HDR_DMAX] = dtot;
 			hdr[HDR_PMIN] = pmin;
 			hdr[HDR_STATUS] = 0.0;
+			hdr[HDR_ZROWS] = (double)n;
 		}
 	}
+}
+
+// anncur_lstsq_seed_shared, second step: the factor of the shared prefix, which slot 0 of the state holds, goes to the slots 1 .. Q-1.
+// Workgroup (q, rb) copies the 16-row block rb of slot 0 up to and including its diagonal block -- rows [16 rb, 16 rb + 16), columns
+// [0, 16 rb + 16): the lower block triangle is all that the factor kernel reads of stored rows -- and, for rb = 0, the four header
+// words that are in use.  16-byte vectors (rows start on 128-byte boundaries, a block row is a whole number of vectors), the tail of
+// the loop by predication; no LDS, no barrier, and no workgroup waits on another.  nrb = ceil16(n_sh) / 16 row blocks per query.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void lstsq_seed_broadcast_kernel(double *ws, int64_t ws_stride, int64_t hdr_off, int pitch, int nrb) {
+	const int tid = threadIdx.x;
+	const int64_t q = 1 + blockIdx.x / nrb;
+	const int rb = (int)(blockIdx.x % nrb);
+	const double *src = ws;
+	double *dst = ws + q * ws_stride;
+	const int vpr = (rb + 1) * (PB / 2), nvec = PB * vpr;   // vectors per row of this block, and in all
+#pragma unroll 4
+	for (int v = tid; v < nvec; v += 256) {
+		const int64_t off = (int64_t)(rb * PB + v / vpr) * pitch + 2 * (v % vpr);
+		*(u32x4 *)(dst + off) = *(const u32x4 *)(src + off);
+	}
+	if (rb == 0 && tid < 2) *(u32x4 *)(dst + hdr_off + 2 * tid) = *(const u32x4 *)(src + hdr_off + 2 * tid);
 }
 
 // The four HIP events of a _timed call: destroyed on every way out of the caller, an error return included.
@@ -485,7 +535,48 @@ int lstsq_extend(const float *Rt, int64_t ldr, int64_t m_items, int32_t kq, cons
 	return ms3 ? evs.elapsed(ms3) : ANNCUR_OK;
 }
 
+// The shared prefix factored ONCE (the Gram and factor kernels of every other call, Q = 1, on shared_ids as the one id row, into slot 0,
+// without a right-hand side), then copied to every other slot.
+int lstsq_seed_shared(const float *Rt, int64_t ldr, int64_t m_items, int32_t kq, const int32_t *shared_ids, int32_t n_sh, int64_t Q, int32_t cap, double ridge,
+					  void *state, size_t state_bytes, void *stream) {
+	ANNCUR_REQUIRE(lstsq_state_ok(Q, cap) && kq >= 1 && kq <= ANNCUR_LSTSQ_MAX_KQ, ANNCUR_E_INVALID,
+				   "lstsq_seed_shared: need Q >= 0, 1 <= cap <= %d and 1 <= kq <= %d (got Q = %lld, cap = %d, kq = %d)", ANNCUR_LSTSQ_MAX_G, ANNCUR_LSTSQ_MAX_KQ,
+				   (long long)Q, (int)cap, (int)kq);
+	ANNCUR_REQUIRE(n_sh >= 1 && n_sh <= cap && n_sh <= kq, ANNCUR_E_INVALID, "lstsq_seed_shared: need 1 <= n_sh <= min(cap, kq) (got n_sh = %d, cap = %d, kq = %d)",
+				   (int)n_sh, (int)cap, (int)kq);
+	ANNCUR_REQUIRE(ridge >= 0.0, ANNCUR_E_INVALID, "lstsq_seed_shared: need ridge >= 0 (got %g)", ridge);   // (a NaN fails too)
+	ANNCUR_REQUIRE(m_items >= 1 && ldr >= kq, ANNCUR_E_INVALID, "lstsq_seed_shared: need m >= 1 and the row pitch ldr >= kq");
+	if (Q == 0) return ANNCUR_OK;
+	ANNCUR_REQUIRE(Rt && shared_ids, ANNCUR_E_INVALID, "lstsq_seed_shared: null pointer");
+	const size_t need = anncur_lstsq_state_bytes(Q, cap);
+	ANNCUR_REQUIRE(state && state_bytes >= need && ((uintptr_t)state & 255) == 0, ANNCUR_E_WORKSPACE,
+				   "lstsq_seed_shared: state missing, misaligned (256 bytes) or too small (%zu < %zu bytes)", state_bytes, need);
+	const int capp = (cap + PB - 1) / PB * PB, gp = (n_sh + PB - 1) / PB * PB, nrb = gp / PB;
+	const int nt = (gp + GT - 1) / GT, ntp = nt * (nt + 1) / 2;
+	ANNCUR_REQUIRE((Q - 1) * nrb < (int64_t)0x7fffffff, ANNCUR_E_INVALID, "lstsq_seed_shared: Q = %lld is too many queries for one launch at this size: split them",
+				   (long long)Q);
+	const int64_t stride = lstsq_state_stride(capp), z_off = (int64_t)capp * capp, y_off = z_off + capp, hdr_off = y_off + capp;
+	const size_t lds = lstsq_factor_lds(gp);
+	const int rc = anncur_ensure_dyn_lds((const void *)lstsq_factor_kernel<0>, (int)lds);
+	if (rc != ANNCUR_OK) return rc;
+	hipStream_t st = (hipStream_t)stream;
+	double *ws = (double *)state;
+	hipLaunchKernelGGL((lstsq_gram_kernel<0>), dim3((unsigned)ntp), dim3(256), 0, st, Rt, ldr, m_items, shared_ids, (int64_t)n_sh, (int)n_sh, (int)kq, gp, capp, 0, 0, ntp,
+					   ws, stride, (int64_t)-1);
+	hipLaunchKernelGGL((lstsq_factor_kernel<0>), dim3(1), dim3(256), lds, st, shared_ids, (int64_t)n_sh, m_items, (const float *)nullptr, (int64_t)0, (int)n_sh, (int)kq,
+					   (int)n_sh, gp, capp, 0, 0, ridge, ws, stride, z_off, y_off, hdr_off, (float *)nullptr, (int64_t)0, (int32_t *)nullptr);
+	if (Q > 1)
+		hipLaunchKernelGGL(lstsq_seed_broadcast_kernel, dim3((unsigned)((Q - 1) * nrb)), dim3(256), 0, st, ws, stride, hdr_off, capp, nrb);
+	ANNCUR_LAUNCH_OK();
+	return ANNCUR_OK;
+}
+
 }  // namespace
+
+extern "C" int anncur_lstsq_seed_shared(const float *Rt, int64_t ldr, int64_t m, int32_t kq, const int32_t *shared_ids, int32_t n_sh, int64_t Q, int32_t cap,
+										 double ridge, void *state, size_t state_bytes, void *stream) {
+	return lstsq_seed_shared(Rt, ldr, m, kq, shared_ids, n_sh, Q, cap, ridge, state, state_bytes, stream);
+}
 
 extern "C" size_t anncur_lstsq_state_bytes(int64_t Q, int32_t cap) {
 	if (!lstsq_state_ok(Q, cap)) return 0;

@@ -1271,6 +1271,7 @@ class LstsqState(object):
 	workspace, which other calls overwrite), and extend() pays for the appended positions only.  Rt [m x kq] fp32, Q queries, at most
 	cap <= ANNCUR_LSTSQ_MAX_G positions per query; ridge is fixed for the state's life.  After every extend(ids, C) the result equals
 	lstsq_rows(Rt, ids, C, ridge) bit for bit, status included; a query that failed once (status 1, NaN row) stays failed.
+	seed_shared(shared_ids), on a fresh state, factors a prefix that all queries share once instead of once per query (same results).
 	.n = the positions absorbed so far, .cap.  Every limit is a ValueError that names it, raised before any launch."""
 
 	def __init__(self, Rt, Q, cap, ridge=0.0, max_bytes=LSTSQ_STATE_LIMIT_BYTES):
@@ -1298,6 +1299,50 @@ class LstsqState(object):
 			self._buf = torch.empty(self.nbytes + 256, dtype=torch.uint8, device=self.Rt.device)
 		off = (-self._buf.data_ptr()) % 256
 		return self._buf[off:off + self.nbytes]
+
+	def seed_shared(self, shared_ids):
+		"""Start the state from a prefix that EVERY query's rows begin with (anncur_lstsq_seed_shared; the adaptive search's anchor items):
+		the prefix is factored once, for one query, and copied to the others, so the first extend() pays for the positions after it only.
+		shared_ids: a host list, numpy array or int32 tensor of n_sh ids, in the order in which the rows hold them (the caller's contract, as
+		for extend).  Afterwards .n = n_sh; every extend() returns what it returns on an unseeded state, bit for bit.  Duplicates are not an
+		error: they are rank deficiency and fail every query through the status of the first extend.  ValueError, before any launch: the
+		state has absorbed something already, n_sh outside 1..min(cap, kq), an id outside [0, m) (ids given on the GPU are taken as they
+		are: checking them would cost a synchronisation).  No host synchronisation."""
+		if self.n != 0:
+			raise ValueError(f"LstsqState.seed_shared: {self.n} positions are absorbed already: a state is seeded before its first extend (.n == 0)")
+		on_gpu = torch.is_tensor(shared_ids) and shared_ids.is_cuda
+		if on_gpu:
+			if shared_ids.dim() != 1 or shared_ids.dtype != torch.int32:
+				raise ValueError(f"LstsqState.seed_shared: shared_ids on the GPU must be a flat int32 tensor (got {shared_ids.dtype}, {shared_ids.dim()}-D)")
+			n_sh = shared_ids.shape[0]
+		else:
+			a = np.asarray(shared_ids.detach().numpy() if torch.is_tensor(shared_ids) else shared_ids)
+			if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+				raise ValueError("LstsqState.seed_shared: shared_ids must be a flat list of integer item ids")
+			a = a.astype(np.int64)
+			n_sh = int(a.size)
+		if n_sh < 1 or n_sh > min(self.cap, self.kq):
+			raise ValueError(f"LstsqState.seed_shared: n_sh = {n_sh} shared ids, outside 1..min(cap, kq) = min({self.cap}, {self.kq}) = {min(self.cap, self.kq)}")
+		m = self.Rt.shape[0]
+		if not on_gpu and (int(a.min()) < 0 or int(a.max()) >= m):
+			bad = int(a.min()) if int(a.min()) < 0 else int(a.max())
+			raise ValueError(f"LstsqState.seed_shared: id {bad} outside [0, m) = [0, {m}): a shared id names an item (holes belong to the appended positions)")
+		_dev(self.Rt)
+		if on_gpu and shared_ids.device != self.Rt.device:
+			raise _lib.AnncurHipError(f"LstsqState.seed_shared: operands live on different devices (Rt on {self.Rt.device}, shared_ids on {shared_ids.device})")
+		ids = shared_ids.contiguous() if on_gpu else torch.from_numpy(a.astype(np.int32)).to(self.Rt.device)
+		self._seed(ids, n_sh)
+
+	@_on_device
+	def _seed(self, ids, n_sh):
+		Rt = _rowmajor(self.Rt)
+		if self.Q:
+			if (self.Q - 1) * -(-n_sh // 16) >= 0x7fffffff:
+				raise ValueError(f"LstsqState.seed_shared: Q = {self.Q} queries are too many for one launch at this size: search the queries in batches")
+			st = self._state()
+			check(_lib.load().anncur_lstsq_seed_shared(_p(Rt), _ld(Rt), Rt.shape[0], self.kq, _p(ids), n_sh, self.Q, self.cap, self.ridge, _p(st), st.numel(),
+													   _stream()), "lstsq_seed_shared")
+		self.n = n_sh
 
 	def extend(self, ids, C, out=None, timings=None):
 		"""ids int32 / C fp32 [Q x n], n > .n: the FULL rows in insertion order, whose first .n positions are what the last call saw (the

@@ -139,6 +139,9 @@ class AdaptiveSearcher(object):
 	bit for bit, ops.lstsq_rows on the same ordered rows; against incremental=False the unknowns are permuted, so the weights agree to
 	rounding only.  The id-sorted copy is kept for the exclusion alone.  A failed query stays failed in the state: it takes the host
 	fallback in every later round and is counted once.
+	seed_shared=True (the default; only read with incremental=True): every query's rows begin with the same kc anchor items, so the state is
+	seeded with them (ops.LstsqState.seed_shared: their kc x kc block is factored once, not once per query) and round 2 extends it by
+	k_step positions like every later round.  Bit-equal to seed_shared=False, which absorbs kc + k_step positions per query in round 2.
 
 	strategy: how a round picks its k_step new items (the paper names both).  "topk" (default): the k_step best of s_hat_q outside S_q --
 	everything above, bit for bit.  "softmax": k_step items drawn without replacement with probability proportional to
@@ -149,12 +152,13 @@ class AdaptiveSearcher(object):
 	CrossEncoderSearcher.search.  The exclusion, the limits (adaptive_limits; the sampler takes k_step directly, so no k + e retrieval and no
 	ops.filtered_k), the solves and the final re-rank are the same; it works with and without incremental=True."""
 
-	def __init__(self, index, scorer, ridge=0.0, incremental=False, strategy="topk", temperature=1.0, seed=0):
+	def __init__(self, index, scorer, ridge=0.0, incremental=False, strategy="topk", temperature=1.0, seed=0, seed_shared=True):
 		if strategy not in STRATEGIES:
 			raise ValueError(f"AdaptiveSearcher: strategy = {strategy!r}, need one of {STRATEGIES}")
 		self.strategy, self.temperature = strategy, ops._temperature_arg(temperature, "AdaptiveSearcher")
 		self.seed = ops._noise_args(seed, 0, "AdaptiveSearcher")[0]
 		self.index, self.scorer, self.ridge, self.incremental = index, scorer, float(ridge), bool(incremental)
+		self.seed_shared = bool(seed_shared)
 		if not self.ridge >= 0.0:
 			raise ValueError(f"AdaptiveSearcher: ridge = {ridge}, need ridge >= 0")
 		dev = index.R.device
@@ -221,6 +225,8 @@ class AdaptiveSearcher(object):
 		if self.incremental:
 			O_ids, O_sc = S_ids.contiguous(), torch.cat([Xf, scores], dim=1)   # insertion order: what the state absorbs
 			state = ops.LstsqState(Rt, Q, self.kc + (n_rounds - 1) * k_step, self.ridge)
+			if self.seed_shared:
+				state.seed_shared(self._anchor_ids)                           # the anchors' block: factored once for all queries
 		S_ids, S_sc, counts = ops.sort_id_rows(S_ids, torch.cat([Xf, scores], dim=1))
 		for r in range(2, n_rounds + 1):
 			if state is None:

@@ -417,8 +417,8 @@ int anncur_lstsq_rows_timed(const float *Rt, int64_t ldr, int64_t m, int32_t kq,
  * and the threshold never falls, so anncur_lstsq_rows fails it too).
  * State: caller-owned, 256-byte aligned, anncur_lstsq_state_bytes(Q, cap) bytes (0 outside 1 <= cap <= ANNCUR_LSTSQ_MAX_G, Q >= 0); per
  * query, in doubles at the row pitch capp = ceil16(cap): capp rows of G's lower triangle, which turns into L; a row of z = L^-1 c; a row
- * of y (z is never overwritten); a header of 16 (the largest Gram diagonal so far, the smallest accepted pivot so far, the status).
- * Rows at or beyond ceil16(n_new) are neither read nor written.  The layout is this library's: anncur_lstsq_state_bytes is its only
+ * of y (z is never overwritten); a header of 16 (the largest Gram diagonal so far, the smallest accepted pivot so far, the status, the
+ * number of leading entries of z that are valid).  Rows at or beyond ceil16(n_new) are neither read nor written.  The layout is this library's: anncur_lstsq_state_bytes is its only
  * authority.
  * Limits: 0 <= n_old < n_new <= min(cap, kq), 1 <= kq <= ANNCUR_LSTSQ_MAX_KQ; n_new > kq (the query side has no incremental form) and
  * anything else outside them is ANNCUR_E_INVALID and nothing is written; a missing, misaligned or short state is ANNCUR_E_WORKSPACE.
@@ -430,6 +430,29 @@ int anncur_lstsq_extend(const float *Rt, int64_t ldr, int64_t m, int32_t kq, con
 int anncur_lstsq_extend_timed(const float *Rt, int64_t ldr, int64_t m, int32_t kq, const int32_t *ids, int64_t ld_ids, const float *C,
                               int64_t ldc, int64_t Q, int32_t n_old, int32_t n_new, int32_t cap, double ridge, float *W, int64_t ldw,
                               int32_t *status, void *state, size_t state_bytes, void *stream, float *ms3);
+/* Seed a state from a SHARED PREFIX: where the id rows of all Q queries begin with the same n_sh ids (the adaptive search's anchor items,
+ * in the index' order), their n_sh x n_sh Gram block and its Cholesky factor are the same for every query.  This call forms and factors
+ * them once -- the Gram and factor kernels of the calls above, for one query, without a right-hand side -- and copies the factor and the
+ * header to every query's slot of the state.
+ *   replaces the first anncur_lstsq_extend(n_old = 0) of a search forming and factoring that block Q times
+ * shared_ids int32[n_sh] on the device, every id in [0, m) (a hole in it is allowed and decouples, but then every row must hold a hole
+ * there).  The state must be fresh: this call takes the place of n_old = 0, the caller pre-fills nothing.
+ * RESULT: take anncur_lstsq_extend(n_old = n_sh, n_new, ...) on the seeded state, n_sh < n_new <= min(cap, kq), where the first n_sh
+ * columns of ids equal shared_ids in every row (the caller's contract, not checked, like "the positions < n_old are what the previous
+ * call saw").  W and status equal anncur_lstsq_rows(ids[:, :n_new], C[:, :n_new], ridge) bit for bit, hence also
+ * anncur_lstsq_extend(n_old = 0, n_new) on a fresh state; so does every later extension.  z = L^-1 c is the one per-query part of the
+ * prefix: the header counts the leading entries of z that are valid (0 after this call, n_new after a successful extension), and an
+ * extension that finds fewer than 16 p0 of them carries the right-hand side through the old panels too -- inside the same factor
+ * kernel, by the same chain of operations as anncur_lstsq_rows.
+ * FAILURE: a shared block that fails the pivot rule makes every query's header sticky-failed: every later extension returns status 1 and
+ * a NaN row for all queries, as anncur_lstsq_rows does for each of them.  Every query gets the shared block's largest diagonal and
+ * smallest pivot, so a shared pivot that falls under the threshold once an appended item has raised the maximum fails that query alone.
+ * Limits: 1 <= n_sh <= min(cap, kq), 1 <= cap <= ANNCUR_LSTSQ_MAX_G, 1 <= kq <= ANNCUR_LSTSQ_MAX_KQ, ridge >= 0 (the one of every later
+ * call), m >= 1, ldr >= kq; anything else is ANNCUR_E_INVALID; a missing, misaligned or short state (anncur_lstsq_state_bytes(Q, cap)
+ * bytes, 256-byte aligned; layout and size as above) is ANNCUR_E_WORKSPACE; both before any pointer is read.  Q = 0 returns ANNCUR_OK.
+ * Rows at or beyond ceil16(n_sh), and the rows of z and y, are neither read nor written. */
+int anncur_lstsq_seed_shared(const float *Rt, int64_t ldr, int64_t m, int32_t kq, const int32_t *shared_ids, int32_t n_sh, int64_t Q,
+                             int32_t cap, double ridge, void *state, size_t state_bytes, void *stream);
 /* Rows of (id, score) pairs sorted ascending by id, holes (id < 0) last, scores carried along; equal keys keep their order.
  *   replaces the per-query numpy.unique of ops.exclusion (one host pass and one synchronisation per call) where a searcher re-sorts its
  *   scored set every round: the sorted full rows ARE the per-query exclusion lists of anncur_filter_topk (off[q] = q w).
