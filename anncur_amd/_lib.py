@@ -22,6 +22,8 @@ TOPK_STAGED = 32
 MAX_TOPK = 2048
 LSTSQ_MAX_KQ = 4096   # ANNCUR_LSTSQ_MAX_KQ
 LSTSQ_MAX_G = 512     # ANNCUR_LSTSQ_MAX_G
+SVD_MAX_G = 2048      # ANNCUR_SVD_MAX_G
+SVD_MAX_L = 8192      # ANNCUR_SVD_MAX_L
 
 _p32 = POINTER(c_int32)
 
@@ -94,6 +96,11 @@ SIGNATURES = {
 	"anncur_select_pivoted_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
 	"anncur_select_pivoted_slice_items": (c_int32, [c_int]),
 	"anncur_select_pivoted": (c_int, [c_void_p, c_int, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+	"anncur_svd_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+	"anncur_svd_init": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
+	"anncur_svd_sweep": (c_int, [c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
+	"anncur_svd_finish": (c_int, [c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+	"anncur_svd_scale_cols": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, ctypes.c_double, c_void_p, c_int64, c_void_p, c_void_p]),
 	"anncur_overlap_counts": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, _p32, _p32, c_int32, c_void_p, c_void_p]),
 	"anncur_copy_bytes": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
 	"anncur_ivf_build_lists": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -17,7 +17,9 @@ Differences from the reference, all deliberate:
 U = pinv(W) (:47,:49): ``pinv_backend="numpy"`` is the reference's own ``numpy.linalg.pinv`` call on the
 host (U bit-identical); the default "auto" computes it on the GPU in fp64 (exact pseudo-inverse of the
 fp32 block, within 1e-5 of numpy's on the golden cases) and keeps the host call for ill-conditioned
-blocks, whose numpy result is an inverse of fp32 round-off.  Every product runs on the GPU.
+blocks, whose numpy result is an inverse of fp32 round-off.  ``pinv_backend="svd"`` (opt-in) decomposes the block
+by Jacobi rotations in fp64 on the GPU and truncates at ``rcond=``: the one route that can leave
+that round-off out instead of inverting it.  Every product runs on the GPU.
 """
 import logging
 
@@ -36,9 +38,13 @@ def _is_sorted(idx_list):
 	return bool(np.all(a[:-1] < a[1:]))
 
 
-def _pinv_host(M):
-	"""numpy.linalg.pinv (LAPACK SVD, rcond=1e-15) on the fp32 values, as the reference does."""
-	return torch.from_numpy(np.linalg.pinv(M.detach().float().cpu().numpy()))
+def _pinv_host(M, rcond=None):
+	"""rcond=None: numpy.linalg.pinv (LAPACK SVD in fp32, rcond=1e-15) on the fp32 values, exactly the reference's call (U bit-identical).
+	A given rcond has no counterpart in the reference to stay identical to; that call is the parity reference of the "svd" route, so it runs
+	LAPACK in fp64 on the same fp32 values and rounds to fp32 once -- numpy's fp32 SVD is itself ~1e-7 ||X|| away from that."""
+	if rcond is None:
+		return torch.from_numpy(np.linalg.pinv(M.detach().float().cpu().numpy()))
+	return torch.from_numpy(np.linalg.pinv(M.detach().float().cpu().numpy().astype(np.float64), rcond=rcond).astype(np.float32))
 
 
 COMPUTE_DTYPES = ("fp32", "bf16", "bf16x3")
@@ -49,8 +55,33 @@ AUTO_COND_SAFETY = 1.25  # ... times this: the power-iteration estimate of cond_
 AUTO_SQUARE_RATIO, AUTO_SQUARE_MIN = 0.9, 32   # "auto": blocks with min(shape) > 0.9 max(shape) (and at least 32 wide) go straight to the host
 
 
-def _pinv(M, device, backend):
-	"""backend "numpy": the reference's own call on the host (U bit-identical to the reference).
+PINV_BACKENDS = ("auto", "device", "numpy", "device32", "svd")
+PINV_RCOND_BACKENDS = ("numpy", "svd")   # the backends that take rcond=: Newton-Schulz ("auto", "device", "device32") cannot truncate
+
+
+def check_pinv_args(backend, rcond):
+	"""The rules of (pinv_backend, rcond) as ValueErrors, before any work: rcond=None is the reference's 1e-15; a given rcond lies in [0, 1)
+	and needs a backend that can truncate."""
+	if backend not in PINV_BACKENDS:
+		raise ValueError(f"pinv_backend = {backend} not supported")
+	if rcond is None:
+		return None
+	if backend not in PINV_RCOND_BACKENDS:
+		raise ValueError(f"rcond = {rcond!r} given with pinv_backend = {backend!r}: Newton-Schulz cannot truncate, only pinv_backend {' / '.join(repr(b) for b in PINV_RCOND_BACKENDS)} "
+						 "takes rcond")
+	return ops._rcond_check(rcond, "pinv")
+
+
+def _pinv(M, device, backend, rcond=None, info=None):
+	"""rcond: the cutoff of the pseudo-inverse relative to the largest singular value (numpy.linalg.pinv's); None = the reference's 1e-15.
+	  Only "numpy" and "svd" take one (check_pinv_args).  info: a dict that backend "svd" fills with singular_values (fp64 on the device,
+	  descending) and rank, both None where the block went to the host.
+	backend "svd": the Jacobi SVD in fp64 on the GPU and the pseudo-inverse truncated at rcond (pinv.pinv_svd), rounded to fp32 once:
+	  numpy.linalg.pinv(M, rcond) up to numpy's own fp32 round-off, at any conditioning.  A decomposition that did not converge goes to the
+	  host call with the same rcond (logged).  A block outside 1 <= min(shape) <= 2048, max(shape) <= 8192 is a ValueError that names the limit:
+	  that excludes the oracle's pinv(C) [n x kc] and pinv(R) [kr x m] at full size -- with A= (cur_oracle) "svd" serves small matrices only.
+	backend "numpy": the reference's own call on the host (U bit-identical to the reference); with a given rcond, numpy.linalg.pinv(M, rcond) in fp64
+	  on the fp32 values, rounded once (_pinv_host): the parity reference of "svd".
 	backend "device": Newton-Schulz in fp64 on the GPU (anncur_amd/pinv.py), rounded to fp32 once: the exact pseudo-inverse of the
 	  fp32 matrix; differs from numpy's fp32 LAPACK SVD by numpy's own round-off, ~cond(W) * 6e-8 (measured 1e-6..1e-5 on the
 	  golden cases).  A block that is singular to fp32 precision (no convergence within the iteration budget) goes to the host
@@ -59,8 +90,22 @@ def _pinv(M, device, backend):
 	  the two agree far inside the 1e-4 score tolerance; an ill-conditioned block (e.g. as many anchor rows as anchor columns:
 	  numpy inverts singular values that are fp32 noise, and the reference's numbers are made of that noise) goes to the host call.
 	backend "device32": the fp32 iteration of round 1 (fast, ~1e-3)."""
+	rcond = check_pinv_args(backend, rcond)
 	if backend == "numpy":
-		return _pinv_host(M).to(device)
+		return _pinv_host(M, rcond).to(device)
+	if backend == "svd":
+		from . import pinv
+		if info is not None:
+			info.update(singular_values=None, rank=None)
+		if min(M.shape) == 0:
+			return torch.zeros((M.shape[1], M.shape[0]), dtype=torch.float32, device=device)
+		X, res = pinv.pinv_svd(M.to(device), 1e-15 if rcond is None else rcond, return_info=True)
+		if res["converged"]:
+			if info is not None:
+				info.update(singular_values=res["singular_values"], rank=res["rank"])
+			return X
+		LOGGER.info("pinv svd: %d x %d block not converged after %d sweeps -> host numpy.linalg.pinv", M.shape[0], M.shape[1], res["sweeps"])
+		return _pinv_host(M, rcond).to(device)
 	if backend in ("device", "auto"):
 		from .pinv import pinv_newton_schulz_f64
 		if min(M.shape) == 0:
@@ -94,9 +139,14 @@ def _is_full_range(idx, n):
 
 class CURApprox(object):
 
-	def __init__(self, rows, cols, row_idxs, col_idxs, approx_preference, A=None, compute_dtype=None, device=None, pinv_backend="auto"):
+	def __init__(self, rows, cols, row_idxs, col_idxs, approx_preference, A=None, compute_dtype=None, device=None, pinv_backend="auto", rcond=None):
+		"""rcond: the cutoff of U = pinv(W) relative to W's largest singular value, for pinv_backend "svd" and "numpy" (None = the reference's
+		1e-15; with any other backend a given rcond is a ValueError).  With "svd" and no A=, singular_values (fp64, descending) and rank (those
+		above the cutoff) describe the anchor block W; they are None otherwise, and where the block went to the host."""
 		super(CURApprox, self).__init__()
 		self.pinv_backend = pinv_backend
+		self.rcond = check_pinv_args(pinv_backend, rcond)
+		self.singular_values = self.rank = None
 		if device is None:
 			device = rows.device if (torch.is_tensor(rows) and rows.is_cuda) else torch.device("cuda", torch.cuda.current_device())
 		self.device = torch.device(device)
@@ -129,10 +179,12 @@ class CURApprox(object):
 
 		if A is not None:  # oracle U = C^+ A R^+  (:46-47), products left to right on the GPU
 			A_dev = self._to_dev(A)
-			CpA = ops.gemm(_pinv(self._C, self.device, pinv_backend), A_dev)       # kc x m
-			self._U = ops.gemm(CpA, _pinv(self._R, self.device, pinv_backend))     # kc x kr
+			CpA = ops.gemm(_pinv(self._C, self.device, pinv_backend, self.rcond), A_dev)       # kc x m
+			self._U = ops.gemm(CpA, _pinv(self._R, self.device, pinv_backend, self.rcond))     # kc x kr
 		else:
-			self._U = _pinv(intersect_mat, self.device, pinv_backend)             # kc x kr  (:49)
+			info = {}
+			self._U = _pinv(intersect_mat, self.device, pinv_backend, self.rcond, info)       # kc x kr  (:49)
+			self.singular_values, self.rank = info.get("singular_values"), info.get("rank")
 
 		self._Et = None   # [m x kc] fp32: latent_cols transposed ("rows" preference)
 		self._Etp = None  # bf16 packed copy for the fused kernel
@@ -450,7 +502,9 @@ class CURRowIndex(object):
 	all-gather, U = pinv(R[:, col_idxs]) and E = U.R replicated, its own queries' anchor scores gathered locally.
 	Same arithmetic as CURApprox(rows=R, cols=A[:, col_idxs], ...) (eval/matrix_approx_zeshel.py:42-65)."""
 
-	def __init__(self, rows, col_idxs, compute_dtype=None, pinv_backend="auto"):
+	def __init__(self, rows, col_idxs, compute_dtype=None, pinv_backend="auto", rcond=None):
+		"""rcond, and the attributes singular_values / rank that pinv_backend "svd" fills: as for CURApprox."""
+		self.rcond = check_pinv_args(pinv_backend, rcond)
 		self.R = rows
 		self.m = rows.shape[1]
 		self.col_idxs = col_idxs
@@ -460,7 +514,9 @@ class CURRowIndex(object):
 			raise ValueError(f"compute_dtype = {compute_dtype} not supported")
 		self.compute_dtype = compute_dtype
 		W = ops.gather_cols(rows, col_idxs)                      # kr x kc
-		self.U = _pinv(W, rows.device, pinv_backend)             # kc x kr
+		info = {}
+		self.U = _pinv(W, rows.device, pinv_backend, self.rcond, info)   # kc x kr
+		self.singular_values, self.rank = info.get("singular_values"), info.get("rank")
 		self._Et = ops.gemm(rows.t(), self.U.t())                # m x kc
 		kp = ops.padded_k(self._Et.shape[1])
 		self._Etp = self._Etp_sorted = self._item_ids = None

@@ -65,12 +65,14 @@ def _log_skipped_pool_cells(skipped, n_anc, n_ent):
 
 # ------------------------------------------------------------------------------------------------ entry point A
 def run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, seed, exact_cache=None, pinv_backend="auto", compute_dtype=None,
-						   rerank_pool="retrieved", literal_rerank=False):
+						   rerank_pool="retrieved", literal_rerank=False, pinv_rcond=None):
 	"""One seed of one grid cell -> {"anchor": {...}, "non_anchor": {...}, "all": {...}} (crossenc.py:47-158).
 	compute_dtype: CURApprox's (None = by the matrix' dtype; "bf16x3" = the fp32-parity route on the bf16 matrix cores).
 	rerank_pool "retrieved+anchors": every subset also reports the overlap metrics of the pool anchor items + top_k_retvr NEW items under
-	POOL_PREFIX (a second retrieval, with the anchor items excluded); a cell beyond pool_cell_limit is left out of that prefix."""
+	POOL_PREFIX (a second retrieval, with the anchor items excluded); a cell beyond pool_cell_limit is left out of that prefix.
+	pinv_rcond: CURApprox's rcond= (pinv_backend "svd" / "numpy": the cutoff of pinv(W); None = the reference's 1e-15, today's call)."""
 	with_pool = _check_rerank_pool(rerank_pool)
+	rcond_kw = {} if pinv_rcond is None else {"rcond": pinv_rcond}
 	n_ments, n_ents = A_dev.shape
 	rng = np.random.default_rng(seed=seed)
 	row_idxs = _select(rng, n_ments, n_ment_anchors)          # rows first, then columns, same generator
@@ -79,9 +81,9 @@ def run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, 
 	cols = ops.gather_cols(A_dev, col_idxs)
 	non_anchor = sorted(set(range(n_ments)) - set(int(i) for i in row_idxs))
 	if approx_method == "cur":
-		cur = CURApprox(rows=rows, cols=cols, row_idxs=row_idxs, col_idxs=col_idxs, approx_preference="rows", pinv_backend=pinv_backend, compute_dtype=compute_dtype)
+		cur = CURApprox(rows=rows, cols=cols, row_idxs=row_idxs, col_idxs=col_idxs, approx_preference="rows", pinv_backend=pinv_backend, compute_dtype=compute_dtype, **rcond_kw)
 	elif approx_method == "cur_oracle":
-		cur = CURApprox(rows=rows, cols=cols, row_idxs=row_idxs, col_idxs=col_idxs, approx_preference="rows", A=A_dev, pinv_backend=pinv_backend, compute_dtype=compute_dtype)
+		cur = CURApprox(rows=rows, cols=cols, row_idxs=row_idxs, col_idxs=col_idxs, approx_preference="rows", A=A_dev, pinv_backend=pinv_backend, compute_dtype=compute_dtype, **rcond_kw)
 	else:
 		raise NotImplementedError(f"approx_method = {approx_method} not supported")
 	# approximate retrieval for EVERY query row + the per-row error terms: one sweep where the fused route takes the cell (cur.eval_rows)
@@ -119,12 +121,12 @@ def run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, 
 
 
 def run_approx_eval(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, n_seeds, exact_cache=None, pinv_backend="auto", compute_dtype=None,
-					rerank_pool="retrieved", literal_rerank=False):
+					rerank_pool="retrieved", literal_rerank=False, pinv_rcond=None):
 	"""Mean over seeds (crossenc.py:162-200)."""
 	acc = defaultdict(lambda: defaultdict(list))
 	for seed in range(n_seeds):
 		res = run_approx_eval_w_seed(approx_method, A_dev, n_ment_anchors, n_ent_anchors, top_k, top_k_retvr, seed, exact_cache, pinv_backend, compute_dtype,
-									 rerank_pool=rerank_pool, literal_rerank=literal_rerank)
+									 rerank_pool=rerank_pool, literal_rerank=literal_rerank, **({} if pinv_rcond is None else {"pinv_rcond": pinv_rcond}))
 		for ment_type, d in res.items():
 			for metric, val in d.items():
 				acc[ment_type][metric].append(float(val))
@@ -206,7 +208,7 @@ def default_grids_A(total_n_ment, total_n_ent):
 	}
 
 
-def run_entry_A(A_dev, grids, n_seeds, progress=None, pinv_backend="auto", compute_dtype=None, rerank_pool="retrieved", literal_rerank=False):
+def run_entry_A(A_dev, grids, n_seeds, progress=None, pinv_backend="auto", compute_dtype=None, rerank_pool="retrieved", literal_rerank=False, pinv_rcond=None):
 	"""-> res[method]["top_k=.."]["k_retvr=.."]["anc_n_m=..~anc_n_e=.."][anchor|non_anchor|all][metric]  (crossenc.py:349-383)."""
 	total_n_ment, total_n_ent = A_dev.shape
 	res = defaultdict(lambda: defaultdict(lambda: defaultdict(dict)))
@@ -221,7 +223,8 @@ def run_entry_A(A_dev, grids, n_seeds, progress=None, pinv_backend="auto", compu
 			if progress:
 				progress(method, ctr, len(cells))
 			res[method][f"top_k={top_k}"][f"k_retvr={kr}"][f"anc_n_m={nm}~anc_n_e={ne}"] = \
-				run_approx_eval(method, A_dev, nm, ne, top_k, kr, n_seeds, exact_cache, pinv_backend, compute_dtype, rerank_pool=rerank_pool, literal_rerank=literal_rerank)
+				run_approx_eval(method, A_dev, nm, ne, top_k, kr, n_seeds, exact_cache, pinv_backend, compute_dtype, rerank_pool=rerank_pool, literal_rerank=literal_rerank,
+								**({} if pinv_rcond is None else {"pinv_rcond": pinv_rcond}))
 	return {m: {a: {b: dict(c) for b, c in d.items()} for a, d in v.items()} for m, v in res.items()}
 
 
@@ -281,7 +284,7 @@ ADAPTIVE_SOFTMAX_PREFIX = "exact_vs_reranked_adaptive_softmax_retvr"   # ... wit
 
 
 def _sweep_adaptive_cells(A_test_dev, A_train_dev, anc, exact, top_k_vals, top_k_retr_vals, n_rounds, compute_dtype, pinv_backend, incremental=False,
-						  strategy="topk", temperature=1.0, seed=0):
+						  strategy="topk", temperature=1.0, seed=0, pinv_rcond=None):
 	"""The adaptive-search metrics (ADAPTIVE_PREFIX) of the (top_k, k_retvr) cells of one anchor set: the pool of a cell is the anchor items
 	+ n_rounds rounds of k_retvr / n_rounds NEW items each, scored through MatrixScorer(A_test) -- its own AdaptiveSearcher run per k_retvr,
 	because adaptive results are not prefixes of one another --, and recall is the closed form |exact[:k] & pool| (retrieval.overlap_pool_cells'
@@ -295,7 +298,7 @@ def _sweep_adaptive_cells(A_test_dev, A_train_dev, anc, exact, top_k_vals, top_k
 	if len(anc) == 0:
 		LOGGER.info("adaptive_rounds=%d: no anchor items: every cell left out of %s (the first round needs anchor scores)", n_rounds, prefix)
 		return out
-	index = CURRowIndex(A_train_dev, np.asarray(anc), compute_dtype=compute_dtype, pinv_backend=pinv_backend)
+	index = CURRowIndex(A_train_dev, np.asarray(anc), compute_dtype=compute_dtype, pinv_backend=pinv_backend, **({} if pinv_rcond is None else {"rcond": pinv_rcond}))
 	searcher = AdaptiveSearcher(index, MatrixScorer(A_test_dev), incremental=incremental, strategy=strategy, temperature=temperature, seed=seed)
 	qids = torch.arange(A_test_dev.shape[0], dtype=torch.int64)
 	for kr in top_k_retr_vals:
@@ -322,7 +325,7 @@ def _sweep_adaptive_cells(A_test_dev, A_train_dev, anc, exact, top_k_vals, top_k
 
 def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None, progress=None, key_n_m=None, pinv_backend="auto", rerank_pool="retrieved",
 						literal_rerank=False, adaptive_rounds=1, adaptive_incremental=False, adaptive_strategy="topk", adaptive_temperature=1.0, adaptive_seed=0,
-						anchor_selection="random"):
+						anchor_selection="random", pinv_rcond=None):
 	"""eval_method == "cur" of entry point B for one seed (splits.py:286-303 + 399-429).
 	rerank_pool "retrieved+anchors": every cell also reports, under POOL_PREFIX, the metrics of the pool anchor items + k_retvr NEW items (a
 	second retrieval per anchor count, with the anchor items excluded, at the largest k_retvr with k_retvr + n_anc <= pool_cell_limit).
@@ -333,8 +336,10 @@ def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None
 	anchor_selection "random": the reference's sorted(rng.choice(...)) per anchor count, today's code path and rng stream.  "pivoted" (DESIGN
 	4.4f): the anchor items of every count are the sorted first n_anc of ONE column-pivoted QR selection from A_train; `seed` is not used,
 	counts the selection cannot deliver are left out and logged once (_pivoted_anchor_counts), n_anc = 0 keeps its branch; the pool and
-	adaptive modes see only the anchor list."""
+	adaptive modes see only the anchor list.
+	pinv_rcond: the rcond= of every index built here (pinv_backend "svd" / "numpy": the cutoff of pinv(W); None = the reference's 1e-15, today's call)."""
 	with_pool = _check_rerank_pool(rerank_pool)
+	rcond_kw = {} if pinv_rcond is None else {"rcond": pinv_rcond}
 	if anchor_selection not in ANCHOR_SELECTIONS:
 		raise ValueError(f"anchor_selection = {anchor_selection} not supported (one of {', '.join(ANCHOR_SELECTIONS)})")
 	if adaptive_rounds < 1:
@@ -367,7 +372,7 @@ def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None
 					res[f"top_k={k}"][f"k_retvr={kr}"][f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}"].update(metrics)
 			continue
 		cur = CURApprox(rows=A_train_dev, cols=ops.gather_cols(A_train_dev, anc), row_idxs=np.arange(n_train), col_idxs=anc,
-						approx_preference="rows", compute_dtype=compute_dtype, pinv_backend=pinv_backend)
+						approx_preference="rows", compute_dtype=compute_dtype, pinv_backend=pinv_backend, **rcond_kw)
 		X = ops.gather_cols(A_test_dev, anc)
 		approx = cur.topk_in_row_device(X, kr_max)
 		for (k, kr), metrics in _sweep_cells(A_test_dev, approx.indices, exact, top_k_vals, retr_vals, n_ent).items():
@@ -380,7 +385,8 @@ def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None
 			del new_items
 		if adaptive_rounds >= 2:
 			for (k, kr), metrics in _sweep_adaptive_cells(A_test_dev, A_train_dev, anc, exact, top_k_vals, retr_vals, adaptive_rounds, compute_dtype, pinv_backend,
-																  adaptive_incremental, adaptive_strategy, adaptive_temperature, adaptive_seed).items():
+																  adaptive_incremental, adaptive_strategy, adaptive_temperature, adaptive_seed,
+																  **({} if pinv_rcond is None else {"pinv_rcond": pinv_rcond})).items():
 				res[f"top_k={k}"][f"k_retvr={kr}"][f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}"].update(metrics)
 		del cur, approx
 	return {a: {b: dict(c) for b, c in d.items()} for a, d in res.items()}

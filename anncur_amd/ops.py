@@ -1478,6 +1478,108 @@ def select_pivoted(R, k):
 	return ids, gains, int(n_sel.item())
 
 
+# ------------------------------------------------------------------ Jacobi SVD and the truncated pseudo-inverse
+SVD = namedtuple("SVD", ["U", "S", "V", "sweeps", "converged"])
+
+
+def _svd_check(rows, cols):
+	"""The limits of anncur_svd_*, as ValueErrors that name them (nothing needs a GPU here)."""
+	g, L = min(rows, cols), max(rows, cols)
+	if g < 1 or g > _lib.SVD_MAX_G:
+		raise ValueError(f"svd_jacobi: min(rows, cols) = {g} outside 1..ANNCUR_SVD_MAX_G = {_lib.SVD_MAX_G} (block {rows} x {cols})")
+	if L > _lib.SVD_MAX_L:
+		raise ValueError(f"svd_jacobi: max(rows, cols) = {L} above ANNCUR_SVD_MAX_L = {_lib.SVD_MAX_L} (block {rows} x {cols})")
+
+
+def _rcond_check(rcond, what):
+	"""rcond of a truncated pseudo-inverse: a number in [0, 1) (numpy.linalg.pinv's cutoff relative to the largest singular value)."""
+	try:
+		r = float(rcond)
+	except (TypeError, ValueError):
+		raise ValueError(f"{what}: rcond must be a number in [0, 1) (got {rcond!r})") from None
+	if not (0.0 <= r < 1.0):
+		raise ValueError(f"{what}: rcond = {rcond!r} outside [0, 1)")
+	return r
+
+
+@_on_device
+def svd_jacobi_unsorted(W, max_sweeps=30, workspace=None, out=None):
+	"""The three C calls of the Jacobi SVD around the convergence loop: anncur_svd_init, then anncur_svd_sweep until a sweep rotates nothing or
+	max_sweeps have run (one 4-byte read of the counter per sweep, the loop's only synchronisation), then anncur_svd_finish.
+	-> (sigma fp64 [g] in the workspace's order, U fp64 [rows x g], V fp64 [cols x g], sweeps, converged).
+	workspace: a 256-byte aligned uint8 tensor of at least anncur_svd_workspace_bytes (default: the grow-only scratch of the device).
+	out: (sigma, U, V, rotations int32 [1], flag int32 [1]) to write into (U, V with unit column stride and any row pitch >= g); default: fresh tensors."""
+	if not torch.is_tensor(W) or W.dim() != 2:
+		raise ValueError("svd_jacobi: W must be a 2-D tensor")
+	rows, cols = W.shape
+	_svd_check(rows, cols)
+	if isinstance(max_sweeps, bool) or not isinstance(max_sweeps, (int, np.integer)) or max_sweeps < 1:
+		raise ValueError(f"svd_jacobi: max_sweeps must be an integer >= 1 (got {max_sweeps!r})")
+	_dev(W)
+	dt = _dt(W)
+	W = _rowmajor(W)
+	g = min(rows, cols)
+	lib = _lib.load()
+	need = lib.anncur_svd_workspace_bytes(rows, cols)
+	ws = _Workspace.get(need, W.device) if workspace is None else workspace
+	if out is None:
+		out = (torch.empty((g,), dtype=torch.float64, device=W.device), torch.empty((rows, g), dtype=torch.float64, device=W.device),
+			   torch.empty((cols, g), dtype=torch.float64, device=W.device), torch.empty((1,), dtype=torch.int32, device=W.device),
+			   torch.empty((1,), dtype=torch.int32, device=W.device))
+	sigma, U, V, rot, flag = out
+	if tuple(U.shape) != (rows, g) or tuple(V.shape) != (cols, g) or sigma.numel() != g or any(t.dtype != torch.float64 for t in (sigma, U, V)) or \
+			(g > 1 and (U.stride(1) != 1 or V.stride(1) != 1)) or not sigma.is_contiguous():
+		raise ValueError("svd_jacobi: out = (sigma fp64 [g], U fp64 [rows x g], V fp64 [cols x g], rotations int32 [1], flag int32 [1]), unit column strides")
+	check(lib.anncur_svd_init(_p(W), dt, _ld(W), rows, cols, _p(ws), ws.numel(), _stream()), "svd_init")
+	sweeps, converged = 0, False
+	while sweeps < max_sweeps and not converged:
+		check(lib.anncur_svd_sweep(rows, cols, _p(ws), ws.numel(), _p(rot), _stream()), "svd_sweep")
+		sweeps += 1
+		converged = int(rot.item()) == 0
+	check(lib.anncur_svd_finish(rows, cols, _p(ws), ws.numel(), _p(sigma), _p(U), max(_ld(U), g), _p(V), max(_ld(V), g), _p(flag), _stream()), "svd_finish")
+	if int(flag.item()) != 0:
+		converged = False   # a singular value that is not finite: W held a NaN / inf, or a norm left the fp64 range
+	return sigma, U, V, sweeps, converged
+
+
+def svd_jacobi(W, max_sweeps=30):
+	"""Singular value decomposition of ONE block W [rows x cols] (fp32 or bf16 on the GPU, any row pitch) by one-sided Jacobi rotations in fp64
+	(anncur_svd_*; include/anncur_hip.h has the contract) -> SVD(U fp64 [rows x g], S fp64 [g] DESCENDING, V fp64 [cols x g], sweeps, converged),
+	g = min(rows, cols), W = U diag(S) V^T.  converged: a whole sweep rotated nothing; otherwise the call stops after max_sweeps sweeps and says
+	so (no exception); a singular value that is not finite also gives converged = False.  Limits: 1 <= g <= ANNCUR_SVD_MAX_G = 2048,
+	max(rows, cols) <= ANNCUR_SVD_MAX_L = 8192 (ValueError, before any launch).  The same input gives the same bits on every run.
+	The kernels leave the singular values in the order of W's vectors; the sort (stable, descending) and the matching column permutation of U
+	and V are torch indexing, not arithmetic."""
+	sigma, U, V, sweeps, converged = svd_jacobi_unsorted(W, max_sweeps)
+	S, order = torch.sort(sigma, descending=True, stable=True)
+	return SVD(U.index_select(1, order), S, V.index_select(1, order), sweeps, converged)
+
+
+def pinv_from_svd(svd, rcond=1e-15):
+	"""Truncated pseudo-inverse from a decomposition: X = sum over sigma_i > rcond sigma_max of v_i u_i^T / sigma_i (numpy.linalg.pinv's rule),
+	summed in fp64 (anncur_svd_scale_cols, then anncur_gemm_f64) and rounded to fp32 once -> (X fp32 [cols x rows], rank = the number of
+	singular values kept).  One decomposition serves any number of cutoffs: a call costs one small GEMM.  rcond in [0, 1), else ValueError."""
+	rcond = _rcond_check(rcond, "pinv_from_svd")
+	return _pinv_from_svd(svd.U, svd.S, svd.V, rcond)
+
+
+@_on_device
+def _pinv_from_svd(U, S, V, rcond):
+	_dev(U, S, V)
+	cols, g = V.shape
+	rows = U.shape[0]
+	if any(t.dtype != torch.float64 for t in (U, S, V)) or U.shape[1] != g or S.numel() != g:
+		raise ValueError("pinv_from_svd: need U fp64 [rows x g], S fp64 [g], V fp64 [cols x g]")
+	V, S = _rowmajor(V), S.contiguous()
+	Vs = torch.empty((cols, g), dtype=torch.float64, device=V.device)
+	rank = torch.empty((1,), dtype=torch.int32, device=V.device)
+	check(_lib.load().anncur_svd_scale_cols(_p(V), max(_ld(V), g), cols, g, _p(S), rcond, _p(Vs), g, _p(rank), _stream()), "svd_scale_cols")
+	X64 = gemm_f64(Vs, U.t())                                # [cols x rows]
+	X = torch.empty((cols, rows), dtype=torch.float32, device=V.device)
+	convert_f64(X64, X)
+	return X, int(rank.item())
+
+
 @_on_device
 def gather_pairs(A, idx):
 	"""out[q, j] = A[q, idx[q, j]] as float32 [Q x n]; an id outside [0, I) (a hole) gives NaN (reference: ..._splits.py:91-96 reads

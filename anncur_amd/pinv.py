@@ -10,7 +10,8 @@ rounded once -- what cur.py's default backend "auto" runs while the block is wel
 LAPACK call as the reference, makes U bit-identical) and round 1's fp32 iteration (pinv_newton_schulz, backend "device32":
 accuracy ~ cond(W) * 6e-8 like an fp32 SVD, singular values below ~1e-4 * sigma_max effectively truncated by the iteration cap).
 The device routes matter for large anchor counts, where the host SVD dominates the index build (2048 x 1024: 1.4 s on the host, a
-few ms here)."""
+few ms here).  A third route, pinv_svd (backend "svd", opt-in), decomposes the block by Jacobi rotations in fp64 and is the only one
+that can leave singular values below a cutoff out: no faster than the host call, but it truncates and reports the spectrum."""
 import torch
 
 from . import ops
@@ -121,3 +122,19 @@ def pinv_newton_schulz_f64(W, max_iters=64, check_from=4, rtol=1e-10, return_inf
 		xs2 = _spectral_norm_sq(X) if final else float("inf")
 		return out, {"iterations": its, "cond_F": (w2 * x2) ** 0.5, "cond_2": (s2 * xs2) ** 0.5, "converged": final}
 	return out
+
+
+def pinv_svd(W, rcond=1e-15, return_info=False, max_sweeps=30):
+	"""Truncated pseudo-inverse through the Jacobi SVD on the device (ops.svd_jacobi + ops.pinv_from_svd): the one device route
+	with a cutoff; its sweep count barely depends on cond(W) (10-18 sweeps measured from cond 1e2 to 4e5), where Newton-Schulz needs
+	~2 log2 cond(W) GEMM pairs -- which are still far cheaper at the sizes measured (DESIGN 4.5a has the table).  W: [m x n] fp32 / bf16 on the GPU -> W^+ [n x m] fp32 on the GPU: the singular values above
+	rcond * sigma_max inverted (numpy.linalg.pinv's rule), the sum in fp64, one rounding.  1 <= min(m, n) <= 2048, max(m, n) <= 8192 and
+	0 <= rcond < 1, else ValueError.
+	info: singular_values (fp64 on the device, descending), rank (those kept), sweeps, converged (False: max_sweeps ran out, or a singular
+	value is not finite; X is then what the unfinished iteration gives, and the caller -- cur._pinv -- hands the block to the host)."""
+	rcond = ops._rcond_check(rcond, "pinv_svd")
+	svd = ops.svd_jacobi(W, max_sweeps=max_sweeps)
+	X, rank = ops.pinv_from_svd(svd, rcond)
+	if return_info:
+		return X, {"singular_values": svd.S, "rank": rank, "sweeps": svd.sweeps, "converged": svd.converged}
+	return X

@@ -31,6 +31,23 @@ def _ints(s):
 	return [int(x) for x in s.split(",") if x != ""]
 
 
+def _rcond(s):
+	r = float(s)
+	if not (0.0 <= r < 1.0):
+		raise argparse.ArgumentTypeError("--pinv_rcond needs a number in [0, 1)")
+	return r
+
+
+class _Parser(argparse.ArgumentParser):
+	"""argparse with the one rule that spans two flags: only a backend that can truncate takes --pinv_rcond."""
+
+	def parse_args(self, args=None, namespace=None):
+		ns = super().parse_args(args, namespace)
+		if ns.pinv_rcond is not None and ns.pinv not in ("svd", "numpy"):
+			self.error(f"--pinv_rcond needs --pinv svd or numpy: Newton-Schulz (--pinv {ns.pinv}) cannot truncate")
+		return ns
+
+
 def plot(res_dir, method_vals):
 	"""Heat maps of the non-anchor-query metrics over the (anchor mentions x anchor entities) grid, one PDF per
 	(method, top_k, k_retvr, metric) under {res_dir}/plots_non_anchor/ (reference: crossenc.py:404-510)."""
@@ -56,7 +73,7 @@ def plot(res_dir, method_vals):
 
 
 def run(base_res_dir, data_info, n_seeds, plot_only, misc, arg_dict, grid_overrides, dtype, device, pinv_backend="auto", score_chunks=None, compute_dtype=None,
-		rerank_pool="retrieved"):
+		rerank_pool="retrieved", pinv_rcond=None):
 	from anncur_amd import harness
 	data_name, data_fname = data_info
 	world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -112,10 +129,11 @@ def run(base_res_dir, data_info, n_seeds, plot_only, misc, arg_dict, grid_overri
 			if torch.device(device).type == "cuda":
 				torch.cuda.set_device(device)   # the launch stream and torch's allocations follow --device
 			A_dev = chunked["A_local"] if chunked is not None else harness.to_device_matrix(scores, device, dtype)
+			rcond_kw = {} if pinv_rcond is None else {"pinv_rcond": pinv_rcond}
 			if rerank_pool == "retrieved":
-				eval_res = harness.run_entry_A(A_dev, grids, n_seeds, progress, pinv_backend, compute_dtype)
+				eval_res = harness.run_entry_A(A_dev, grids, n_seeds, progress, pinv_backend, compute_dtype, **rcond_kw)
 			else:
-				eval_res = harness.run_entry_A(A_dev, grids, n_seeds, progress, pinv_backend, compute_dtype, rerank_pool=rerank_pool)
+				eval_res = harness.run_entry_A(A_dev, grids, n_seeds, progress, pinv_backend, compute_dtype, rerank_pool=rerank_pool, **rcond_kw)
 		eval_res["other_args"] = other_args
 		with open(f"{res_dir}/retrieval_wrt_exact_crossenc.json", "w") as fout:
 			json.dump(obj=eval_res, fp=fout, indent=4)
@@ -129,7 +147,7 @@ def run(base_res_dir, data_info, n_seeds, plot_only, misc, arg_dict, grid_overri
 
 def build_parser(worlds=None, data_dir="../../data/zeshel"):
 	worlds = get_zeshel_world_info() if worlds is None else worlds
-	parser = argparse.ArgumentParser(description="Run eval for various retrieval methods wrt exact crossencoder scores. "
+	parser = _Parser(description="Run eval for various retrieval methods wrt exact crossencoder scores. "
 												 "This evaluation does not use ground-truth entity information into account")
 	parser.add_argument("--data_name", type=str, choices=[w for _, w in worlds], help="Dataset name")
 	parser.add_argument("--bi_model_file", type=str, default="", help="File for biencoder ckpt (bienc baseline: not part of this build)")
@@ -149,9 +167,13 @@ def build_parser(worlds=None, data_dir="../../data/zeshel"):
 	parser.add_argument("--data_dir", type=str, default=data_dir)
 	parser.add_argument("--dtype", type=str, default="fp32", choices=["fp32", "bf16"], help="storage/compute type of the score matrix on the GPU")
 	parser.add_argument("--device", type=str, default="cuda:0")
-	parser.add_argument("--pinv", type=str, default="auto", choices=["numpy", "device", "auto", "device32"],
+	parser.add_argument("--pinv", type=str, default="auto", choices=["numpy", "device", "auto", "device32", "svd"],
 						help="pseudo-inverse: numpy = the reference's numpy.linalg.pinv on the host (bit-identical U); device = fp64 Newton-Schulz on the GPU "
-							 "(exact pseudo-inverse of the fp32 block, rounded once); auto = device while the block is well conditioned, else numpy")
+							 "(exact pseudo-inverse of the fp32 block, rounded once); auto = device while the block is well conditioned, else numpy; svd = Jacobi SVD in "
+							 "fp64 on the GPU, truncated at --pinv_rcond (blocks up to 2048 on the short side and 8192 on the long one: cur_oracle only on small matrices)")
+	parser.add_argument("--pinv_rcond", type=_rcond, default=None,
+						help="with --pinv svd or numpy: singular values of the anchor block at or below this fraction of the largest are left out of the pseudo-inverse "
+							 "(in [0, 1); default: the reference's 1e-15).  Newton-Schulz (auto, device, device32) cannot truncate: an error beside those")
 	parser.add_argument("--compute_dtype", type=str, default="auto", choices=["auto", "fp32", "bf16", "bf16x3"],
 						help="arithmetic of the CUR retrieval: auto = by --dtype (fp32 matrix -> dense fp32 route, bf16 -> fused bf16 kernel); bf16x3 = for --dtype fp32: "
 							 "operands split into bf16 hi + lo parts on the fused kernel, candidates rescored in fp32 (the fp32 route's values, S_hat never written)")
@@ -173,6 +195,8 @@ def main(argv=None):
 	arg_dict = dict(args.__dict__)
 	if args.rerank_pool == "retrieved":
 		del arg_dict["rerank_pool"]   # the default run writes the output it wrote before the flag existed, byte for byte
+	if args.pinv_rcond is None:
+		del arg_dict["pinv_rcond"]   # (the same rule)
 	datasets = get_dataset_info(data_dir=args.data_dir, res_dir=args.res_dir, worlds=worlds, n_ment=args.n_ment)
 	LOGGER.info(f"Running inference for world = {args.data_name}")
 	return run(base_res_dir=f"{args.res_dir}/{args.data_name}/Retrieval_wrt_Exact_CrossEnc", data_info=(args.data_name, datasets[args.data_name]),
@@ -181,7 +205,8 @@ def main(argv=None):
 							   "n_ent_anchors_vals": args.n_ent_anchors_vals, "top_k_vals": args.top_k_vals, "top_k_retr_vals": args.top_k_retr_vals},
 			   dtype=args.dtype, device=torch.device(args.device), pinv_backend=args.pinv, score_chunks=args.score_chunks,
 			   compute_dtype=None if args.compute_dtype == "auto" else args.compute_dtype,
-			   **({} if args.rerank_pool == "retrieved" else {"rerank_pool": args.rerank_pool}))
+			   **({} if args.rerank_pool == "retrieved" else {"rerank_pool": args.rerank_pool}),
+			   **({} if args.pinv_rcond is None else {"pinv_rcond": args.pinv_rcond}))
 
 
 if __name__ == "__main__":

@@ -54,6 +54,13 @@ def _seed(s):
 	return n
 
 
+def _rcond(s):
+	r = float(s)
+	if not (0.0 <= r < 1.0):
+		raise argparse.ArgumentTypeError("--pinv_rcond needs a number in [0, 1)")
+	return r
+
+
 def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, device):
 	from anncur_amd import harness, ops
 	LOGGER.info("Loading precomputed ment_to_ent scores")
@@ -83,6 +90,8 @@ def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, de
 			pool_kw = dict(pool_kw, adaptive_seed=args.adaptive_seed)
 	if args.anchor_selection != "random" and curr_method == "cur":
 		pool_kw = dict(pool_kw, anchor_selection=args.anchor_selection)   # (random = today's call; the other methods ignore the flag)
+	if args.pinv_rcond is not None and curr_method == "cur":
+		pool_kw = dict(pool_kw, pinv_rcond=args.pinv_rcond)   # (None = today's call; the other methods build no pseudo-inverse through --pinv)
 	LOGGER.info(f"Computing approximate test mention-to-entity scores using method={curr_method}")
 	if curr_method == "cur":
 		A_train_dev = harness.to_device_matrix(A_train, device, args.dtype)
@@ -134,7 +143,7 @@ def run(args, device):
 		del arg_dict["adaptive_rounds"]   # (the same rule)
 	if not args.adaptive_incremental:
 		del arg_dict["adaptive_incremental"]   # (the same rule)
-	for key, default in (("adaptive_strategy", "topk"), ("adaptive_temperature", 1.0), ("adaptive_seed", 0), ("anchor_selection", "random")):
+	for key, default in (("adaptive_strategy", "topk"), ("adaptive_temperature", 1.0), ("adaptive_seed", 0), ("anchor_selection", "random"), ("pinv_rcond", None)):
 		if getattr(args, key) == default:
 			del arg_dict[key]   # (the same rule)
 	eval_res["other_args"] = arg_dict
@@ -148,12 +157,15 @@ def run(args, device):
 
 
 class _Parser(argparse.ArgumentParser):
-	"""argparse with the one rule that spans two flags: a deterministic anchor selection has no seeds to average over."""
+	"""argparse with the rules that span two flags: a deterministic anchor selection has no seeds to average over, and only a backend that
+	can truncate takes --pinv_rcond."""
 
 	def parse_args(self, args=None, namespace=None):
 		ns = super().parse_args(args, namespace)
 		if ns.anchor_selection == "pivoted" and ns.n_seeds > 1:
 			self.error(f"--anchor_selection pivoted is deterministic: --n_seeds {ns.n_seeds} would repeat one result (use --n_seeds 1)")
+		if ns.pinv_rcond is not None and ns.pinv not in ("svd", "numpy"):
+			self.error(f"--pinv_rcond needs --pinv svd or numpy: Newton-Schulz (--pinv {ns.pinv}) cannot truncate")
 		return ns
 
 
@@ -184,9 +196,13 @@ def build_parser(worlds=None):
 	parser.add_argument("--entity_embeds_file", type=str, default="")
 	parser.add_argument("--dtype", type=str, default="fp32", choices=["fp32", "bf16"])
 	parser.add_argument("--device", type=str, default="cuda:0")
-	parser.add_argument("--pinv", type=str, default="auto", choices=["numpy", "device", "auto", "device32"],
+	parser.add_argument("--pinv", type=str, default="auto", choices=["numpy", "device", "auto", "device32", "svd"],
 						help="pseudo-inverse: numpy = the reference's numpy.linalg.pinv on the host (bit-identical U); device = fp64 Newton-Schulz on the GPU "
-							 "(exact pseudo-inverse of the fp32 block, rounded once); auto = device while the block is well conditioned, else numpy")
+							 "(exact pseudo-inverse of the fp32 block, rounded once); auto = device while the block is well conditioned, else numpy; svd = Jacobi SVD in "
+							 "fp64 on the GPU, truncated at --pinv_rcond (blocks up to 2048 on the short side and 8192 on the long one: cur_oracle only on small matrices)")
+	parser.add_argument("--pinv_rcond", type=_rcond, default=None,
+						help="with --pinv svd or numpy: singular values of the anchor block at or below this fraction of the largest are left out of the pseudo-inverse "
+							 "(in [0, 1); default: the reference's 1e-15).  Newton-Schulz (auto, device, device32) cannot truncate: an error beside those")
 	parser.add_argument("--rerank_pool", type=str, default="retrieved", choices=["retrieved", "retrieved+anchors"],
 						help="items the exact re-rank of a CUR cell chooses from: retrieved = the k_retvr retrieved items (the reference's cell); retrieved+anchors = "
 							 "additionally report, under exact_vs_reranked_approx_retvr_w_anchors~..., the pool of the anchor items (whose exact scores every query has "

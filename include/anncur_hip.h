@@ -526,6 +526,47 @@ int32_t anncur_select_pivoted_slice_items(int dtype);   /* items per slice of th
 int anncur_select_pivoted(const void *R, int dtype, int64_t ldr, int32_t kq, int64_t m, int32_t k, int32_t *out_ids, double *out_gain,
                           int32_t *n_sel, void *workspace, size_t workspace_bytes, void *stream);
 
+/* a3b: singular value decomposition of ONE block by one-sided (Hestenes) Jacobi rotations in fp64, and the truncated pseudo-inverse --------
+ *   U = numpy.linalg.pinv(W) with a cutoff the caller chooses                                               eval/matrix_approx_zeshel.py:47,49
+ * (the reference's call fixes rcond = 1e-15; Newton-Schulz, the other device route, has no notion of a cutoff).  DESIGN 4.5a.
+ * W [rows x cols] row-major, dtype ANNCUR_F32 or ANNCUR_BF16 (widened exactly), row pitch ldw >= cols (the pad is never read).
+ * g = min(rows, cols), L = max(rows, cols).  The g short-side vectors of W -- its columns if rows >= cols, else its rows -- are made mutually
+ * orthogonal; their norms are the singular values.
+ * WORKSPACE (caller-owned, 256-byte aligned, anncur_svd_workspace_bytes(rows, cols) bytes, 0 outside the limits; nothing in it is pre-filled):
+ *   H  [g x Lp] fp64, row i = vector i;  Vt [g x gp] fp64, starts as the identity;  Lp, gp = L, g rounded up to 32.  The pad is never read.
+ * THE ALGORITHM (a contract):
+ *   a sweep = the gE - 1 steps of the round-robin tournament on gE = g rounded up to even (circle method); in step s pair p holds
+ *       (gE - 1, s) for p = 0,   ((s + p) mod (gE - 1), (s - p + gE - 1) mod (gE - 1)) for p >= 1;   a pair with an index >= g idles
+ *   the pair (i, j), i < j:  alpha = |h_i|^2, beta = |h_j|^2, gamma = h_i . h_j, recomputed from the rows every time
+ *       rotate iff alpha > 0, beta > 0 and |gamma| > sqrt(L) 2^-53 sqrt(alpha) sqrt(beta)        (dgesvj's tolerance)
+ *       zeta = (beta - alpha) / (2 gamma),  t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2))  (t = 1 at zeta = 0),  c = 1 / sqrt(1 + t^2),  s = c t
+ *       h_i <- c h_i - s h_j,  h_j <- s h_i + c h_j;  the same on rows i, j of Vt
+ *   each sum: thread t of 256 takes the elements t, t + 256, .. by fma in ascending order, the lanes of a wave are combined by the xor
+ *       butterfly 32 .. 1, the four waves are added in wave order: an order fixed by L alone, so a result is bit-reproducible from call to call
+ * One launch per step, one workgroup per pair; the pairs of a step touch disjoint rows and the kernel boundary orders the steps: no
+ * cooperative launch, no workgroup waits for another, no loop without a bound, no floating-point atomics.
+ *  anncur_svd_init    widens W into H and sets Vt = I.
+ *  anncur_svd_sweep   one sweep (gE - 1 launches).  rotations int32[1] (device) is zeroed on the stream first and then counts the pairs that
+ *                     rotated (an integer atomic): 0 after a sweep means converged.  The caller's loop reads these 4 bytes; no call here
+ *                     synchronises.
+ *  anncur_svd_finish  sigma double[g] = |h_i| (in the workspace's order, NOT sorted), the normalised h_i (zeros where sigma_i = 0) and Vt^T in
+ *                     W's own orientation: rows >= cols: U [rows x g] = the normalised vectors, V [cols x g] = Vt^T; rows < cols: U [rows x g] =
+ *                     Vt^T, V [cols x g] = the normalised vectors; so W = U diag(sigma) V^T.  Row pitches ldu, ldv >= g; nothing beyond column g
+ *                     of a row is written.  flag int32[1] (device): zeroed on the stream, then 1 if any sigma_i is not finite.
+ *  anncur_svd_scale_cols  out[r, i] = V[r, i] / sigma[i] where sigma[i] > rcond max(sigma), else 0, for r < n (numpy.linalg.pinv's rule;
+ *                     the pseudo-inverse is out . U^T); rank int32[1] (device) = the number of sigma kept.  0 <= rcond < 1, 1 <= n <= ANNCUR_SVD_MAX_L.
+ * Limits: 1 <= g <= ANNCUR_SVD_MAX_G, L <= ANNCUR_SVD_MAX_L; anything else is ANNCUR_E_INVALID and nothing is written; a missing, short or
+ * misaligned workspace is ANNCUR_E_WORKSPACE.  Every launch is asynchronous on `stream`; nothing is allocated. */
+#define ANNCUR_SVD_MAX_G 2048
+#define ANNCUR_SVD_MAX_L 8192
+size_t anncur_svd_workspace_bytes(int64_t rows, int64_t cols);
+int anncur_svd_init(const void *W, int dtype, int64_t ldw, int64_t rows, int64_t cols, void *workspace, size_t workspace_bytes, void *stream);
+int anncur_svd_sweep(int64_t rows, int64_t cols, void *workspace, size_t workspace_bytes, int32_t *rotations, void *stream);
+int anncur_svd_finish(int64_t rows, int64_t cols, const void *workspace, size_t workspace_bytes, double *sigma, double *U, int64_t ldu, double *V,
+                      int64_t ldv, int32_t *flag, void *stream);
+int anncur_svd_scale_cols(const double *V, int64_t ldv, int64_t n, int32_t g, const double *sigma, double rcond, double *out, int64_t ldo,
+                          int32_t *rank, void *stream);
+
 /* f3: IVF-flat inner-product index (the branch of build_flat_or_ivff_index above 11 000 vectors) -------------------------------
  *   faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT).train / .add / .search     models/nearest_nbr.py:40-52
  * FAISS is not vendored nor pinned by the reference (parity unpinned): restated from the published algorithm, judged on recall
