@@ -74,6 +74,11 @@ __device__ __forceinline__ float f32_unsortable(uint32_t s) {
 	uint32_t u = (s & 0x80000000u) ? (s & 0x7fffffffu) : ~s;
 	return __uint_as_float(u);
 }
+// Candidate count a sweep gives a lane past Q (a padded row of the last row block).  Such a lane runs with the threshold +inf on the operand
+// row of a real query, and `+inf >= +inf` holds: where that query scores +inf the lane passes the filter.  Every candidate store is gated by
+// `count < capacity` and every count write-back by `q < Q`, so a count that starts here (and cannot wrap: fewer than 2^31 items) makes the
+// lane's stores impossible -- its segment does not exist (the candidate region holds Q rows).
+constexpr uint32_t PAD_ROW_COUNT = 0x80000000u;
 // composite key: larger = better score, ties -> smaller index wins.  All keys of one row are distinct.
 __device__ __forceinline__ uint64_t make_key(float v, uint32_t idx) {
 	return ((uint64_t)f32_sortable(v) << 32) | (uint64_t)(0xffffffffu - idx);

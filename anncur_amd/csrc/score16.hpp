@@ -324,7 +324,7 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 	uint32_t fill = w.base;
 	{
 		const int64_t q = q_wave0 + lane;
-		lds_write_u32(w.cnt + (uint32_t)lane * 4u, (p.carry && q < p.Q) ? p.seg_cnt[q * p.nseg + split] : 0u);
+		lds_write_u32(w.cnt + (uint32_t)lane * 4u, q < p.Q ? (p.carry ? p.seg_cnt[q * p.nseg + split] : 0u) : PAD_ROW_COUNT);
 		lds_write_u32(w.jcur + (uint32_t)lane * 4u, 0u);
 	}
 	if (p.ladder_on) {   // (uniform) the wave's 64 level rows: 2 KB = two DMA pieces, waited for with the first tile

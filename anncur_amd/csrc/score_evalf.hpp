@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void evalf_kernel(const FusedParams p, cons
 	uint32_t fill = w.base;
 	{
 		const int64_t q = q_wave0 + lane;
-		lds_write_u32(w.cnt + (uint32_t)lane * 4u, (p.carry && q < p.Q) ? p.seg_cnt[q * p.nseg + split] : 0u);
+		lds_write_u32(w.cnt + (uint32_t)lane * 4u, q < p.Q ? (p.carry ? p.seg_cnt[q * p.nseg + split] : 0u) : PAD_ROW_COUNT);
 	}
 
 	const int j_begin = p.tile_begin + split * p.tiles_per_split, j_end = min(j_begin + p.tiles_per_split, p.tile_end);

@@ -578,7 +578,7 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 #pragma unroll
 	for (int t = 0; t < QT; ++t) {
 		tau[t] = (MODE == 1 && qv[t] < p.Q) ? p.tau[qv[t] * p.tau_stride] + p.tau_bias : INFINITY;
-		ncand[t] = (MODE == 1 && p.carry && qv[t] < p.Q) ? p.seg_cnt[qv[t] * p.nseg + h * p.S + split] : 0u;
+		ncand[t] = qv[t] < p.Q ? ((MODE == 1 && p.carry) ? p.seg_cnt[qv[t] * p.nseg + h * p.S + split] : 0u) : PAD_ROW_COUNT;
 		qcnt[t] = 0;
 	}
 	// candidate segment of (query, lane half, split); sub-tile t adds a wave-uniform stride
@@ -1275,7 +1275,8 @@ __global__ __launch_bounds__(SEL_THREADS) void select_candidates_kernel(
 	// (the threshold the last sweep stage ran with: earlier stages' candidates below it are dropped at the load)
 	float tau = tau_in ? tau_in[q * tau_stride] : -INFINITY;
 	uint64_t tau_key = 0;
-	bool full = !repair && total < k;  // cannot happen with a valid threshold; kept as the last line of defence
+	bool full = !repair && total < k;  // the sweep ran without a usable threshold -- a NaN query row, fewer than k non-NaN group maxima, or a k-th
+	                                    // maximum of -inf (a NaN out of the coarse threshold kernel): nothing was offered, the whole row is rescanned (nfb counts it)
 	if (!full) {
 		for (int sb = 0; sb < nseg; sb += 4) {
 			const int sg = sb + wave;
@@ -1640,7 +1641,7 @@ void plan_workspace(FusedPlan &P, int64_t Q, int k, size_t ctr_bytes, size_t own
 	P.off_owner = region(owner_bytes);                        // chunk owners
 	P.off_lvl = region(ladder_rows * 4 * LADDER_LEVELS);
 	P.off_tau2 = region(P.ladder ? (size_t)Q * 4 : 0);
-	P.off_cand = region((size_t)Q * P.nseg * (size_t)P.capg * 8);
+	P.off_cand = region((size_t)Q * P.nseg * (size_t)P.capg * 8);   // (lanes past Q never store: PAD_ROW_COUNT in csrc/common.hpp)
 	P.total = off;
 	P.ok = true;
 }

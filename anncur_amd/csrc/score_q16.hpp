@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 	uint32_t fill = w.base;
 	if (lane < 32) {
 		const int64_t q = q_wave0 + lane;
-		lds_write_u32(w.cnt + (uint32_t)lane * 4u, (p.carry && q < p.Q) ? p.seg_cnt[q * p.nseg + split] : 0u);
+		lds_write_u32(w.cnt + (uint32_t)lane * 4u, q < p.Q ? (p.carry ? p.seg_cnt[q * p.nseg + split] : 0u) : PAD_ROW_COUNT);
 	}
 
 	// ---- tile schedule: tickets (see score_kernel), or a static contiguous share

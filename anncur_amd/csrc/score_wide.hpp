@@ -117,7 +117,7 @@ __global__ __launch_bounds__(512, 2) void wide_kernel(const WideParams p) {
 		qv[t] = qb + wq * 64 + 32 * t + r;
 		const bool ok = qv[t] < p.Q;
 		tau[t] = (MODE == 1 && ok) ? p.tau[qv[t] * p.tau_stride] + p.tau_bias : INFINITY;
-		ncand[t] = (MODE == 1 && p.carry && ok) ? p.seg_cnt[qv[t] * nseg + sg] : 0u;
+		ncand[t] = ok ? ((MODE == 1 && p.carry) ? p.seg_cnt[qv[t] * nseg + sg] : 0u) : PAD_ROW_COUNT;
 		segoff[t] = (uint32_t)(((wq * 64 + 32 * t + r) * nseg + sg) * p.capg) * 8u;
 	}
 

@@ -132,7 +132,10 @@ int anncur_approx_error_packed(const void *X, int64_t ldx, const void *Et, int64
  * beside the MFMA chain also runs the threshold filter on the accumulator it holds (csrc/score_evalf.hpp).
  * X [Q x Kp], Et [ceil32(I) x Kp] packed bf16 in ITEM order (a tile of Et faces the same 32 columns of A), Kp in {64,128,256};
  * A [Q x I] bf16, 16-byte aligned, lda a multiple of 8 (ANNCUR_E_UNSUPPORTED otherwise: the two calls above).  Workspace:
- * anncur_eval_fused_workspace_bytes (0: shape outside the fused path). */
+ * anncur_eval_fused_workspace_bytes (0: shape outside the fused path).
+ * Non-finite values: the top-k follows anncur_score_topk (NaN never selected, +-inf ordinary candidates, (-inf, -1) pads); err_sq[q] is
+ * NaN if row q of S_hat - A holds a NaN (a NaN in either, or equal infinities in both), else +inf if it holds an infinity; norm_sq[q]
+ * likewise from row q of A alone.  Rows without such a cell are not affected by the others' (anncur_approx_error(_packed): the same). */
 size_t anncur_eval_fused_workspace_bytes(int64_t Q, int64_t I, int32_t Kp, int32_t k);
 int anncur_eval_fused(const void *X, int64_t ldx, const void *Et, int64_t lde, const void *A, int a_dtype, int64_t lda,
                       int64_t Q, int64_t I, int32_t Kp, int32_t k, float *out_val, int32_t *out_idx, float *err_sq, float *norm_sq,
@@ -186,6 +189,12 @@ int anncur_rowwise_topk_gather(const void *A, int dtype, int64_t Q, int64_t I, i
  * >= tau appended to per-lane candidate segments, tau raised between stages; (4) per-query
  * select + sort (a query whose segments overflowed is repaired in the same call by
  * recomputing the affected item range: the result is always the exact top-k of S_hat).
+ * Non-finite scores, on every body and under every flag: S_hat[q,i] is a NaN if a product has a NaN factor or is inf . 0, or if the sum
+ * meets +inf and -inf (in any summation order), and a NaN is never selected; +inf and -inf scores are ordinary candidates (+inf first,
+ * -inf last, ties by ascending row).  A query with fewer than k non-NaN scores gets all of them, then (-inf, -1) pads; a NaN in a row of
+ * X makes that query's result k pads; a NaN row of Et is never returned and costs no other item or query its place (the prepass' group
+ * maxima skip NaN; a query whose sample holds fewer than k non-NaN maxima, or whose k-th maximum is -inf, sweeps without a threshold and
+ * its row is rescanned by the select).
  * out_val float[Q x k], out_idx int32[Q x k]. */
 size_t anncur_score_topk_workspace_bytes(int64_t Q, int64_t I, int32_t Kp, int32_t k);
 int anncur_score_topk_supported(int64_t Q, int64_t I, int32_t Kp, int32_t k);   /* 1 / 0 */
@@ -237,6 +246,12 @@ int anncur_score_topk_ex(const void *X, int64_t ldx, const void *Et, int64_t lde
  * is ONE bf16 inner product of length 3K, so anncur_score_topk_ex sweeps the packed operands unchanged with Kp >= 3K; the dropped
  * lo.lo term and the roundings of lo leave |S_split - S| <= (2^-16 + 3K 2^-23) (|X|.|E|^T) elementwise.  The few candidates it
  * returns are then rescored in true fp32 (anncur_rescore_topk): the values the caller sees are those of anncur_gemm bit for bit.
+ * NaN operands behave as on the fp32 route (the NaN scores are never candidates).  LIMIT: an operand entry that is +-inf (or rounds to
+ * it in bf16) has hi = +-inf and lo = 0, and its term inside the sweep is lo_x hi_e + hi_x lo_e + hi_x hi_e with inf . 0 = NaN or two
+ * infinities of opposite sign -- a NaN unless the other side's entry has a non-zero low part of its high part's sign.  So a score that
+ * anncur_gemm reports as +-inf is a candidate only against those entries and a NaN, never retrieved, against all others (every entry that
+ * is exact in bf16 among them): an item or a query with an infinite entry loses the results the fp32 route returns at +-inf, all of them
+ * or an operand-dependent part.  Keep infinities off this route.
  *
  * anncur_pack_split_bf16: src [n_rows x K] (F32 or BF16, row pitch lds_) -> dst bf16 [n_rows_pad x ldd], ldd >= 3K a multiple of 8,
  *   dst 16-byte aligned.  role 0 (query rows) writes [ lo | hi | hi ], role 1 (item rows) [ hi | lo | hi ], each segment K wide at
