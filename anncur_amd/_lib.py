@@ -24,6 +24,7 @@ LSTSQ_MAX_KQ = 4096   # ANNCUR_LSTSQ_MAX_KQ
 LSTSQ_MAX_G = 512     # ANNCUR_LSTSQ_MAX_G
 SVD_MAX_G = 2048      # ANNCUR_SVD_MAX_G
 SVD_MAX_L = 8192      # ANNCUR_SVD_MAX_L
+SUMSQ_PARTIALS = 1024 # ANNCUR_SUMSQ_PARTIALS
 
 _p32 = POINTER(c_int32)
 
@@ -39,6 +40,7 @@ SIGNATURES = {
 	"anncur_gemm_ex": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int64, c_int64,
 							   c_int64, c_int64, c_int64, ctypes.c_float, ctypes.c_float, c_void_p, c_int64, c_int64, c_void_p]),
 	"anncur_sumsq": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+	"anncur_sumsq_ordered": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
 	"anncur_scale_copy": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, ctypes.c_float, c_void_p, c_void_p]),
 	"anncur_gemm_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
 								ctypes.c_double, ctypes.c_double, c_void_p, c_int64, c_int64, c_void_p]),

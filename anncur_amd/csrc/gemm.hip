@@ -243,6 +243,34 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float *__restrict__ A,
 	for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
 	if ((threadIdx.x & 63) == 0) atomicAdd(out, acc);
 }
+// The same sum in an order that depends on the shape alone: one partial per workgroup (lanes by shuffle, the four waves through LDS in wave
+// order), then ONE workgroup adds the partials (strided by thread, then a fixed tree).  sumsq_kernel's atomic adds arrive in whatever order
+// the waves finish, so its last bits differ from call to call -- and with them every bit of a Newton-Schulz run that is scaled by the sum.
+__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float *__restrict__ A, int64_t n_rows, int64_t n_cols, int64_t lda, float *__restrict__ partials) {
+	__shared__ float s_wave[4];
+	float acc = 0.f;
+	const int64_t total = n_rows * n_cols;
+	for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+		const float v = A[(i / n_cols) * lda + (i % n_cols)];
+		acc += v * v;
+	}
+	for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
+	if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = acc;
+	__syncthreads();
+	if (threadIdx.x == 0) partials[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+__global__ __launch_bounds__(256) void sumsq_final_kernel(const float *__restrict__ partials, int n, float *__restrict__ out) {
+	__shared__ float s[256];
+	float acc = 0.f;
+	for (int i = threadIdx.x; i < n; i += 256) acc += partials[i];
+	s[threadIdx.x] = acc;
+	__syncthreads();
+	for (int d = 128; d > 0; d >>= 1) {
+		if ((int)threadIdx.x < d) s[threadIdx.x] += s[threadIdx.x + d];
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) out[0] = s[0];
+}
 __global__ __launch_bounds__(256) void scale_copy_kernel(const float *__restrict__ src, int64_t s0, int64_t s1, float *__restrict__ dst, int64_t d0,
 														  int64_t d1, int64_t M, int64_t N, float alpha, const float *__restrict__ inv_scale) {
 	const float a = inv_scale ? alpha / inv_scale[0] : alpha;
@@ -259,6 +287,22 @@ extern "C" int anncur_sumsq(const float *A, int64_t n_rows, int64_t n_cols, int6
 	ANNCUR_REQUIRE(A, ANNCUR_E_INVALID, "sumsq: null pointer");
 	const int64_t blocks = ceil_div64(n_rows * n_cols, 256 * 8);
 	hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, st, A, n_rows, n_cols, lda, out);
+	ANNCUR_LAUNCH_OK();
+	return ANNCUR_OK;
+}
+
+extern "C" int anncur_sumsq_ordered(const float *A, int64_t n_rows, int64_t n_cols, int64_t lda, float *partials, float *out, void *stream) {
+	ANNCUR_REQUIRE(out && n_rows >= 0 && n_cols >= 0 && lda >= n_cols, ANNCUR_E_INVALID, "sumsq_ordered: bad arguments");
+	hipStream_t st = (hipStream_t)stream;
+	if (n_rows * n_cols == 0) {
+		ANNCUR_HIP_OK(hipMemsetAsync(out, 0, 4, st));
+		return ANNCUR_OK;
+	}
+	ANNCUR_REQUIRE(A && partials, ANNCUR_E_INVALID, "sumsq_ordered: null pointer");
+	int64_t blocks = ceil_div64(n_rows * n_cols, 256 * 8);
+	if (blocks > ANNCUR_SUMSQ_PARTIALS) blocks = ANNCUR_SUMSQ_PARTIALS;
+	hipLaunchKernelGGL(sumsq_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A, n_rows, n_cols, lda, partials);
+	hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, st, (const float *)partials, (int)blocks, out);
 	ANNCUR_LAUNCH_OK();
 	return ANNCUR_OK;
 }

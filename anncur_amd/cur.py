@@ -51,7 +51,7 @@ COMPUTE_DTYPES = ("fp32", "bf16", "bf16x3")
 
 
 AUTO_COND_LIMIT = 1e3   # pinv_backend "auto": the device result is taken while cond_2(W) stays below this (numpy's fp32 SVD is then good to ~1e-4)
-AUTO_COND_SAFETY = 1.25  # ... times this: the power-iteration estimate of cond_2 is a lower bound
+AUTO_COND_SAFETY = 1.25  # ... times this: the power-iteration estimate of cond_2 is a lower bound, at most this factor short (pinv._spectral_norm_sq)
 AUTO_SQUARE_RATIO, AUTO_SQUARE_MIN = 0.9, 32   # "auto": blocks with min(shape) > 0.9 max(shape) (and at least 32 wide) go straight to the host
 
 
@@ -117,7 +117,8 @@ def _pinv(M, device, backend, rcond=None, info=None):
 			return _pinv_host(M).to(device)
 		# auto: a block with cond_2 <= 1e3 converges within ~2 log2(cond) + 6 = 26 steps; one that has not by 36 is beyond the limit
 		X, info = pinv_newton_schulz_f64(M.to(device), return_info=True, max_iters=36 if backend == "auto" else 64)
-		# cond_2 comes from two 8-step power iterations, each a LOWER bound (a few per cent): judged with a safety factor
+		# cond_2 comes from two power iterations (pinv._spectral_norm_sq: 2^POWER_SQUARINGS steps), each a LOWER bound: cond_2 <= true <= AUTO_COND_SAFETY * cond_2 is held
+		# by test on clustered, geometric and power-law spectra (tests/test_gpu_pinv_gate.py), hence the safety factor
 		if info["converged"] and (backend == "device" or AUTO_COND_SAFETY * info["cond_2"] <= AUTO_COND_LIMIT):
 			return X
 		LOGGER.info("pinv %s: cond_2 = %.3g after %d iterations (converged: %s) -> host numpy.linalg.pinv", backend, info["cond_2"], info["iterations"], info["converged"])

@@ -165,14 +165,20 @@ def gemm(A, B, out=None, out_dtype=torch.float32, alpha=1.0, beta=0.0, cin=None)
 
 
 @_on_device
-def sumsq(A, out=None):
-	"""Frobenius norm squared of an fp32 matrix -> 1-element device tensor (no host sync)."""
+def sumsq(A, out=None, ordered=True):
+	"""Frobenius norm squared of an fp32 matrix -> 1-element device tensor (no host sync).  ordered (default): the sum is taken in an order
+	that depends on the shape alone, so equal inputs give equal bits (anncur_sumsq_ordered); False: partial sums meet by atomic adds in
+	the order the waves finish (anncur_sumsq), and the last bits differ from call to call."""
 	_dev(A)
 	A = _rowmajor(A)
 	if A.dtype != torch.float32:
 		raise TypeError("sumsq takes fp32")
 	out = torch.empty(1, dtype=torch.float32, device=A.device) if out is None else out
-	check(_lib.load().anncur_sumsq(_p(A), A.shape[0], A.shape[1], _ld(A), _p(out), _stream()), "sumsq")
+	if ordered:
+		partials = torch.empty(_lib.SUMSQ_PARTIALS, dtype=torch.float32, device=A.device)
+		check(_lib.load().anncur_sumsq_ordered(_p(A), A.shape[0], A.shape[1], _ld(A), _p(partials), _p(out), _stream()), "sumsq_ordered")
+	else:
+		check(_lib.load().anncur_sumsq(_p(A), A.shape[0], A.shape[1], _ld(A), _p(out), _stream()), "sumsq")
 	return out
 
 
@@ -211,7 +217,8 @@ _DT64 = {torch.float32: F32, torch.bfloat16: BF16, torch.float64: _lib.F64}
 
 @_on_device
 def convert_f64(src, dst, alpha=1.0, divide_by=None):
-	"""dst[i, j] = alpha / divide_by[0] * src[i, j]; f32 / bf16 / f64 -> f64, or f64 -> f32 (one rounding); any strides."""
+	"""dst[i, j] = (alpha * src[i, j]) / divide_by[0] in fp64: the product rounded, then the division rounded (alpha * src[i, j] without a
+	divisor); f32 / bf16 / f64 -> f64, or f64 -> f32 (one more rounding, to nearest even); any strides."""
 	_dev(src, dst)
 	if tuple(src.shape) != tuple(dst.shape) or src.dim() != 2:
 		raise ValueError("convert_f64: 2-D tensors of equal shape")

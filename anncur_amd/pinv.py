@@ -12,13 +12,16 @@ accuracy ~ cond(W) * 6e-8 like an fp32 SVD, singular values below ~1e-4 * sigma_
 The device routes matter for large anchor counts, where the host SVD dominates the index build (2048 x 1024: 1.4 s on the host, a
 few ms here).  A third route, pinv_svd (backend "svd", opt-in), decomposes the block by Jacobi rotations in fp64 and is the only one
 that can leave singular values below a cutoff out: no faster than the host call, but it truncates and reports the spectrum."""
+import math
+
 import torch
 
 from . import ops
 
 
 def pinv_newton_schulz(W, max_iters=80, check_every=4, rtol=1e-6):
-	"""W: [m x n] fp32 / bf16 tensor on the GPU -> W^+ [n x m] fp32 on the GPU."""
+	"""W: [m x n] fp32 / bf16 tensor on the GPU -> W^+ [n x m] fp32 on the GPU.  Equal inputs give equal bits: the GEMMs add in k order and
+	the two sums the run depends on (the start scale, the stopping rule) are ops.sumsq's ordered ones."""
 	if W.dtype != torch.float32:
 		W = ops.convert(W, torch.float32)
 	m, n = W.shape
@@ -46,22 +49,44 @@ def pinv_newton_schulz(W, max_iters=80, check_every=4, rtol=1e-6):
 	return X
 
 
-def _spectral_norm_sq(M, iters=8):
-	"""||M||_2^2 by power iteration on M^T M (fp64 GEMVs on the device, one host read at the end).  A lower bound that is within
-	a few per cent after 8 iterations for the spectra met here; callers add their own safety factor.
-	M: [m x n] fp64.  The iterate is rescaled by 1 / ||.||^2 (a scaling is all power iteration needs; no square root kernel)."""
+POWER_SQUARINGS = 5   # _spectral_norm_sq applies G^(2^5) to its start vector: 32 power steps for the price of 5 small GEMMs
+
+
+def _spectral_norm_sq(M, squarings=POWER_SQUARINGS):
+	"""||M||_2^2 by power iteration on the Gram matrix of M's short side, G = A A^T [g x g] (A = M or M^T, g = min(m, n)): G is squared
+	`squarings` times -- G^(2^k) in k GEMMs of g^3, where the same number of single steps took 2^(k+1) GEMVs over all of M, each a launch that
+	fills a few workgroups -- then v = G^(2^k) v_0, and the result is the Rayleigh quotient ||A^T v||^2 / ||v||^2 on M itself.  Two host
+	reads: ||M||_F^2 at the start, the quotient at the end.
+	G is divided once by a power of two >= ||M||_F^2 >= sigma_max^2: its eigenvalues are then <= 1, the largest > 1 / (2 g), so 2^5 powers
+	neither overflow nor lose the top direction ((2 g)^-32 >= 2^-672 for g <= 2^20), and being a power of two the scale changes no mantissa:
+	the result is the same bits whichever one is taken, and scales exactly with a power-of-two multiple of M.
+	The quotient of ANY v is a lower bound, so the result is never above sigma_max^2 except by rounding (1e-9 relative is ample); how far
+	below depends on how much of v_0 lies along the top singular vector and on the gap under sigma_max.  What is held by test on the spectrum
+	families of tests/pinv_numpy.py (power-law, geometric, flat, two clusters with sigma_2 / sigma_1 = 0.8 .. 0.96; up to 2048 x 1024,
+	cond_2 300 .. 1050) is sigma_max^2 / 1.25^2 <= result <= sigma_max^2 (1 + 1e-9), and for cond_2, the root of two such estimates,
+	cond_2 <= true <= 1.25 cond_2 (cur.AUTO_COND_SAFETY).  That serves both callers: X_0 = W^T / (1.1 s2) contracts while
+	s2 > sigma_max^2 / 2.2.  A slowly converging quotient sits near sigma_2^2, so a cluster with (sigma_2 / sigma_1)^2 >= 0.8 is inside the
+	factor at any step count; the steps are there for the clusters below that, which the 8 single steps this replaced did not leave (one
+	estimate up to 1.55 short, cond_2 up to 1.33).  Nothing covers a v_0 that is orthogonal to the top singular vector to many digits.
+	M: [m x n] fp64.  0.0 for a zero matrix and for one whose ||M||_F^2 is not finite."""
 	m, n = M.shape
-	v = torch.full((n, 1), 1.0 / n, dtype=torch.float64, device=M.device)
-	v[::2] *= 1.5                                            # (not orthogonal to anything structured)
-	t = torch.empty((m, 1), dtype=torch.float64, device=M.device)
-	u = torch.empty((n, 1), dtype=torch.float64, device=M.device)
+	if not M.is_contiguous():
+		M = M.contiguous()
 	nrm = torch.empty(2, dtype=torch.float64, device=M.device)
-	for _ in range(iters):
-		ops.gemm_f64(M, v, out=t)                            # t = M v
-		ops.gemm_f64(M.t(), t, out=u)                        # u = M^T M v
-		ops.diff_sumsq_f64(u, out=nrm)
-		ops.convert_f64(u, v, 1.0, divide_by=nrm[1:2])       # v = u / ||u||^2
-	ops.gemm_f64(M, v, out=t)
+	f2 = float(ops.diff_sumsq_f64(M, out=nrm)[1].item())
+	if not (0.0 < f2 < float("inf")):
+		return 0.0
+	A = M if m <= n else M.t()                               # [g x L]: the short side's vectors as rows
+	g = min(m, n)
+	G = ops.gemm_f64(A, A.t(), alpha=2.0 ** -math.frexp(f2)[1])   # (frexp: f2 = x 2^e with x in [0.5, 1), so 2^e > f2)
+	B = torch.empty_like(G)
+	for _ in range(squarings):
+		ops.gemm_f64(G, G, out=B)
+		G, B = B, G
+	v0 = torch.full((g, 1), 1.0 / g, dtype=torch.float64, device=M.device)
+	v0[::2] *= 1.5                                           # (not orthogonal to anything structured)
+	v = ops.gemm_f64(G, v0)                                  # v = G^(2^k) v_0
+	t = ops.gemm_f64(A.t(), v)                               # [L x 1]
 	num = float(ops.diff_sumsq_f64(t, out=nrm)[1].item())
 	den = float(ops.diff_sumsq_f64(v, out=nrm)[1].item())
 	return num / den if den > 0 else 0.0
@@ -71,7 +96,7 @@ def pinv_newton_schulz_f64(W, max_iters=64, check_from=4, rtol=1e-10, return_inf
 	"""Parity-grade pseudo-inverse: Newton-Schulz in DOUBLE precision on the fp64 matrix cores (anncur_gemm_f64), the result
 	rounded to fp32 once.  W: [m x n] fp32 / bf16 on the GPU -> W^+ [n x m] fp32 on the GPU.
 
-	X_0 = W^T / (1.1 sigma_max^2) with sigma_max from a short power iteration (iterations ~ 2 log2 cond(W) + 4 instead of
+	X_0 = W^T / (1.1 sigma_max^2) with sigma_max from a power iteration on the Gram matrix (_spectral_norm_sq; iterations ~ 2 log2 cond(W) + 4 instead of
 	+ log2 rank with the Frobenius scaling).  In fp64 the iteration resolves singular values down to ~2^-(iters/2) of the
 	largest, i.e. it converges to the exact pseudo-inverse of the fp32 matrix W for any conditioning the fp32 SVD of
 	numpy.linalg.pinv can resolve; what separates the two is then numpy's own fp32 round-off (~cond(W) * 6e-8).  Stops when
@@ -80,8 +105,8 @@ def pinv_newton_schulz_f64(W, max_iters=64, check_from=4, rtol=1e-10, return_inf
 	to fp32 precision (numpy then inverts singular values that are fp32 round-off, and so would this iteration, to different
 	noise) -- info["converged"] is False and the caller (cur._pinv) hands such a block to the host's LAPACK call, as the reference
 	does.
-	info: iterations, converged, cond_2 = ||W||_2 ||W^+||_2 (both by power iteration: the caller's handle on how far numpy's
-	fp32 SVD can be trusted), cond_F."""
+	info: iterations, converged, cond_2 = ||W||_2 ||W^+||_2 (both by _spectral_norm_sq, so a lower bound, at most 1.25 short on the
+	families it is tested on: the caller's handle on how far numpy's fp32 SVD can be trusted), cond_F."""
 	m, n = W.shape
 	Wd = torch.empty((m, n), dtype=torch.float64, device=W.device)
 	ops.convert_f64(W, Wd)

@@ -84,8 +84,14 @@ int anncur_gemm_ex(const void *A, int a_dtype, int64_t a_sm, int64_t a_sk,
                    int64_t M, int64_t N, int64_t K, float alpha, float beta,
                    const float *Cin, int64_t i_sm, int64_t i_sn, void *stream);
 /* out[0] = sum of squares of an fp32 matrix (Frobenius norm squared); dst(i,j) = alpha / (divide_by ? divide_by[0] : 1) * src(i,j)
- * with arbitrary strides (scaled transpose).  Helpers of the on-device pseudo-inverse; no host synchronisation. */
+ * with arbitrary strides (scaled transpose).  Helpers of the on-device pseudo-inverse; no host synchronisation.
+ * anncur_sumsq combines its waves' partial sums by atomic adds, in the order they finish: the last bits of out[0] differ from call to call.
+ * anncur_sumsq_ordered adds in an order that depends on the shape alone (one partial per workgroup in `partials`, ANNCUR_SUMSQ_PARTIALS
+ * floats of caller-owned workspace, nothing pre-filled, then one workgroup over them): equal inputs give equal bits.  pinv.py scales and
+ * stops its fp32 iteration by this sum, so it takes the ordered one. */
+#define ANNCUR_SUMSQ_PARTIALS 1024
 int anncur_sumsq(const float *A, int64_t n_rows, int64_t n_cols, int64_t lda, float *out, void *stream);
+int anncur_sumsq_ordered(const float *A, int64_t n_rows, int64_t n_cols, int64_t lda, float *partials, float *out, void *stream);
 int anncur_scale_copy(const float *src, int64_t s0, int64_t s1, float *dst, int64_t d0, int64_t d1, int64_t M, int64_t N,
                       float alpha, const float *divide_by, void *stream);
 
@@ -93,8 +99,10 @@ int anncur_scale_copy(const float *src, int64_t s0, int64_t s1, float *dst, int6
  * double precision, rounded to fp32 once at the end): replaces the host call
  *   U = numpy.linalg.pinv(W)                 eval/matrix_approx_zeshel.py:47,49
  * when the caller asks for it (pinv_backend "device" / "auto").  Strided like anncur_gemm_ex; products and sums in fp64 on
- * v_mfma_f64_16x16x4_f64.  anncur_convert_f64: dst(i,j) = alpha / (divide_by ? divide_by[0] : 1) * src(i,j) for the dtype pairs
- * F32->F64, BF16->F64, F64->F64 (scaled copy / transpose) and F64->F32 (one rounding).  anncur_diff_sumsq_f64:
+ * v_mfma_f64_16x16x4_f64.  anncur_convert_f64: dst(i,j) = (alpha * src(i,j)) / divide_by[0] in fp64 -- one rounded product, then one rounded
+ * division, in that order (pinv.py's results depend on it) -- or alpha * src(i,j) where divide_by is NULL, for the dtype pairs
+ * F32->F64, BF16->F64 (widened exactly, denormals included), F64->F64 (scaled copy / transpose) and F64->F32 (one more rounding, to
+ * nearest even); any other pair is ANNCUR_E_INVALID and writes nothing, M * N == 0 returns without a launch.  anncur_diff_sumsq_f64:
  * out2 = {sum (x - y)^2, sum x^2} over n contiguous doubles (y may be NULL), device doubles, no host synchronisation. */
 int anncur_gemm_f64(const double *A, int64_t a_sm, int64_t a_sk, const double *B, int64_t b_sk, int64_t b_sn,
                     double *C, int64_t c_sm, int64_t c_sn, int64_t M, int64_t N, int64_t K,
