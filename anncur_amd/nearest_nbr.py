@@ -38,7 +38,9 @@ class FlatIPIndex:
 	"""Exact maximum-inner-product search on the GPU.  fp32 by default (dense fp32-MFMA GEMM + exact scan);
 	dtype="bf16" uses the fused score+top-k kernel when the dimension fits (d <= 4096: the register-resident bodies up to 512, the
 	K-general wide kernel above); dtype="bf16x3" keeps fp32 parity on that kernel: the stored fp32 vectors split into bf16 hi + lo
-	parts (3 d <= 4096), the fused kernel for the candidates, an fp32 rescore for the values -- those of the fp32 route bit for bit."""
+	parts (3 d <= 4096), the fused kernel for the candidates, an fp32 rescore for the values -- those of the fp32 route bit for bit.
+	Score ties: the fp32 route orders them by the smaller id; the bf16 route on the fused kernel by the smaller ROW of its descending-norm copy
+	(256 norm buckets, id order inside a bucket), so by the smaller id only among vectors of one norm bucket (tests/test_gpu_ivf_index_exact.py)."""
 
 	def __init__(self, d, dtype="fp32", device=None):
 		self.d = d
@@ -94,8 +96,21 @@ class IVFFlatIPIndex:
 	inner-product quantiser, centroid = mean of its points RENORMALISED TO UNIT L2 NORM (IndexIVF sets cp.spherical = true for
 	METRIC_INNER_PRODUCT: fvec_renorm_L2 after every update, and after the re-seeding of empty lists -- with arg-max inner-product
 	assignment an unnormalised mean of large-norm points would keep attracting points and the lists would grow unbalanced; spherical=False
-	restores the plain means), an empty list re-seeded by splitting a large one.  FAISS' random draws cannot be reproduced, so parity is
-	unpinned and the index is judged on recall and list balance.  Results are deterministic for a given seed."""
+	restores the plain means), an empty list re-seeded by splitting a large one.  FAISS' random draws cannot be reproduced, so parity with
+	FAISS is unpinned and the index is judged on recall and list balance.  Results are deterministic for a given seed.
+
+	What IS pinned is the algorithm stated here: tests/ivf_index_numpy.py restates train / add / search on the host (train_ref, add_ref,
+	search_ref; flat_search_ref for FlatIPIndex' fp32 route), and tests/test_gpu_ivf_index_exact.py holds both classes to it BIT FOR BIT, with no
+	tolerance, on integer data in [-8, 8] (n = 1500 .. 4096 and 11 001, d = 16, 24, 64, 130, nlist = 7, 16, 64, 104; FlatIPIndex fp32 on fixed-point
+	grid data, bf16 on integers): scores against centroids are ops.gemm's k-ordered fp32 fmaf chain, top-1 / top-nprobe break ties to the smaller
+	list, lists are a stable counting sort, a mean is sum * (1.0f / count), the sub-sample is sorted, the split draws one list per empty list
+	with weight max(count - 1, 0) and perturbs by 1 +- 2^-10 on alternating columns, renormalisation comes after the split and on the initial
+	centroids; add() rebuilds every list from all vectors; the search pads queries with zeros and breaks score ties by vector id (ivf_scan), by
+	probe slot then list position (the batched routes); an exclusion list of e ids is filtered from k + e candidates.  94 tests, 6.2 s on an
+	MI355X; ten Python mutants of this file and of ops.score_topk_dense each fail named tests (table in the test's docstring).
+	ops.renorm_rows, pinned to the bit as well (1.0f / sqrtf(tot) was measured to be correctly rounded on the device): a row whose sum of
+	squares is not > 0 -- all zero, a NaN present, every square underflowing -- stays as it is; squares that overflow give tot = inf, inv = 0,
+	a row of (signed) zeros; one infinite element becomes NaN, the others zeros; nothing outside the row's n_cols columns is written."""
 
 	def __init__(self, d, nlist, device=None, niter=10, seed=1234, max_points_per_centroid=256, spherical=True, dtype="fp32"):
 		self.d, self.nlist = int(d), int(nlist)

@@ -26,11 +26,15 @@ Mutations tried on scratch builds when this file was written (73 tests, 6.5 s on
     step that straddles a quarter boundary drops the other quarter's lanes; the rounding only aligns the reads.  An equivalent mutant.
 Needs an MI355X."""
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 from hypothesis import HealthCheck, given, settings, strategies as st
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from ivf_index_numpy import lists_search_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 # Deterministic by default (the same examples every run); ANNCUR_FUZZ=1 draws fresh ones and ANNCUR_FUZZ_EXAMPLES=n draws more.
@@ -80,41 +84,8 @@ def _poisoned(ops, call):
 
 
 # ------------------------------------------------------------------ the host reference
-def _reference(X, Q, off, ids, probe, k, ties, lmax=1):
-	"""The search on the host.  X [n x d], Q [nq x d] integer arrays, off [nlist + 1], ids [n], probe [nq x nprobe].  Per query: walk the probe slots
-	in order, skip ids outside [0, nlist), concatenate the surviving lists' rows (list order) into the packed row, exact integer scores, sort
-	descending with the tie rule, take min(k, len), map through ids; (-inf, -1) past that.
-	ties -> {rule: (values fp32 [nq x k], ids int32 [nq x k])} for each rule asked for:
-	  "packed":  the smaller packed column (a stable descending sort of the packed row);
-	  "slotted": the smaller column slot * lmax + position in the list (the [nq x nprobe * lmax] matrix of ivf_scan_grouped);
-	  "id":      the smaller vector id (ivf_scan's selection key).
-	The sort is a top-k over the int64 keys score * 2^32 - tiebreak: the keys of a row are distinct, so it IS the stable descending sort.
-	The products run in fp64 (every partial sum is an integer below 2^53: exact), then are taken as int64."""
-	nq, nlist = Q.shape[0], len(off) - 1
-	Xf, Qf = X.astype(np.float64), Q.astype(np.float64)
-	out = {t: (np.full((nq, k), -np.inf, dtype=np.float32), np.full((nq, k), -1, dtype=np.int32)) for t in ties}
-	for q0 in range(0, nq, 512):
-		S = Qf[q0:q0 + 512] @ Xf.T
-		for j in range(S.shape[0]):
-			rows, cols = [], []
-			for slot, l in enumerate(probe[q0 + j]):
-				if 0 <= l < nlist:
-					r = np.arange(off[l], off[l + 1], dtype=np.int64)
-					rows.append(r)
-					cols.append(slot * lmax + (r - off[l]))
-			if not rows: continue
-			rows = np.concatenate(rows)
-			if rows.size == 0: continue
-			s = S[j, rows].astype(np.int64)
-			assert (s == S[j, rows]).all() and np.abs(s).max(initial=0) < 1 << 24
-			m = min(k, rows.size)
-			for t in ties:
-				tb = np.arange(rows.size, dtype=np.int64) if t == "packed" else np.concatenate(cols) if t == "slotted" else ids[rows].astype(np.int64)
-				assert t == "packed" or np.unique(tb).size == tb.size, "tie-break keys of one row must be distinct"
-				order = torch.topk(torch.from_numpy(s * (1 << 32) - tb), m).indices.numpy()
-				out[t][0][q0 + j, :m] = s[order]
-				out[t][1][q0 + j, :m] = ids[rows[order]]
-	return out
+# (moved to tests/ivf_index_numpy.py, where the index classes' host restatement shares it; unchanged)
+_reference = lists_search_ref
 
 
 def _equal(got, want, what):
