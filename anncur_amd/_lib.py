@@ -25,6 +25,7 @@ LSTSQ_MAX_G = 512     # ANNCUR_LSTSQ_MAX_G
 SVD_MAX_G = 2048      # ANNCUR_SVD_MAX_G
 SVD_MAX_L = 8192      # ANNCUR_SVD_MAX_L
 SUMSQ_PARTIALS = 1024 # ANNCUR_SUMSQ_PARTIALS
+RANK_MAX_T = 1024     # ANNCUR_RANK_MAX_T
 
 _p32 = POINTER(c_int32)
 
@@ -104,6 +105,9 @@ SIGNATURES = {
 	"anncur_svd_finish": (c_int, [c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
 	"anncur_svd_scale_cols": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, ctypes.c_double, c_void_p, c_int64, c_void_p, c_void_p]),
 	"anncur_overlap_counts": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, _p32, _p32, c_int32, c_void_p, c_void_p]),
+	"anncur_rank_in_rows": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+	"anncur_score_rank_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+	"anncur_score_rank": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 	"anncur_copy_bytes": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
 	"anncur_ivf_build_lists": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
 	"anncur_ivf_list_means": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),

@@ -307,6 +307,19 @@ class CURApprox(object):
 		v, i = self.topk_in_row_device(sparse_rows, k, exclude=exclude)
 		return TopK(self._back(v, sparse_rows), self._back(i.long(), sparse_rows))
 
+	def rank_route(self, t):
+		"""The route rank_in_row takes for t targets per query: "bf16" (fused, S_hat never written) or "dense"."""
+		return _rank_route_name(self, t)
+
+	def rank_in_row(self, sparse_rows, ids, return_scores=False):
+		"""The inverse of topk_in_row: rank[q, j] = the position of item ids[q, j] in row q of the approximation sorted by score descending,
+		ties to the smaller id (ops.rank_in_rows states the contract: -1 for a hole or a NaN score, at most ops.RANK_MAX_T targets per query).
+		int32 [Q x t], on the device of sparse_rows; with return_scores (rank, score).  compute_dtype "bf16" with Kp <= 512 never writes S_hat."""
+		if self.approx_preference != "rows":
+			raise NotImplementedError("This is not designed to give good approx of rows as C and U matrix are multiplied together. Build index w/ approx_preference = rows instead.")
+		res = _route_rank(self, self._to_dev(sparse_rows), ids, return_scores)
+		return tuple(self._back(r, sparse_rows) for r in res) if return_scores else self._back(res, sparse_rows)
+
 	def eval_rows(self, sparse_rows, exact_rows, k):
 		"""One grid cell of entry point A for these query rows (crossenc.py:84,106,146-147): (approximate top-k of S_hat, per-row
 		sum (S_hat - A)^2, per-row sum A^2).  On the bf16 route with Kp <= 256 and a bf16 exact matrix this is ONE sweep
@@ -412,6 +425,51 @@ def _route_topk(op, X, k, exclude=None):
 	if op.compute_dtype == "bf16" and X.dtype != torch.bfloat16:
 		X = ops.convert(X, torch.bfloat16)
 	return _filtered(ops.score_topk_dense(X, Et, kc), excl, k)
+
+
+def _rank_ids_arg(ids, device):
+	"""Target ids as the index classes take them -- a list, a NumPy array or a tensor, int32 or int64, e.g. the indices of a top-k or a slice of
+	them -- as a contiguous int32 tensor on `device`.  A value outside int32 cannot be an item id: ValueError, before the narrowing hides it."""
+	ids = ids if torch.is_tensor(ids) else torch.as_tensor(np.asarray(ids))
+	if ids.dtype not in (torch.int32, torch.int64):
+		raise TypeError(f"rank: ids must be int32 or int64 (got {ids.dtype})")
+	if ids.dim() != 2:
+		raise ValueError(f"rank: ids must be [Q x t] (got {tuple(ids.shape)})")
+	if ids.dtype == torch.int64:
+		if ids.numel():
+			lo, hi = (int(v) for v in torch.aminmax(ids))
+			if lo < -1 or hi >= 1 << 31:
+				raise ValueError(f"rank: id {lo if lo < -1 else hi} is no item id")
+		ids = ids.to(torch.int32)
+	return ids.to(device).contiguous()
+
+
+def _rank_route_name(op, t):
+	"""Which of the two rank routes `op` takes for t targets per query: "bf16" (ops.score_rank on the item-order packed operand, S_hat never
+	written) or "dense" (ops.rank_dense on the fp32 item operand -- "fp32", "bf16x3", Kp > 512 and whatever the fused route refuses: the
+	values the "bf16x3" top-k returns)."""
+	if op.compute_dtype == "bf16" and op._Etp is not None and ops.score_rank_ok(op._Etp.shape[1], op.m, t):
+		return "bf16"
+	return "dense"
+
+
+def _route_rank(op, X, ids, return_scores=False):
+	"""Ranks of the items ids [Q x t] under X . Et^T over the item operand of `op` (ops.rank_in_rows states the contract), beside _route_topk."""
+	ids = _rank_ids_arg(ids, X.device)
+	if _rank_route_name(op, ids.shape[1]) == "bf16":
+		return ops.score_rank(ops.pack_bf16(X, op._Etp.shape[1]), op._Etp, op.m, ids, return_scores)
+	if X.dtype != torch.float32:
+		X = ops.convert(X, torch.float32)
+	return ops.rank_dense(X, op._Et, ids, return_scores=return_scores)
+
+
+class _RankOperand(object):
+	"""An item-major fp32 matrix Et [m x K] prepared for _route_rank: "bf16" packs it in ITEM order where the fused route takes the width."""
+
+	def __init__(self, Et, compute_dtype):
+		self._Et, self.m, self.compute_dtype = Et, Et.shape[0], compute_dtype
+		kp = ops.padded_k(Et.shape[1])
+		self._Etp = ops.pack_bf16(Et, kp, row_multiple=32) if compute_dtype == "bf16" and kp is not None and kp <= 512 else None
 
 
 SAMPLE_ROUTE = "sample-dense"   # the one route of _route_sample, as the adaptive search's trace names it
@@ -532,6 +590,17 @@ class CURRowIndex(object):
 		exclude: items left out of the result, as for CURApprox.topk_in_row_device (e.g. ops.exclusion(self.col_idxs, ...), built once:
 		the anchor items, whose exact scores the caller holds already)."""
 		return _route_topk(self, X, k, exclude)
+
+	def rank_route(self, t):
+		"""The route rank_of() takes for t targets per query: "bf16" (fused, S_hat never written) or "dense"."""
+		return _rank_route_name(self, t)
+
+	def rank_of(self, X, ids, return_scores=False):
+		"""The inverse of topk: X [q x kc], ids [q x t] (int32 / int64, -1 = hole) -> rank int32 [q x t] on the GPU, the position of each item in
+		its query's approximate ranking (score descending, ties to the smaller id; ops.rank_in_rows states the contract); with return_scores
+		(rank, score).  rank_of(X, exact_top_k_ids) is the whole recall curve at once: retrieval.overlap_from_ranks / rank_curve.
+		(Not `rank`: that name is the attribute pinv_backend "svd" fills with the anchor block's numerical rank.)"""
+		return _route_rank(self, X, ids, return_scores)
 
 	def sample(self, X, k, temperature=1.0, seed=0, stream=0, row_keys=None, exclude=None):
 		"""X [q x kc] -> TopK(perturbed keys f32, indices int32) on the GPU: k items per query drawn without replacement with probability

@@ -323,9 +323,19 @@ def _sweep_adaptive_cells(A_test_dev, A_train_dev, anc, exact, top_k_vals, top_k
 	return out
 
 
+RANK_METRICS_KEY = "approx_rank"   # --rank_metrics of entry point B: res["top_k=k"][RANK_METRICS_KEY]["anc_n_m=.._anc_n_e=.."]
+
+
+def _put_rank_metrics(res, ranks, top_k_vals, k_max, anc_key):
+	"""ranks [Q x k_max]: the approximate ranks of the exact top-k_max items, in exact order."""
+	from .retrieval import rank_curve
+	for k, metrics in rank_curve(ranks, [k for k in top_k_vals if k <= k_max]).items():
+		res[f"top_k={k}"][RANK_METRICS_KEY][anc_key] = metrics
+
+
 def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None, progress=None, key_n_m=None, pinv_backend="auto", rerank_pool="retrieved",
 						literal_rerank=False, adaptive_rounds=1, adaptive_incremental=False, adaptive_strategy="topk", adaptive_temperature=1.0, adaptive_seed=0,
-						anchor_selection="random", pinv_rcond=None):
+						anchor_selection="random", rank_metrics=False, pinv_rcond=None):
 	"""eval_method == "cur" of entry point B for one seed (splits.py:286-303 + 399-429).
 	rerank_pool "retrieved+anchors": every cell also reports, under POOL_PREFIX, the metrics of the pool anchor items + k_retvr NEW items (a
 	second retrieval per anchor count, with the anchor items excluded, at the largest k_retvr with k_retvr + n_anc <= pool_cell_limit).
@@ -337,9 +347,14 @@ def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None
 	4.4f): the anchor items of every count are the sorted first n_anc of ONE column-pivoted QR selection from A_train; `seed` is not used,
 	counts the selection cannot deliver are left out and logged once (_pivoted_anchor_counts), n_anc = 0 keeps its branch; the pool and
 	adaptive modes see only the anchor list.
-	pinv_rcond: the rcond= of every index built here (pinv_backend "svd" / "numpy": the cutoff of pinv(W); None = the reference's 1e-15, today's call)."""
+	pinv_rcond: the rcond= of every index built here (pinv_backend "svd" / "numpy": the cutoff of pinv(W); None = the reference's 1e-15, today's call).
+	rank_metrics (--rank_metrics; with adaptive_rounds 1): every top_k also reports, under res["top_k=k"]["approx_rank"]["anc_n_m=.._anc_n_e=.."],
+	retrieval.rank_curve of the approximate ranks of the exact top-k items -- one cur.rank_in_row call per anchor count: the whole
+	recall curve, beyond ANNCUR_MAX_TOPK too, and the smallest k_retvr that reaches a recall."""
 	with_pool = _check_rerank_pool(rerank_pool)
 	rcond_kw = {} if pinv_rcond is None else {"rcond": pinv_rcond}
+	if rank_metrics and adaptive_rounds != 1:
+		raise ValueError(f"rank_metrics needs adaptive_rounds = 1 (got {adaptive_rounds}): an adaptive pool is no prefix of one ranking")
 	if anchor_selection not in ANCHOR_SELECTIONS:
 		raise ValueError(f"anchor_selection = {anchor_selection} not supported (one of {', '.join(ANCHOR_SELECTIONS)})")
 	if adaptive_rounds < 1:
@@ -367,6 +382,8 @@ def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None
 			approx_idx = torch.arange(kr_max, dtype=torch.int32, device=A_test_dev.device).expand(A_test_dev.shape[0], kr_max).contiguous()
 			for (k, kr), metrics in _sweep_cells(A_test_dev, approx_idx, exact, top_k_vals, retr_vals, n_ent).items():
 				res[f"top_k={k}"][f"k_retvr={kr}"][f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}"] = metrics
+			if rank_metrics:   # (every score ties: an item's rank is its id)
+				_put_rank_metrics(res, exact.indices, top_k_vals, k_max, f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}")
 			if with_pool:   # no anchors: the pool is the retrieved list
 				for (k, kr), metrics in _sweep_pool_cells(A_test_dev, anc, approx_idx, exact, top_k_vals, retr_vals, n_ent, literal_rerank).items():
 					res[f"top_k={k}"][f"k_retvr={kr}"][f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}"].update(metrics)
@@ -377,6 +394,9 @@ def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None
 		approx = cur.topk_in_row_device(X, kr_max)
 		for (k, kr), metrics in _sweep_cells(A_test_dev, approx.indices, exact, top_k_vals, retr_vals, n_ent).items():
 			res[f"top_k={k}"][f"k_retvr={kr}"][f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}"] = metrics
+		if rank_metrics:
+			ranks = torch.cat([cur.rank_in_row(X, exact.indices[:, c:c + ops.RANK_MAX_T]) for c in range(0, k_max, ops.RANK_MAX_T)], dim=1)
+			_put_rank_metrics(res, ranks, top_k_vals, k_max, f"anc_n_m={n_train if key_n_m is None else key_n_m}_anc_n_e={n_anc}")
 		if with_pool:
 			kr_pool = max([kr for kr in retr_vals if 0 < kr and kr + n_anc <= pool_cell_limit(n_ent)] or [0])
 			new_items = cur.topk_in_row_device(X, kr_pool, exclude=np.asarray(anc)).indices if kr_pool else approx.indices[:, :0]

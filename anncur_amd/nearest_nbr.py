@@ -50,6 +50,7 @@ class FlatIPIndex:
 		self._X = None
 		self._Xp = self._ids = None  # packed bf16 copy in descending-norm order + row -> id map (built at the first bf16 search)
 		self._split = None           # dtype "bf16x3": the split-bf16 copy (built at the first search)
+		self._rank_operand = None    # the item operand of rank() (built at the first call)
 		self.nprobe = 1  # accepted for FAISS API compatibility
 
 	def add(self, embeds):
@@ -57,7 +58,7 @@ class FlatIPIndex:
 		assert x.dim() == 2 and x.shape[1] == self.d, f"expected [n, {self.d}] embeddings"
 		self._X = x if self._X is None else torch.cat([self._X, x], dim=0)
 		self.ntotal = self._X.shape[0]
-		self._Xp = self._split = None
+		self._Xp = self._split = self._rank_operand = None
 
 	def train(self, embeds):  # FAISS API compatibility (flat index needs no training)
 		return None
@@ -86,6 +87,30 @@ class FlatIPIndex:
 			v, i = ops.score_topk_dense(q, self._X, kc)
 		v, i = _filtered(ops.TopK(v, i), excl, k_eff)
 		return _faiss_pad(v, i, q.shape[0], k, k_eff)
+
+	def _rank_op(self):
+		if self._rank_operand is None:
+			from .cur import _RankOperand
+			# dtype "bf16": an ITEM-order packed copy (the search's copy is in descending-norm order); "fp32" / "bf16x3": the stored fp32 vectors
+			self._rank_operand = _RankOperand(self._X, "bf16" if self.dtype == "bf16" else "fp32")
+		return self._rank_operand
+
+	def rank_route(self, t):
+		"""The route rank() takes for t ids per query: "bf16" (fused, no score matrix) or "dense"."""
+		from .cur import _rank_route_name
+		assert self._X is not None, "index is empty"
+		return _rank_route_name(self._rank_op(), t)
+
+	def rank(self, x, ids):
+		"""The inverse of search(): ids [nq x t] vector ids (-1 = hole) -> int32 [nq x t] (NumPy), the position of each vector in its query's
+		result list (inner product descending, ties to the smaller id), -1 for a hole; at most ops.RANK_MAX_T ids per query.  dtype "bf16" with
+		d <= 512 ranks under the bf16 scores without a score matrix; "fp32" and "bf16x3" under the fp32 scores of the dense route."""
+		assert self._X is not None, "index is empty"
+		from .cur import _route_rank
+		q = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(self.device)
+		return _route_rank(self._rank_op(), q, ids).cpu().numpy()
+
+	rank_of = rank   # the name CURRowIndex gives the same question (its `rank` is the anchor block's numerical rank)
 
 
 class IVFFlatIPIndex:

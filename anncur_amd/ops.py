@@ -959,6 +959,127 @@ def score_topk_dense(X, Et, k, max_bytes=2 << 30):
 	return TopK(val, idx)
 
 
+# ------------------------------------------------------------------ ranks of given items
+RANK_MAX_T = _lib.RANK_MAX_T
+_RANK_KP = (64, 128, 256, 512)
+
+
+def _rank_ids(ids, Q, I, what):
+	"""The target ids of a rank call, checked on the host before anything touches the device: int32 [Q x t] (tensor on any device, or a NumPy
+	array), 1 <= t <= RANK_MAX_T, every id in [0, I) or -1 (a hole).  A wrong dtype is a TypeError, everything else a ValueError.  Ids that live
+	on the GPU cost one synchronisation for their minimum and maximum: an id outside the row is never a device read."""
+	if not torch.is_tensor(ids):
+		ids = torch.as_tensor(np.asarray(ids))
+	if ids.dtype != torch.int32:
+		raise TypeError(f"{what}: ids must be int32 (got {ids.dtype})")
+	if ids.dim() != 2 or ids.shape[0] != Q:
+		raise ValueError(f"{what}: ids must be [Q x t] with Q = {Q} rows (got {tuple(ids.shape)})")
+	t = ids.shape[1]
+	if not 1 <= t <= RANK_MAX_T:
+		raise ValueError(f"{what}: t = {t} targets per row, need 1 <= t <= {RANK_MAX_T}")
+	if ids.numel():
+		lo, hi = (int(v) for v in torch.aminmax(ids))
+		if lo < -1 or hi >= I:
+			raise ValueError(f"{what}: id {lo if lo < -1 else hi} is outside [0, {I}) and is not the hole -1")
+	return ids
+
+
+def _rank_out(Q, t, device, return_scores):
+	rank = torch.empty((Q, t), dtype=torch.int32, device=device)
+	score = torch.empty((Q, t), dtype=torch.float32, device=device) if return_scores else None
+	return rank, score
+
+
+@_on_device
+def rank_in_rows(S, ids, return_scores=False):
+	"""rank[q, j] = the position of item ids[q, j] in row q of S sorted by score descending, ties to the smaller id (the order of
+	rowwise_topk): #{i != id : S[q, i] > a or (S[q, i] == a and i < id)}, a = S[q, id].  -0.0 ties with +0.0, a NaN is never ahead of
+	anything, a NaN target and a hole (id -1) get rank -1; duplicate ids are allowed.  S [Q x I] fp32 / bf16 (rows may be padded), ids int32
+	[Q x t], 1 <= t <= RANK_MAX_T.  -> rank int32 [Q x t], with return_scores (rank, score fp32 [Q x t]): the targets' scores (NaN for a hole)."""
+	if not torch.is_tensor(S) or S.dim() != 2:
+		raise ValueError("rank_in_rows: S must be a 2-D tensor")
+	dt = _dt(S)
+	Q, I = S.shape
+	if I < 1:
+		raise ValueError("rank_in_rows: S has no columns")
+	ids = _rank_ids(ids, Q, I, "rank_in_rows")
+	_dev(S)
+	S = _rowmajor(S)
+	ids = ids.to(S.device).contiguous()
+	rank, score = _rank_out(Q, ids.shape[1], S.device, return_scores)
+	check(_lib.load().anncur_rank_in_rows(_p(S), dt, Q, I, _ld(S), _p(ids), ids.shape[1], _p(rank), _p(score) if return_scores else None, _stream()), "rank_in_rows")
+	return (rank, score) if return_scores else rank
+
+
+def score_rank_ok(Kp, I, t):
+	"""True if anncur_score_rank takes this shape: the packed widths of approx_error_packed, at most RANK_MAX_T targets per query."""
+	return Kp in _RANK_KP and 1 <= t <= RANK_MAX_T and 1 <= I < (1 << 31) - 65
+
+
+@_on_device
+def score_rank(Xp, Etp, I, ids, return_scores=False, workspace=None):
+	"""rank_in_rows under S_hat = Xp . Etp^T without writing S_hat: Xp [Q x Kp] packed bf16, Etp [ceil32(I) x Kp] packed bf16 in ITEM order
+	(pack_bf16(..., row_multiple=32); a descending-norm copy is NOT item order), Kp in {64, 128, 256, 512}.  A target's score is computed by
+	the counting pass' own tile routine, so it is bit-identical to the score that pass compares it with.  workspace: a private 256-byte
+	aligned uint8 tensor of anncur_score_rank_workspace_bytes (default: the shared grow-only one); nothing in it needs to be pre-filled."""
+	for name, M in (("Xp", Xp), ("Etp", Etp)):
+		if not torch.is_tensor(M) or M.dim() != 2:
+			raise ValueError(f"score_rank: {name} must be a 2-D tensor")
+		if M.dtype != torch.bfloat16:
+			raise TypeError(f"score_rank: {name} must be packed bfloat16 (got {M.dtype})")
+	Q, Kp = Xp.shape
+	if Kp not in _RANK_KP or Etp.shape[1] != Kp or I < 1 or Etp.shape[0] < -(-I // 32) * 32:
+		raise ValueError(f"score_rank: Xp [Q x Kp], Etp [ceil32(I) x Kp] with Kp in {_RANK_KP} (got Xp {tuple(Xp.shape)}, Etp {tuple(Etp.shape)}, I = {I})")
+	ids = _rank_ids(ids, Q, I, "score_rank")
+	if not score_rank_ok(Kp, I, ids.shape[1]):
+		raise ValueError(f"score_rank: shape (I = {I}, Kp = {Kp}, t = {ids.shape[1]}) is outside the fused route")
+	_dev(Xp, Etp)
+	if not Etp.is_contiguous():
+		raise ValueError("score_rank: Etp must be contiguous")
+	Xp = _rowmajor(Xp)
+	if _ld(Xp) % 8 != 0 or Xp.data_ptr() % 16 != 0:
+		Xp = Xp.contiguous()
+	ids = ids.to(Xp.device).contiguous()
+	t = ids.shape[1]
+	rank, score = _rank_out(Q, t, Xp.device, return_scores)
+	if Q == 0:
+		return (rank, score) if return_scores else rank
+	lib = _lib.load()
+	nbytes = lib.anncur_score_rank_workspace_bytes(Q, I, Kp, t)
+	if nbytes == 0:
+		raise _lib.AnncurHipError(f"score_rank: shape (Q={Q}, I={I}, Kp={Kp}, t={t}) is outside the fused route")
+	if workspace is None:
+		workspace = _Workspace.get(nbytes, Xp.device)
+	elif workspace.dtype != torch.uint8 or workspace.numel() < nbytes or workspace.data_ptr() % 256 != 0 or not workspace.is_contiguous():
+		raise ValueError(f"score_rank: workspace must be a contiguous 256-byte aligned uint8 tensor of at least {nbytes} bytes")
+	check(lib.anncur_score_rank(_p(Xp), _ld(Xp), _p(Etp), Kp, Q, I, Kp, _p(ids), t, _p(rank), _p(score) if return_scores else None,
+								_p(workspace), workspace.numel(), _stream()), "score_rank")
+	return (rank, score) if return_scores else rank
+
+
+@_on_device
+def rank_dense(X, Et, ids, max_bytes=2 << 30, return_scores=False):
+	"""Unfused route of the ranks: S = X @ Et^T in fp32 in row chunks of at most max_bytes, exactly as score_topk_dense takes it, and
+	rank_in_rows on each chunk.  Any K, any dtype: the scores are the ones score_topk_dense ranks."""
+	if not torch.is_tensor(X) or not torch.is_tensor(Et) or X.dim() != 2 or Et.dim() != 2 or X.shape[1] != Et.shape[1]:
+		raise ValueError("rank_dense: X [Q x K] and Et [I x K] must be 2-D tensors with one inner dimension")
+	_dt(X), _dt(Et)
+	Q, I = X.shape[0], Et.shape[0]
+	ids = _rank_ids(ids, Q, I, "rank_dense")
+	_dev(X, Et)
+	ids = ids.to(X.device).contiguous()
+	rank, score = _rank_out(Q, ids.shape[1], X.device, return_scores)
+	rows = max(1, min(Q, max_bytes // max(4 * I, 1)))
+	for q0 in range(0, Q, rows):
+		q1 = min(Q, q0 + rows)
+		res = rank_in_rows(_dense_scores(X[q0:q1], Et), ids[q0:q1], return_scores)
+		if return_scores:
+			rank[q0:q1], score[q0:q1] = res
+		else:
+			rank[q0:q1] = res
+	return (rank, score) if return_scores else rank
+
+
 # ------------------------------------------------------------------ SoftMax item sampling (DESIGN 4.4e)
 def _temperature_arg(temperature, what):
 	if isinstance(temperature, bool) or not isinstance(temperature, (int, float, np.integer, np.floating)) or not np.isfinite(temperature) or not temperature > 0:

@@ -33,6 +33,67 @@ def overlap_cells(exact_idx, approx_idx, cells, A_dev=None, literal_rerank=False
 	return out
 
 
+# ------------------------------------------------------------------ the recall curve from ranks
+def _host_ranks(ranks):
+	r = ranks.detach().cpu().numpy() if torch.is_tensor(ranks) else np.asarray(ranks)
+	if r.ndim != 2 or r.dtype.kind not in "iu":
+		raise ValueError("ranks must be an integer [Q x k] array (index.rank_of(X, exact.indices[:, :k]))")
+	return r
+
+
+def overlap_from_ranks(ranks, cells):
+	"""common counts [n_cells, Q] (NumPy int32) for cells = [(top_k, k_retvr), ...] from ranks [Q x >= max top_k], the approximate rank of each
+	query's exact top-k items in exact order (index.rank_of(X, exact.indices)): #{j < top_k : 0 <= ranks[q, j] < k_retvr} -- what overlap_cells
+	counts from a retrieved list, for ANY k_retvr up to n_ent and without that list.  A rank of -1 (a hole, a NaN score) is never retrieved."""
+	r = _host_ranks(ranks)
+	out = np.empty((len(cells), r.shape[0]), dtype=np.int32)
+	for j, (k, kr) in enumerate(cells):
+		if not 0 <= k <= r.shape[1]:
+			raise ValueError(f"overlap_from_ranks: cell ({k}, {kr}) needs {k} ranks per query, {r.shape[1]} given")
+		out[j] = ((r[:, :k] >= 0) & (r[:, :k] < kr)).sum(axis=1)
+	return out
+
+
+RANK_CURVE_RECALLS = (0.5, 0.9, 0.95, 0.99, 1.0)
+RANK_CURVE_PREFIX = "exact_topk_approx_rank"
+
+
+def _nth_smallest(sorted_vals, frac, n):
+	"""The ceil(frac n)-th smallest of the n pairs (the product taken exactly, not in binary floating point), None where it falls among
+	the pairs without a rank (sorted_vals holds only the ranked ones)."""
+	from fractions import Fraction
+	m = max(1, -((-Fraction(str(frac)) * n) // 1))
+	return int(sorted_vals[m - 1]) if m <= len(sorted_vals) else None
+
+
+def rank_curve(ranks, top_k_vals, recalls=RANK_CURVE_RECALLS):
+	"""{top_k: metrics} from ranks [Q x >= max top_k] (as for overlap_from_ranks), over all Q top_k pairs (query, exact top-k item):
+	  exact_topk_approx_rank~mean                 mean rank (0-based) of the ranked pairs, rounded to 4 decimals
+	  exact_topk_approx_rank~p50 / p90 / p99      the ceil(p Q k)-th smallest rank (nearest-rank percentile, an integer)
+	  exact_topk_approx_rank~max                  the largest rank
+	  k_retvr_for_recall~{r}                      the ceil(r Q k)-th smallest rank, plus 1: the smallest k_retvr whose retrieved lists hold
+	                                              that fraction of all exact top-k items
+	A pair without a rank (-1) counts as never retrieved: it is left out of mean and max, and a percentile or recall level that falls among
+	such pairs is None."""
+	r = _host_ranks(ranks)
+	out = {}
+	for k in top_k_vals:
+		if not 1 <= k <= r.shape[1]:
+			raise ValueError(f"rank_curve: top_k = {k} needs {k} ranks per query, {r.shape[1]} given")
+		flat = r[:, :k].reshape(-1)
+		n = flat.size
+		s = np.sort(flat[flat >= 0].astype(np.int64))
+		m = {f"{RANK_CURVE_PREFIX}~mean": round(float(s.mean()), 4) if s.size else None}
+		for name, frac in (("p50", 0.5), ("p90", 0.9), ("p99", 0.99)):
+			m[f"{RANK_CURVE_PREFIX}~{name}"] = _nth_smallest(s, frac, n) if n else None
+		m[f"{RANK_CURVE_PREFIX}~max"] = int(s[-1]) if s.size else None
+		for frac in recalls:
+			v = _nth_smallest(s, frac, n) if n else None
+			m[f"k_retvr_for_recall~{frac}"] = None if v is None else v + 1
+		out[k] = m
+	return out
+
+
 # ------------------------------------------------------------------ the pool "retrieved + anchors" (DESIGN 4.4c)
 POOL_PREFIX = "exact_vs_reranked_approx_retvr_w_anchors"
 OVERLAP_MAX_LIST = 4096   # longest list anncur_overlap_counts takes

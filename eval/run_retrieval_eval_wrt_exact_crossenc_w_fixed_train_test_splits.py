@@ -92,6 +92,8 @@ def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, de
 		pool_kw = dict(pool_kw, anchor_selection=args.anchor_selection)   # (random = today's call; the other methods ignore the flag)
 	if args.pinv_rcond is not None and curr_method == "cur":
 		pool_kw = dict(pool_kw, pinv_rcond=args.pinv_rcond)   # (None = today's call; the other methods build no pseudo-inverse through --pinv)
+	if args.rank_metrics and curr_method == "cur":
+		pool_kw = dict(pool_kw, rank_metrics=True)   # (off = today's call; the other methods ignore the flag)
 	LOGGER.info(f"Computing approximate test mention-to-entity scores using method={curr_method}")
 	if curr_method == "cur":
 		A_train_dev = harness.to_device_matrix(A_train, device, args.dtype)
@@ -143,6 +145,8 @@ def run(args, device):
 		del arg_dict["adaptive_rounds"]   # (the same rule)
 	if not args.adaptive_incremental:
 		del arg_dict["adaptive_incremental"]   # (the same rule)
+	if not args.rank_metrics:
+		del arg_dict["rank_metrics"]   # (the same rule)
 	for key, default in (("adaptive_strategy", "topk"), ("adaptive_temperature", 1.0), ("adaptive_seed", 0), ("anchor_selection", "random"), ("pinv_rcond", None)):
 		if getattr(args, key) == default:
 			del arg_dict[key]   # (the same rule)
@@ -166,6 +170,8 @@ class _Parser(argparse.ArgumentParser):
 			self.error(f"--anchor_selection pivoted is deterministic: --n_seeds {ns.n_seeds} would repeat one result (use --n_seeds 1)")
 		if ns.pinv_rcond is not None and ns.pinv not in ("svd", "numpy"):
 			self.error(f"--pinv_rcond needs --pinv svd or numpy: Newton-Schulz (--pinv {ns.pinv}) cannot truncate")
+		if ns.rank_metrics and ns.adaptive_rounds != 1:
+			self.error(f"--rank_metrics needs --adaptive_rounds 1: the pool of --adaptive_rounds {ns.adaptive_rounds} is no prefix of one ranking")
 		return ns
 
 
@@ -227,6 +233,11 @@ def build_parser(worlds=None):
 							 "today's run and output); pivoted = the sorted first n_anc items of one column-pivoted QR selection from the training matrix, on the "
 							 "device (deterministic: needs --n_seeds 1; anchor counts above the number of training queries, ANNCUR_MAX_TOPK or the numerical rank "
 							 "are left out and logged)")
+	parser.add_argument("--rank_metrics", action="store_true",
+						help="eval_method cur with --adaptive_rounds 1: every top_k additionally reports, under res[seed][top_k=k][approx_rank][anc_n_m=.._anc_n_e=..], the "
+							 "approximate rank of the exact top-k items over all (query, item) pairs -- exact_topk_approx_rank~mean / p50 / p90 / p99 / max -- and "
+							 "k_retvr_for_recall~r, the smallest k_retvr whose retrieved lists hold the fraction r of them: the whole recall curve from one rank call "
+							 "per anchor count, not limited to ANNCUR_MAX_TOPK; off (default) = today's run and output")
 	parser.add_argument("--compute_dtype", type=str, default="auto", choices=["auto", "fp32", "bf16", "bf16x3"],
 						help="arithmetic of the CUR retrieval: auto = by --dtype (fp32 matrix -> dense fp32 route, bf16 -> fused bf16 kernel); bf16x3 = for --dtype fp32: "
 							 "operands split into bf16 hi + lo parts on the fused kernel, candidates rescored in fp32 (the fp32 route's values, S_hat never written)")

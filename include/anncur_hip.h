@@ -366,6 +366,38 @@ int anncur_overlap_counts(const int32_t *a, int32_t la, const int32_t *b, int32_
                           const int32_t *ka, const int32_t *kb, int32_t n_pairs,
                           int32_t *common, void *stream);
 
+/* ranks of given items -----------------------------------------------------------------------------------------------
+ * The inverse of a top-k: where does item `id` stand in a score row?  For a row s[0..I) and a target id, a = s[id]:
+ *
+ *     rank = #{ i != id : s[i] > a  or  (s[i] == a and i < id) }
+ *
+ * i.e. the position of id in the row sorted by score descending, ties to the smaller id -- the order of anncur_rowwise_topk.  The compare
+ * is the float compare: -0.0 and +0.0 tie; a NaN score is never ahead of anything; a target whose own score is NaN gets rank -1, and so
+ * does a hole (id == -1).  Any other id outside [0, I) is the caller's error (the Python binding raises ValueError); the kernels treat it
+ * as a hole and never read through it.  Duplicate ids in a row are allowed, each reports that item's rank.
+ *   ids int32[Q x t], rank int32[Q x t], score float[Q x t] or NULL, all contiguous; 1 <= t <= ANNCUR_RANK_MAX_T.
+ *   score[q, j] = the target's score as the route computed it (NaN for a hole).
+ * Every score in one comparison comes from the same arithmetic, the target's own included: anncur_rank_in_rows reads a from the row it
+ * counts over; anncur_score_rank computes a with the tile routine of its counting pass (same fragments, same k order), so a is
+ * bit-identical to what that pass computes for (q, id) and an item with the target's embedding and a larger id lands right behind it.
+ *
+ * anncur_rank_in_rows: S [Q x I] (ANNCUR_F32 / ANNCUR_BF16), row pitch lds_ >= I elements, any alignment.  One workgroup per row: target keys
+ *   sorted in LDS, the row streamed with 16-byte loads, elements that beat the weakest target binary-searched into t bins, prefix sum.
+ *   0 <= Q < 2^31 (Q == 0 returns OK), 1 <= I < 2^31 - 1; anything else is ANNCUR_E_INVALID and nothing is written.  No workspace.
+ * anncur_score_rank: ranks under S_hat = X . Et^T, which is never written.  X [Q x Kp] packed bf16 (pitch ldx, a multiple of 8), Et
+ *   [ceil32(I) x Kp] packed bf16 in ITEM order (lde == Kp), both 16-byte aligned -- the operands of anncur_approx_error_packed; Kp in
+ *   {64, 128, 256, 512} (ANNCUR_E_UNSUPPORTED otherwise).  Rows I .. ceil32(I) - 1 of Et are padding and are not counted; lanes past Q
+ *   neither store nor count.  Workspace: caller-owned, anncur_score_rank_workspace_bytes(Q, I, Kp, t) bytes (0 = shape not taken), 256-byte
+ *   aligned, nothing in it pre-filled by the caller; missing, misaligned or short is ANNCUR_E_WORKSPACE.  The counts of different item
+ *   splits meet by integer atomics: results are deterministic. */
+#define ANNCUR_RANK_MAX_T 1024
+int anncur_rank_in_rows(const void *S, int dtype, int64_t Q, int64_t I, int64_t lds_, const int32_t *ids, int32_t t,
+                        int32_t *rank, float *score, void *stream);
+size_t anncur_score_rank_workspace_bytes(int64_t Q, int64_t I, int32_t Kp, int32_t t);
+int anncur_score_rank(const void *X, int64_t ldx, const void *Et, int64_t lde, int64_t Q, int64_t I, int32_t Kp,
+                      const int32_t *ids, int32_t t, int32_t *rank, float *score,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 /* search without the exact matrix: re-rank from caller-supplied scores ---------------------------------------------
  *   temp[approx_idx] = exact[approx_idx]; temp.topk(k)      ..._splits.py:91-96 ; ...crossenc.py:108-113
  *   the anchor items' exact scores, which every query has paid for already        ..._w_fixed_train_test_splits.py:297-301
