@@ -1,7 +1,7 @@
 // Prepass on the sweep's MFMA body (Kp <= 256, the plans that run score16_kernel; included by score_fused.hip behind score16.hpp).
 //
 // The prepass multiplies an 8 % sample of the item tiles with every query and keeps one maximum per group of 16 items; the threshold kernel
-// takes the k-th largest of a query's group maxima as tau0.  Until round 6 it ran score_kernel<KP, 0, 16>: 32x32x16 MFMAs, compiler-placed
+// takes the k-th largest of a query's group maxima as tau0.  Until round 6 it ran score_prepass_kernel<KP, 16>: 32x32x16 MFMAs, compiler-placed
 // ds_read with lgkmcnt(0) in front of every k-step, one tile ahead.  This kernel is score16_kernel's tile loop minus everything that serves
 // candidates: queries as the resident B operand (four 16-query sub-tiles per wave), the tile image and its XOR swizzle, LDS-DMA staging with
 // an SGPR base + M0, the five-quad fragment ring with counted waits, v_mfma_f32_16x16x32_bf16.  No queue, no ladder, no tickets: a workgroup
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256, 2) void prepass16_kernel(const FusedParams p) 
 			xb[t][s] = __builtin_bit_cast(bf16x8, w);
 		}
 	}
-	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the queries and the first tile (see score_kernel)
+	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the queries and the first tile (see score_sweep_kernel)
 	if (j_dma < j_end) fetch(1);
 	__builtin_amdgcn_s_barrier();
 

@@ -1,5 +1,5 @@
 // Sweep kernel on v_mfma_f32_16x16x32_bf16 (Kp <= 256).  Same pipeline position, operands, LDS tile image and DMA as
-// score_kernel<KP, 1> (included by score_fused.hip); what changes is the MFMA shape and with it the lane <-> (query, item) map:
+// score_sweep_kernel<KP> (included by score_fused.hip); what changes is the MFMA shape and with it the lane <-> (query, item) map:
 //   D[16 items][16 queries] per MFMA, C/D layout col = lane & 15 = query, row = 4 (lane >> 4) + reg = item;
 //   a wave owns 64 queries as FOUR 16-query sub-tiles (the lane serves one query of each), a 32-item tile is two 16-item halves.
 // Why: under MFMA load the chip lowers its clock, and it holds a higher one on the 16x16x32 shape than on 32x32x16 at equal
@@ -50,7 +50,7 @@ struct Fused16Cfg {
 	static constexpr int DRAIN_AT = 192;             // a step drains at its head from this fill on (three full passes; 128 / 320 measured: see DESIGN 4.1)
 	static constexpr int QUEUE_OFF = 2 * TILE_BYTES;
 	static constexpr int CNT_OFF = QUEUE_OFF + NW * QCAP * 8;       // 64 NW per-query candidate counts of this item split
-	static constexpr int TICKET_OFF = CNT_OFF + NW * 64 * 4;        // ticket words of the dynamic tile schedule (score_kernel)
+	static constexpr int TICKET_OFF = CNT_OFF + NW * 64 * 4;        // ticket words of the dynamic tile schedule (score_sweep_kernel)
 	static constexpr int PIECES = TILE_BYTES / 1024 / NW;           // DMA pieces per wave and tile
 	static_assert(PIECES >= 1, "a tile holds at least one 1 KB piece per wave");
 	// threshold ladder (wave-private rows, local query l of wave w at (w * 64 + l)):
@@ -281,8 +281,8 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 	//  0.4517-0.4542 without; profiles/r05_static_priority_null.txt.)
 	const int wid = xcd_remap(blockIdx.x, p.n_wg);
 	const int n_rb = (int)((p.Q + C::BQ - 1) / C::BQ);
-	// work id -> (row block, split): split-major (p.rb_major = 1, row-block-major, measured worse: see launch_fused)
-	const int split = p.rb_major ? wid % p.S : wid / n_rb, rb = p.rb_major ? wid / p.S : wid - split * n_rb;
+	// work id -> (row block, split): split-major (row-block-major was measured worse: see launch_fused)
+	const int split = wid / n_rb, rb = wid - split * n_rb;
 
 	// ---- this lane's four queries: B operand fragments, resident for the whole kernel.  B[k = 8 (lane >> 4) + j][col = lane & 15]
 	bf16x8 xb[4][KS32];
@@ -299,12 +299,12 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 			xb[t][s] = __builtin_bit_cast(bf16x8, w);
 		}
 	}
-	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see score_kernel
+	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see score_sweep_kernel
 
 	const int j_begin = p.tile_begin + split * p.tiles_per_split, j_end = min(j_begin + p.tiles_per_split, p.tile_end);
 	float tau[4];
 #pragma unroll
-	for (int t = 0; t < 4; ++t) tau[t] = qv[t] < p.Q ? p.tau[qv[t] * p.tau_stride] + p.tau_bias : INFINITY;
+	for (int t = 0; t < 4; ++t) tau[t] = qv[t] < p.Q ? p.tau[qv[t] * p.tau_stride] : INFINITY;
 	// candidate path: the wave's queue, its 64 per-query counts (lane l <-> local query l = 16 * sub-tile + (lane & 15) of the wave)
 	const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 	const uint32_t lds_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(smem));
@@ -340,7 +340,7 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 	uint32_t lad_tick = 0;
 	bool lad_pending = false;
 
-	// ---- tile schedule (see score_kernel): static contiguous share, or tickets of p.chunk_tiles tiles from the row block's counter
+	// ---- tile schedule (see score_sweep_kernel): static contiguous share, or tickets of p.chunk_tiles tiles from the row block's counter
 	int t_cur = j_begin < j_end ? j_begin : -1, t_cend = j_end, t_next_chunk = -1;
 	bool ticket_pending = false;
 	const bool dyn = p.chunk_tiles > 0;

@@ -12,7 +12,7 @@
 //     two workgroups per CU.  Kp <= 256 (Kp = 512 would be one workgroup per CU: the two-kernel route stays there).
 //   * the matrix' last, partial tile (I % 32 items) is swept for candidates only; its columns' error terms are added by the strided
 //     kernel of gemm.hip, as in anncur_approx_error_packed.
-//   * values: the same MFMAs in the same order as score_kernel<Kp, 1, 16> (the 32x32x16 body, ANNCUR_TOPK_MFMA32) -- bit for bit.
+//   * values: the same MFMAs in the same order as score_sweep_kernel<Kp> (the 32x32x16 body, ANNCUR_TOPK_MFMA32) -- bit for bit.
 #pragma once
 
 template <int KP>
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256, 2) void evalf_kernel(const FusedParams p, cons
 		const bool ok = qv[t] < p.Q;
 		aread[t] = lds_addr(smem) + (uint32_t)(AOFF + row * 64 + 8 * h);
 		asw[t] = (uint32_t)((row >> 2) & 3) << 4;
-		tau[t] = ok ? p.tau[qv[t] * p.tau_stride] + p.tau_bias : INFINITY;
+		tau[t] = ok ? p.tau[qv[t] * p.tau_stride] : INFINITY;
 		const u32x4 *src = reinterpret_cast<const u32x4 *>(p.X + (ok ? qv[t] : 0) * p.ldx) + h;
 #pragma unroll
 		for (int s = 0; s < KSTEPS; ++s) {
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256, 2) void evalf_kernel(const FusedParams p, cons
 		}
 #endif
 	};
-	__builtin_amdgcn_s_waitcnt(0x0F70);  // see score_kernel: keeps vmcnt(0) out of the tile loop
+	__builtin_amdgcn_s_waitcnt(0x0F70);  // see score_sweep_kernel: keeps vmcnt(0) out of the tile loop
 
 	// candidate path: the wave's queue and its 64 per-query counts (local query 32 t + r)
 	const int64_t q_wave0 = (int64_t)rb * Cfg::BQ + wave_u * 64;

@@ -63,7 +63,8 @@ struct FusedCfg {
 	static constexpr int QUEUE_OFF = (2 * TILE_BYTES + 16383) / 16384 * 16384;  // rings are 16 KiB aligned (filter_one)
 	static constexpr int TICKET_OFF = QUEUE_OFF + QUEUE_BYTES;        // two 32-bit words: the chunk tickets thread 0 hands to its workgroup (dynamic tile schedule)
 	// (Kp = 512: two 32 KiB tile buffers + 16 KiB of rings are exactly half a CU's LDS -- 16 bytes more and only ONE workgroup fits per CU
-	//  (measured: the sweep of cfg4 20 % slower); that body keeps static tile shares and no ticket words)
+	//  (measured: the sweep of cfg4 20 % slower); that body keeps static tile shares and no ticket words.  Tickets are drawn by the
+	//  two-sub-tile body only: the one-sub-tile body at Kp = 128 / 256 (ANNCUR_TOPK_QT1) has the words and leaves them alone)
 	static constexpr int LDS_BYTES = TICKET_OFF + (KP >= 512 ? 0 : 16);  // the prepass kernel uses only the tile part
 	static constexpr int NAOFF = KSTEPS < 8 ? KSTEPS : 8;             // fragment address registers of the staggered sweep (see stagger_tile)
 };
@@ -90,28 +91,19 @@ struct FusedParams {
 	const float *tau; int tau_stride; // threshold per query: tau[q * tau_stride]
 	uint2 *cand; uint32_t *seg_cnt; int capg;
 	int nseg;                         // candidate segments per query (2 S: 32x32x16 body, lane halves; S: 16x16x32 body)
-	int rb_major;                     // work id -> (row block, split): 0 = split-major (1 = row-block-major: see launch_fused)
 	int flush_tiles;                  // wave-cooperative queue flush period (tiles)
-	// Left over from retired tuning experiments, always 0: tau_bias and rb_major are still read by the kernels; debug_nostore,
-	// debug_stamp, prio_mode, ring_stagger and ring_spin_sleep by none (launch_fused leaves them zero).  They stay while removing them
-	// would change the kernel argument layout.
-	int debug_nostore;
-	int debug_stamp;
-	float tau_bias;
 	int n_wg;                         // grid size (for the XCD remap)
 	// dynamic tile schedule of a sweep stage (chunk_tiles > 0): the workgroups of a query row block draw chunks of `chunk_tiles` consecutive
-	// tiles from the row block's ticket counter instead of sweeping a fixed share -- see score_kernel
+	// tiles from the row block's ticket counter instead of sweeping a fixed share -- see score_sweep_kernel
 	int chunk_tiles, n_chunks;
 	uint32_t *chunk_ctr;              // [n row blocks], zero at launch
 	uint8_t *chunk_owner;             // [n row blocks x n_chunks]: which item split swept the chunk (the repair path's map)
 	int sliced, chunks_per_slice;     // XCD-sliced tickets: chunk_ctr is [row block][N_SLICES], slice s = chunks [s * chunks_per_slice, + chunks_per_slice)
 	// threshold ladder of score16_kernel (score16.hpp): levels [n_rb x BQ][LADDER_LEVELS], counter words [n_rb x BQ][4] (zero at launch),
 	// the cell each wave raises to the threshold it ended with (initialised to tau0 by the threshold kernel), k
-	int prio_mode;
 	int ladder_on; uint32_t ladder_k, ladder_mask;   // ladder_mask = period - 1 (a power of two): tiles between two fetches of a wave's counter words
 	const float *ladder; uint32_t *ladder_cnt; float *tau_final;
 	uint32_t *nfb;                    // workspace word 0 (zero_ws_header)
-	int ring_stagger, ring_spin_sleep;
 	uint32_t zero_bytes;              // prepass kernels: workspace bytes [0, zero_bytes) to clear (a multiple of 16; 0: none) -- see zero_ws_header
 };
 
@@ -251,7 +243,7 @@ __device__ __forceinline__ void lds_write_2x32(uint32_t addr, uint32_t lo, uint3
 // Measured on cfg2 (MI355X): branch version 0.58 ms per sweep, predicated version 0.655 ms independent of the hit rate (its
 // compare -> exec -> store chain sits in front of the wave's next MFMA) -> the branch version is the one in use.
 // (plan_stages picks the variant per sweep stage from the expected hit rate: predicated above ~0.5 taken branches per compare)
-template <int D, bool FILTER_PREDICATED = false, bool INLINE_HIT = false>
+template <int D, bool FILTER_PREDICATED = false>
 __device__ __forceinline__ void filter_one(float v, int e, float tau, uint32_t item0, uint32_t lq, uint32_t &qcnt) {
 	static_assert((D & (D - 1)) == 0, "queue depth must be a power of two");
 	// qcnt is kept pre-shifted (slot stride 2048 B); lq has bits 11..13 clear (16 KiB-aligned ring), so OR == ADD
@@ -266,27 +258,12 @@ __device__ __forceinline__ void filter_one(float v, int e, float tau, uint32_t i
 			lds_write_2x32((qcnt & (uint32_t)((D - 1) << 11)) | lq, __float_as_uint(v), item0 + (uint32_t)((e & 3) + 8 * (e >> 2)));
 			qcnt += 2048u;
 		}
-	} else if (INLINE_HIT) {
-		// the push block stays IN LINE behind a short forward skip (taken when no lane hits) instead of out of line behind a far
-		// branch out and back (taken when one does)
-		if (__builtin_expect(__ballot(v >= tau) != 0ull, 1)) {
-			if (v >= tau) {
-				lds_write_2x32((qcnt & (uint32_t)((D - 1) << 11)) | lq, __float_as_uint(v), item0 + (uint32_t)((e & 3) + 8 * (e >> 2)));
-				qcnt += 2048u;
-			}
-		}
 	} else if (__builtin_expect(__ballot(v >= tau) != 0ull, 0)) {
 		if (v >= tau) {
 			lds_write_2x32((qcnt & (uint32_t)((D - 1) << 11)) | lq, __float_as_uint(v), item0 + (uint32_t)((e & 3) + 8 * (e >> 2)));
 			qcnt += 2048u;
 		}
 	}
-}
-
-template <int D>
-__device__ __forceinline__ void filter_queue(const f32x16 &acc, float tau, uint32_t item0, uint32_t lq, uint32_t &qcnt) {
-#pragma unroll
-	for (int e = 0; e < 16; ++e) filter_one<D>(acc[e], e, tau, item0, lq, qcnt);
 }
 
 // Dense splits (norm-ordered rows: the leading splits of the first stage; their rings are drained every tile): a lane that finds
@@ -419,7 +396,7 @@ __device__ __forceinline__ void lds_wait_frag(u32x4 &frag, int pending) {  // `p
 // Fragment address of k-step s (tile buffer 0): row r, chunk (2 s + h) ^ f(r).  For Kp = 256 (32 chunks per row, f(r) = r & 15) the XOR
 // leaves bit 4 of the chunk alone, so k-steps s and s + 8 are 256 bytes apart: eight address registers plus an immediate offset serve
 // the sixteen k-steps (the eight registers this saves are what the dynamic tile schedule's ticket lives in).
-template <int KP, int CUR, bool PRED, bool INL = false>
+template <int KP, int CUR, bool PRED>
 __device__ __forceinline__ void stagger_tile(const uint32_t (&aoff)[FusedCfg<KP>::NAOFF], const bf16x8 (&xb)[2][FusedCfg<KP>::KSTEPS],
 											  f32x16 &acc1, float tau0, float tau1_prev, uint32_t item0, uint32_t item0_prev,
 											  uint32_t lq0, uint32_t lq1, uint32_t &q0, uint32_t &q1, bool dense) {
@@ -451,7 +428,7 @@ __device__ __forceinline__ void stagger_tile(const uint32_t (&aoff)[FusedCfg<KP>
 			accA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[0][g], accA, 0, 0, 0);
 #pragma unroll
 			for (int e = (g == 1 ? 0 : g) * EPS; e < (g == 0 ? 0 : g + 1) * EPS; ++e)
-				filter_one<Cfg::QDEPTH, PRED, INL>(acc1[e], e, tau1_prev, item0_prev, lq1, q1);
+				filter_one<Cfg::QDEPTH, PRED>(acc1[e], e, tau1_prev, item0_prev, lq1, q1);
 			if (g == K - 1 && dense) mark_wrapped_raw<Cfg::QDEPTH>(acc1, lq1, q1);  // (uniform) the previous tile's sub-tile 1 is filtered
 		} else {
 			// no filter in the first step of the half: accA's last MFMA is still in the pipe (and the predicated filter is
@@ -459,7 +436,7 @@ __device__ __forceinline__ void stagger_tile(const uint32_t (&aoff)[FusedCfg<KP>
 			accB = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[1][g - K], accB, 0, 0, 0);
 #pragma unroll
 			for (int e = (g - K == 1 ? 0 : g - K) * EPS; e < (g == K ? 0 : g - K + 1) * EPS; ++e)
-				filter_one<Cfg::QDEPTH, PRED, INL>(accA[e], e, tau0, item0, lq0, q0);
+				filter_one<Cfg::QDEPTH, PRED>(accA[e], e, tau0, item0, lq0, q0);
 		}
 	}
 #undef ST_READ
@@ -481,7 +458,8 @@ __device__ __forceinline__ void mfma_chain_done(f32x16 &acc) {
 #endif
 }
 
-// Kp = 512 (one 32-query sub-tile per wave: the query operand alone takes 128 VGPRs): the same idea across TILES -- while the
+// One 32-query sub-tile per wave (Kp = 512, where the query operand alone takes 128 VGPRs; Kp = 128 / 256 under ANNCUR_TOPK_QT1, for
+// three workgroups per CU): the same idea across TILES -- while the
 // 32-MFMA chain of tile j executes into `acc`, the filter of tile j-1's accumulator `accP` is issued in its shadow, one element every
 // second k-step; A fragments through the counted-wait register ring as in stagger_tile.  The caller alternates two accumulators
 // (no copy: see mfma_chain_done).  Fragment address of k-step s:
@@ -520,24 +498,100 @@ __device__ __forceinline__ void stagger1_tile(const uint32_t (&aoff8)[8], const 
 	if (dense) mark_wrapped_raw<Cfg::QDEPTH>(accP, lq, qcnt);  // (uniform) the previous tile is filtered
 }
 
-// MODE 0: prepass (GROUP = 16 or 4 items per group maximum).  MODE 1: filter sweep (PRED: branch-free filter, for stages in
-// which most compares find a survivor in some lane -- large k).
-template <int KP, int MODE, int GROUP, bool PRED = false, bool INL = false, int QTV = FusedCfg<KP>::QT>
-__global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_kernel(const FusedParams p) {
+// Prepass on the 32x32x16 body: group maxima (GROUP = 16 or 4 items per maximum) of S_hat over the sample tiles, plain double-buffered
+// tile loop with compiler-placed fragment reads.  (The plans that sweep with score16_kernel run prepass16_kernel instead.)
+template <int KP, int GROUP, int QTV = FusedCfg<KP>::QT>
+__global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_prepass_kernel(const FusedParams p) {
 	using Cfg = FusedCfg<KP, QTV>;
 	constexpr int KSTEPS = Cfg::KSTEPS, QT = Cfg::QT, CPR = Cfg::CPR;
+	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int r = lane & 31, h = lane >> 5;
+	zero_ws_header(p);
+	const int wid = xcd_remap(blockIdx.x, p.n_wg);
+	const int n_rb = (int)((p.Q + Cfg::BQ - 1) / Cfg::BQ);
+	const int split = wid / n_rb, rb = wid - split * n_rb;
+
+	// ---- this wave's queries: B operand fragments, resident for the whole kernel
+	bf16x8 xb[QT][KSTEPS];
+	int64_t qv[QT];
+#pragma unroll
+	for (int t = 0; t < QT; ++t) {
+		qv[t] = (int64_t)rb * Cfg::BQ + wave * 32 * QT + 32 * t + r;
+		const bool ok = qv[t] < p.Q;
+		const u32x4 *src = reinterpret_cast<const u32x4 *>(p.X + (ok ? qv[t] : 0) * p.ldx) + h;
+#pragma unroll
+		for (int s = 0; s < KSTEPS; ++s) {
+			const u32x4 zero = {0u, 0u, 0u, 0u};
+			const u32x4 w = ok ? src[2 * s] : zero;
+			xb[t][s] = __builtin_bit_cast(bf16x8, w);
+		}
+	}
+	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the fragments are complete before the tile loop (see score_sweep_kernel)
+
+	// ---- work range: sample tiles [j_begin, j_end) of p.n_st; sample tile j is the matrix' tile tile_of(j)
+	const int j_begin = split * p.st_per_split, j_end = min(j_begin + p.st_per_split, p.n_st);
+#define tile_of(j) (!p.sample_leading ? (int)(((int64_t)(j) * p.n_full_tiles) / p.n_st) : (j))
+	if (j_begin < j_end) tile_dma<KP>(p.Et, tile_of(j_begin), smem, wave, lane);
+	__builtin_amdgcn_s_waitcnt(0x0F70);
+	__syncthreads();
+	ANNCUR_PAD_HERE();
+
+	int cur = 0;
+	for (int j = j_begin; j < j_end; ++j, cur ^= 1) {
+		if (j + 1 < j_end) tile_dma<KP>(p.Et, tile_of(j + 1), smem + (cur ^ 1) * Cfg::TILE_BYTES, wave, lane);
+		f32x16 acc[QT];
+#pragma unroll
+		for (int t = 0; t < QT; ++t)
+#pragma unroll
+			for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+		const u32x4 *tb = reinterpret_cast<const u32x4 *>(smem + cur * Cfg::TILE_BYTES);
+#pragma unroll
+		for (int s = 0; s < KSTEPS; ++s) {
+			const u32x4 w = tb[r * CPR + swz<CPR>(r, 2 * s + h)];
+			const bf16x8 a = __builtin_bit_cast(bf16x8, w);
+#pragma unroll
+			for (int t = 0; t < QT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[t][s], acc[t], 0, 0, 0);
+		}
+
+		// ---- epilogue.  C/D layout: query = lane & 31 (col), item row = (e & 3) + 8 * (e >> 2) + 4 * h
+#pragma unroll
+		for (int t = 0; t < QT; ++t) {
+			if (GROUP == 16) {
+				float m = acc[t][0];
+#pragma unroll
+				for (int e = 1; e < 16; ++e) m = fmaxf(m, acc[t][e]);
+				if (qv[t] < p.Q) p.gmax[qv[t] * p.n_groups + (int64_t)j * 2 + h] = m;
+			} else {
+				float4 m;
+				m.x = fmaxf(fmaxf(acc[t][0], acc[t][1]), fmaxf(acc[t][2], acc[t][3]));
+				m.y = fmaxf(fmaxf(acc[t][4], acc[t][5]), fmaxf(acc[t][6], acc[t][7]));
+				m.z = fmaxf(fmaxf(acc[t][8], acc[t][9]), fmaxf(acc[t][10], acc[t][11]));
+				m.w = fmaxf(fmaxf(acc[t][12], acc[t][13]), fmaxf(acc[t][14], acc[t][15]));
+				if (qv[t] < p.Q) *reinterpret_cast<float4 *>(p.gmax + qv[t] * p.n_groups + ((int64_t)j * 2 + h) * 4) = m;
+			}
+		}
+		__builtin_amdgcn_s_waitcnt(0x0F70);  // the DMA of tile j+1 has landed
+		__syncthreads();
+	}
+#undef tile_of
+}
+
+// Filter sweep on the 32x32x16 body with per-lane rings (PRED: branch-free filter, for stages in which most compares find a survivor in
+// some lane -- large k).  Three tile functions on one schedule: two sub-tiles per wave staggered inside a tile (stagger_tile, Kp <= 256),
+// one sub-tile per wave pipelined across tiles (stagger1_tile: Kp = 512, and Kp = 128 / 256 under ANNCUR_TOPK_QT1).
+template <int KP, bool PRED = false, int QTV = FusedCfg<KP>::QT>
+__global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_sweep_kernel(const FusedParams p) {
+	using Cfg = FusedCfg<KP, QTV>;
+	constexpr int KSTEPS = Cfg::KSTEPS, QT = Cfg::QT, CPR = Cfg::CPR;
+	static_assert(QT == 2 || (KP >= 128 && !PRED), "one sub-tile per wave: stagger1_tile (Kp >= 128, branch filter)");
 	constexpr bool FLUSH_BATCH = !(QTV == 1 && KP <= 256);   // (see flush_queue)
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const int r = lane & 31, h = lane >> 5;
-	if (MODE == 0) zero_ws_header(p);
 	const int wid = xcd_remap(blockIdx.x, p.n_wg);
-	const int nsplit = (MODE == 0) ? p.S0 : p.S;
-	const int n_rb_ = (int)((p.Q + Cfg::BQ - 1) / Cfg::BQ);
-	const bool rbm = MODE == 1 && p.rb_major;   // (uniform) tickets: row-block-major work ids, see score16.hpp
-	const int split = rbm ? wid % p.S : wid / n_rb_;
-	const int rb = rbm ? wid / p.S : wid - split * n_rb_;
-	(void)nsplit;
+	const int n_rb = (int)((p.Q + Cfg::BQ - 1) / Cfg::BQ);
+	const int split = wid / n_rb, rb = wid - split * n_rb;
 
 	// ---- this wave's queries: B operand fragments, resident for the whole kernel
 	bf16x8 xb[QT][KSTEPS];
@@ -562,23 +616,21 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 
 	// ---- work range
 	int j_begin, j_end;  // tile iterations
-	if (MODE == 0) { j_begin = split * p.st_per_split; j_end = min(j_begin + p.st_per_split, p.n_st); }
-	else if (MODE == 1 && p.tile_step > 1) { j_begin = p.tile_begin + split; j_end = p.tile_end; }                          // interleaved splits
-	else { j_begin = p.tile_begin + split * p.tiles_per_split; j_end = min(j_begin + p.tiles_per_split, p.tile_end); }  // MODE 1 and 2
-	const int ts = (MODE == 1 && p.tile_step > 1) ? p.tile_step : 1;  // distance between two tiles of this workgroup
+	if (p.tile_step > 1) { j_begin = p.tile_begin + split; j_end = p.tile_end; }                                        // interleaved splits
+	else { j_begin = p.tile_begin + split * p.tiles_per_split; j_end = min(j_begin + p.tiles_per_split, p.tile_end); }  // contiguous shares
+	const int ts = p.tile_step > 1 ? p.tile_step : 1;  // distance between two tiles of this workgroup
 	// Norm-ordered rows: the survivors crowd into the leading tiles (several times the average density: about half of their elements
 	// pass the prepass threshold at large k).  The first quarter of the first stage's tiles is swept with the rings drained every
 	// tile (a ring then holds nothing but one tile: see mark_wrapped_raw); a step drains when the tile before it was such a tile.
-	const int dense_end = (MODE == 1 && p.sample_leading && !p.carry) ? p.tile_begin + (p.tile_end - p.tile_begin + 3) / 4 : p.tile_begin;
+	const int dense_end = (p.sample_leading && !p.carry) ? p.tile_begin + (p.tile_end - p.tile_begin + 3) / 4 : p.tile_begin;
 	const bool every_tile = p.flush_tiles <= 1;  // (uniform) the whole stage drains every tile (large k): every ring holds one tile
-#define tile_of(j) ((MODE == 0 && !p.sample_leading) ? (int)(((int64_t)(j) * p.n_full_tiles) / p.n_st) : (j))
 
 	float tau[QT];
 	uint32_t ncand[QT], qcnt[QT];
 #pragma unroll
 	for (int t = 0; t < QT; ++t) {
-		tau[t] = (MODE == 1 && qv[t] < p.Q) ? p.tau[qv[t] * p.tau_stride] + p.tau_bias : INFINITY;
-		ncand[t] = qv[t] < p.Q ? ((MODE == 1 && p.carry) ? p.seg_cnt[qv[t] * p.nseg + h * p.S + split] : 0u) : PAD_ROW_COUNT;
+		tau[t] = qv[t] < p.Q ? p.tau[qv[t] * p.tau_stride] : INFINITY;
+		ncand[t] = qv[t] < p.Q ? (p.carry ? p.seg_cnt[qv[t] * p.nseg + h * p.S + split] : 0u) : PAD_ROW_COUNT;
 		qcnt[t] = 0;
 	}
 	// candidate segment of (query, lane half, split); sub-tile t adds a wave-uniform stride
@@ -586,55 +638,82 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 	const int64_t seg_dt = (int64_t)32 * p.nseg * p.capg;
 	const uint32_t lq0 = lds_addr(smem + Cfg::QUEUE_OFF) + (uint32_t)tid * 8u;  // slot i of sub-tile t at byte lq0 + (t*QDEPTH + i)*2048
 	static_assert(Cfg::QUEUE_OFF % (Cfg::QDEPTH * 2048) == 0 && Cfg::QDEPTH * 2048 == 16384, "ring must be 16 KiB aligned");
-	if (MODE == 1 && (lds_addr(smem) & 0x3fffu) != 0u) __builtin_trap();  // filter_one() ORs the slot offset into the address
+	if ((lds_addr(smem) & 0x3fffu) != 0u) __builtin_trap();  // filter_one() ORs the slot offset into the address
 
 	uint32_t last_item0 = 0;  // first item (+ 4 h) of the last tile filtered: what a raw ring holds at the final flush
-	// ---- tile schedule of the staggered sweep (wave-uniform scalars).  Static: tiles j_begin, j_begin + ts, ... below j_end.
-	// Dynamic (p.chunk_tiles > 0): the workgroups of a query row block draw chunks of p.chunk_tiles consecutive tiles from the row
-	// block's ticket counter, one chunk ahead of the one they sweep.  Why: the 480 workgroups of a cfg2 stage do not run at one speed --
+	// ---- tile schedule (wave-uniform scalars).  Static: tiles j_begin, j_begin + ts, ... below j_end.
+	// Dynamic (p.chunk_tiles > 0; the two-sub-tile body only): the workgroups of a query row block draw chunks of p.chunk_tiles consecutive
+	// tiles from the row block's ticket counter, one chunk ahead of the one they sweep.  Why: the 480 workgroups of a cfg2 stage do not run at one speed --
 	// in-kernel stamps (round 2) put the ends of their tile loops between 193 and 271 us (median 234) for equal shares: 32 CUs hold one
 	// workgroup instead of two, the others differ by XCD / CU placement -- and a launch lasts as long as its slowest workgroup.  With tickets
 	// a fast workgroup simply sweeps more chunks.  Any assignment is exact: a workgroup's survivors go to its own segments whatever tiles
 	// it swept; the repair path finds a split's tiles in p.chunk_owner.  Thread 0 draws a ticket when the workgroup starts the chunk
 	// BEFORE the one the ticket is for (atomic in flight during a whole tile), hands it over through LDS at that tile's barrier.
+	// The one-sub-tile bodies run the same step with `dyn` constant-false: static shares, the ticket statements compile out (Kp = 512
+	// has no LDS left for the ticket words, see FusedCfg).
 	int t_cur = j_begin < j_end ? j_begin : -1, t_cend = j_end, t_step = ts, t_next_chunk = -1, t_prev = -1;
 	bool ticket_pending = false;
-	constexpr bool STAG = MODE == 1 && (QT == 2 || (KP == 512 && !INL));   // the bodies that take the ticket schedule and the hand-placed DMA
-	const bool dyn = STAG && KP < 512 && p.chunk_tiles > 0;
+	const bool dyn = QT == 2 && p.chunk_tiles > 0;
 	// two LDS words used in turn: a ticket is published at the end of one step and read at the head of the next, and nothing but program
 	// order separates that read from the NEXT publication (possible one step later when a chunk is a single tile)
 	uint32_t ticket_slot = lds_addr(smem + Cfg::TICKET_OFF);
-	if constexpr (STAG) {
-		if (dyn) {
-			if (tid == 0) {
-				const uint32_t c = atomicAdd(p.chunk_ctr + rb, 2u);   // the first chunk and the look-ahead
-				if (p.chunk_owner) {
-					if (c < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c] = (uint8_t)split;
-					if (c + 1 < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c + 1] = (uint8_t)split;
-				}
-				lds_write_u32(ticket_slot, c);
-				__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the word is in LDS before this wave reaches the barrier
+	if (dyn) {
+		if (tid == 0) {
+			const uint32_t c = atomicAdd(p.chunk_ctr + rb, 2u);   // the first chunk and the look-ahead
+			if (p.chunk_owner) {
+				if (c < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c] = (uint8_t)split;
+				if (c + 1 < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c + 1] = (uint8_t)split;
 			}
-			__syncthreads();
-			const uint32_t c = lds_load_u32_uniform(ticket_slot);
-			t_step = 1;
-			t_cur = c < (uint32_t)p.n_chunks ? p.tile_begin + (int)c * p.chunk_tiles : -1;
-			t_cend = min(t_cur + p.chunk_tiles, p.tile_end);
-			t_next_chunk = c + 1 < (uint32_t)p.n_chunks ? p.tile_begin + (int)(c + 1) * p.chunk_tiles : -1;
+			lds_write_u32(ticket_slot, c);
+			__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the word is in LDS before this wave reaches the barrier
 		}
+		__syncthreads();
+		const uint32_t c = lds_load_u32_uniform(ticket_slot);
+		t_step = 1;
+		t_cur = c < (uint32_t)p.n_chunks ? p.tile_begin + (int)c * p.chunk_tiles : -1;
+		t_cend = min(t_cur + p.chunk_tiles, p.tile_end);
+		t_next_chunk = c + 1 < (uint32_t)p.n_chunks ? p.tile_begin + (int)(c + 1) * p.chunk_tiles : -1;
 	}
 	const int wave_u = __builtin_amdgcn_readfirstlane(wave);             // (the compiler does not know tid >> 6 is wave-uniform)
 	const uint32_t lds_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(smem));
-	uint32_t dma_off[STAG ? Cfg::TILE_BYTES / 4096 : 1];
-	if constexpr (STAG) {
-		tile_dma_offsets<KP>(dma_off, wave_u, lane);
-		if (t_cur >= 0) tile_dma_s<KP>(p.Et, t_cur, lds_base, wave_u, dma_off);
-	} else if (j_begin < j_end) tile_dma<KP>(p.Et, tile_of(j_begin), smem, wave, lane);
+	uint32_t dma_off[Cfg::TILE_BYTES / 4096];
+	tile_dma_offsets<KP>(dma_off, wave_u, lane);
+	if (t_cur >= 0) tile_dma_s<KP>(p.Et, t_cur, lds_base, wave_u, dma_off);
 	__builtin_amdgcn_s_waitcnt(0x0F70);
 	__syncthreads();
 	ANNCUR_PAD_HERE();
 
-	if constexpr (MODE == 1 && QT == 2) {
+	// One step of the schedule, around a body's drain and tile function: (head) read the pending ticket, pick the next tile, issue its DMA into
+	// the other buffer, draw the ticket of the chunk after the one that tile opens; (tail) wait, publish the ticket, barrier, advance.
+#define SWEEP_STEP_HEAD(CUR)                                                                                                    \
+		const int J = t_cur;                                                                                                    \
+		if (ticket_pending) {  /* (uniform) the ticket thread 0 drew during the previous step */                                \
+			const uint32_t c = lds_load_u32_uniform(ticket_slot);                                                               \
+			t_next_chunk = c < (uint32_t)p.n_chunks ? p.tile_begin + (int)c * p.chunk_tiles : -1;                               \
+			ticket_pending = false;                                                                                             \
+			ticket_slot ^= 4u;  /* (TICKET_OFF is 16-byte aligned) */                                                           \
+		}                                                                                                                       \
+		int nx = J + t_step;                                                                                                    \
+		bool crossed = false;  /* (uniform) the next tile opens the look-ahead chunk: draw the ticket of the one after it */    \
+		if (nx >= t_cend) { nx = t_next_chunk; crossed = dyn && nx >= 0; }                                                      \
+		if (nx >= 0) tile_dma_s<KP>(p.Et, nx, lds_base + ((CUR) ^ 1) * Cfg::TILE_BYTES, wave_u, dma_off);                       \
+		uint32_t ticket = 0;                                                                                                    \
+		if (crossed && tid == 0) ticket_draw(ticket, p.chunk_ctr + rb);  /* in flight until ticket_wait() below */
+#define SWEEP_STEP_TAIL()                                                                                                       \
+		ticket_wait(ticket);  /* vmcnt(0): the DMA of the next tile, the queue stores issued with it and the ticket have landed */ \
+		if (crossed) {                                                                                                          \
+			if (tid == 0) {                                                                                                     \
+				lds_write_u32(ticket_slot, ticket);                                                                             \
+				if (p.chunk_owner && ticket < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + ticket] = (uint8_t)split; \
+				__builtin_amdgcn_s_waitcnt(0xC07F);                                                                             \
+			}                                                                                                                   \
+			ticket_pending = true;                                                                                              \
+			t_cend = min(nx + p.chunk_tiles, p.tile_end);                                                                       \
+		}                                                                                                                       \
+		__syncthreads();                                                                                                        \
+		t_prev = J; t_cur = nx;
+
+	if constexpr (QT == 2) {
 		// ---- staggered sweep (stagger_tile): tile loop unrolled by two so that the LDS buffer parity is a compile-time offset
 		f32x16 acc1;
 #pragma unroll
@@ -649,24 +728,11 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 		// stagger_tile() counts LDS reads with lgkmcnt(n): no scalar load of the prologue may still be in flight (scalar loads share
 		// the counter and return out of order)
 		__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0) only
-#define STAGGER_DMA(NX, CUR) tile_dma_s<KP>(p.Et, (NX), lds_base + ((CUR) ^ 1) * Cfg::TILE_BYTES, wave_u, dma_off)
 // (Round 3 tried draining by occupancy as well -- a ballot "some lane's ring holds >= 3 / >= 4 entries" per step, beside or instead of the
 //  planned window: both cost 4 % of the sweep at cfg2, same box, alternating -- the check itself, not the drains.  The planned window stays.)
 #define STAGGER_STEP(CUR)                                                                                                       \
 		do {                                                                                                                    \
-			const int J = t_cur;                                                                                                \
-			if (ticket_pending) {  /* (uniform) the ticket thread 0 drew during the previous step */                            \
-				const uint32_t c = lds_load_u32_uniform(ticket_slot);                                                           \
-				t_next_chunk = c < (uint32_t)p.n_chunks ? p.tile_begin + (int)c * p.chunk_tiles : -1;                           \
-				ticket_pending = false;                                                                                         \
-				ticket_slot ^= 4u;  /* (TICKET_OFF is 16-byte aligned) */                                                       \
-			}                                                                                                                   \
-			int nx = J + t_step;                                                                                                \
-			bool crossed = false;  /* (uniform) the next tile opens the look-ahead chunk: draw the ticket of the one after it */ \
-			if (nx >= t_cend) { nx = t_next_chunk; crossed = dyn && nx >= 0; }                                                  \
-			if (nx >= 0) STAGGER_DMA(nx, CUR);                                                                                  \
-			uint32_t ticket = 0;                                                                                                \
-			if (crossed && tid == 0) ticket_draw(ticket, p.chunk_ctr + rb);  /* in flight until ticket_wait() below */          \
+			SWEEP_STEP_HEAD(CUR)                                                                                                \
 			if (t_prev < dense_end || --flush_in2 <= 0) {                                                                       \
 				flush_in2 = p.flush_tiles;                                                                                      \
 				/* (a raw ring holds one tile: sub-tile 0 of the previous tile, sub-tile 1 of the one before) */                \
@@ -674,20 +740,9 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 				flush_queue<Cfg::QDEPTH>(lq1, qcnt[1], seg0 + seg_dt, ncand[1], (uint32_t)p.capg, (uint32_t)p.I, tau[1], item0_pp); \
 			}                                                                                                                   \
 			const uint32_t item0 = (uint32_t)J * TILE_I + 4 * h;                                                                \
-			stagger_tile<KP, CUR, PRED, INL>(aoff, xb, acc1, tau[0], tau1_prev, item0, item0_prev, lq0, lq1, qcnt[0], qcnt[1], J < dense_end || every_tile); \
+			stagger_tile<KP, CUR, PRED>(aoff, xb, acc1, tau[0], tau1_prev, item0, item0_prev, lq0, lq1, qcnt[0], qcnt[1], J < dense_end || every_tile); \
 			tau1_prev = tau[1]; item0_pp = item0_prev; item0_prev = item0;                                                      \
-			ticket_wait(ticket);  /* vmcnt(0): the DMA of the next tile, the queue stores issued with it and the ticket have landed */ \
-			if (crossed) {                                                                                                      \
-				if (tid == 0) {                                                                                                 \
-					lds_write_u32(ticket_slot, ticket);                                                                         \
-					if (p.chunk_owner && ticket < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + ticket] = (uint8_t)split; \
-					__builtin_amdgcn_s_waitcnt(0xC07F);                                                                         \
-				}                                                                                                               \
-				ticket_pending = true;                                                                                          \
-				t_cend = min(nx + p.chunk_tiles, p.tile_end);                                                                   \
-			}                                                                                                                   \
-			__syncthreads();                                                                                                    \
-			t_prev = J; t_cur = nx;                                                                                             \
+			SWEEP_STEP_TAIL()                                                                                                   \
 		} while (0)
 		while (t_cur >= 0) {
 			STAGGER_STEP(0);
@@ -701,8 +756,8 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 			filter_one<Cfg::QDEPTH>(acc1[e], e, tau1_prev, item0_prev, lq1, qcnt[1]);
 		mark_wrapped_raw<Cfg::QDEPTH>(acc1, lq1, qcnt[1]);  // (its ring was just drained: exact in every split)
 		last_item0 = item0_prev;
-	} else if constexpr (STAG && QT == 1) {
-		// ---- software-pipelined sweep for Kp = 512 (stagger1_tile) on the ticket schedule: tile loop unrolled by two (buffer parity =
+	} else {
+		// ---- one sub-tile per wave, software-pipelined across tiles (stagger1_tile): tile loop unrolled by two (buffer parity =
 		// immediate offset); even steps accumulate into accA and filter accB, odd steps the other way round
 		f32x16 accA, accB;
 #pragma unroll
@@ -716,19 +771,7 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 		__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): stagger1_tile() counts LDS reads
 #define STAGGER1_STEP(CUR, ACC, ACCP)                                                                                           \
 		do {                                                                                                                    \
-			const int J = t_cur;                                                                                                \
-			if (ticket_pending) {                                                                                               \
-				const uint32_t c = lds_load_u32_uniform(ticket_slot);                                                           \
-				t_next_chunk = c < (uint32_t)p.n_chunks ? p.tile_begin + (int)c * p.chunk_tiles : -1;                           \
-				ticket_pending = false;                                                                                         \
-				ticket_slot ^= 4u;                                                                                              \
-			}                                                                                                                   \
-			int nx = J + t_step;                                                                                                \
-			bool crossed = false;                                                                                               \
-			if (nx >= t_cend) { nx = t_next_chunk; crossed = dyn && nx >= 0; }                                                  \
-			if (nx >= 0) STAGGER_DMA(nx, CUR);                                                                                  \
-			uint32_t ticket = 0;                                                                                                \
-			if (crossed && tid == 0) ticket_draw(ticket, p.chunk_ctr + rb);                                                     \
+			SWEEP_STEP_HEAD(CUR)                                                                                                \
 			if (t_prev < dense_end || --flush_in2 <= 0) {                                                                       \
 				flush_in2 = p.flush_tiles;                                                                                      \
 				/* (a raw ring holds the tile before the previous one, filtered during the previous step) */                    \
@@ -736,18 +779,7 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 			}                                                                                                                   \
 			stagger1_tile<KP, CUR>(aoff8, xb[0], ACC, ACCP, tau_prev, item0_prev, lq0, qcnt[0], J < dense_end || every_tile);   \
 			tau_prev = tau[0]; item0_pp = item0_prev; item0_prev = (uint32_t)J * TILE_I + 4 * h;                                \
-			ticket_wait(ticket);                                                                                                \
-			if (crossed) {                                                                                                      \
-				if (tid == 0) {                                                                                                 \
-					lds_write_u32(ticket_slot, ticket);                                                                         \
-					if (p.chunk_owner && ticket < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + ticket] = (uint8_t)split; \
-					__builtin_amdgcn_s_waitcnt(0xC07F);                                                                         \
-				}                                                                                                               \
-				ticket_pending = true;                                                                                          \
-				t_cend = min(nx + p.chunk_tiles, p.tile_end);                                                                   \
-			}                                                                                                                   \
-			__syncthreads();                                                                                                    \
-			t_prev = J; t_cur = nx;                                                                                             \
+			SWEEP_STEP_TAIL()                                                                                                   \
 		} while (0)
 		bool last_in_a = false;  // (uniform) which accumulator holds the last tile
 		while (t_cur >= 0) {
@@ -758,7 +790,6 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 			last_in_a = false;
 		}
 #undef STAGGER1_STEP
-#undef STAGGER_DMA
 		flush_queue<Cfg::QDEPTH, FLUSH_BATCH>(lq0, qcnt[0], seg0, ncand[0], (uint32_t)p.capg, (uint32_t)p.I, tau[0], item0_pp);
 		if (last_in_a) {  // drain: the last tile (its ring was just drained: the raw path is exact in every split)
 #pragma unroll
@@ -770,123 +801,14 @@ __global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_ke
 			mark_wrapped_raw<Cfg::QDEPTH>(accB, lq0, qcnt[0]);
 		}
 		last_item0 = item0_prev;
-	} else if constexpr (MODE == 1 && QT == 1 && KP >= 128 && !INL) {  // (INL: the plain loop below instead; no launch asks for it)
-		// ---- software-pipelined sweep for Kp = 512 (stagger1_tile): tile loop unrolled by two (buffer parity = immediate offset);
-		// even steps accumulate into accA and filter accB, odd steps the other way round
-		f32x16 accA, accB;
-#pragma unroll
-		for (int e = 0; e < 16; ++e) { accA[e] = 0.f; accB[e] = 0.f; }
-		float tau_prev = INFINITY;   // no previous tile yet: the filter never fires
-		uint32_t item0_prev = 0;
-		uint32_t aoff8[8];
-#pragma unroll
-		for (int s = 0; s < 8; ++s) aoff8[s] = lds_addr(smem) + (uint32_t)(r * CPR + ((2 * s + h) ^ (r & 15))) * 16u;
-		int flush_in2 = p.flush_tiles;
-		__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): stagger1_tile() counts LDS reads
-#define STAGGER1_STEP(CUR, J, ACC, ACCP)                                                                                        \
-		do {                                                                                                                    \
-			if ((J) + ts < j_end) tile_dma<KP>(p.Et, (J) + ts, smem + ((CUR) ^ 1) * Cfg::TILE_BYTES, wave, lane);               \
-			if ((J) - ts < dense_end || --flush_in2 <= 0) {                                                                     \
-				flush_in2 = p.flush_tiles;                                                                                      \
-				/* (a raw ring holds the tile before the previous one, filtered during the previous step) */                    \
-				flush_queue<Cfg::QDEPTH, FLUSH_BATCH>(lq0, qcnt[0], seg0, ncand[0], (uint32_t)p.capg, (uint32_t)p.I, tau[0], item0_prev - (uint32_t)ts * TILE_I); \
-			}                                                                                                                   \
-			stagger1_tile<KP, CUR>(aoff8, xb[0], ACC, ACCP, tau_prev, item0_prev, lq0, qcnt[0], (J) < dense_end || every_tile);               \
-			tau_prev = tau[0]; item0_prev = (uint32_t)(J) * TILE_I + 4 * h;                                                     \
-			__builtin_amdgcn_s_waitcnt(0x0F70);                                                                                 \
-			__syncthreads();                                                                                                    \
-		} while (0)
-		bool last_in_a = false;  // (uniform) which accumulator holds the last tile
-		for (int j = j_begin; j < j_end; j += 2 * ts) {
-			STAGGER1_STEP(0, j, accA, accB);
-			last_in_a = true;
-			if (j + ts < j_end) { STAGGER1_STEP(1, j + ts, accB, accA); last_in_a = false; }
-		}
-#undef STAGGER1_STEP
-		flush_queue<Cfg::QDEPTH, FLUSH_BATCH>(lq0, qcnt[0], seg0, ncand[0], (uint32_t)p.capg, (uint32_t)p.I, tau[0], item0_prev - (uint32_t)ts * TILE_I);
-		if (last_in_a) {  // drain: the last tile (its ring was just drained: the raw path is exact in every split)
-#pragma unroll
-			for (int e = 0; e < 16; ++e) filter_one<Cfg::QDEPTH>(accA[e], e, tau_prev, item0_prev, lq0, qcnt[0]);
-			mark_wrapped_raw<Cfg::QDEPTH>(accA, lq0, qcnt[0]);
-		} else {
-#pragma unroll
-			for (int e = 0; e < 16; ++e) filter_one<Cfg::QDEPTH>(accB[e], e, tau_prev, item0_prev, lq0, qcnt[0]);
-			mark_wrapped_raw<Cfg::QDEPTH>(accB, lq0, qcnt[0]);
-		}
-		last_item0 = item0_prev;
-	} else {
-	int flush_in = p.flush_tiles, cur = 0;
-	for (int j = j_begin; j < j_end; j += ts, cur ^= 1) {
-		const int tile = tile_of(j);
-		const bool more = j + ts < j_end;
-		if (more) tile_dma<KP>(p.Et, tile_of(j + ts), smem + (cur ^ 1) * Cfg::TILE_BYTES, wave, lane);
-		bool ring_fresh = false;  // (uniform) the rings were drained at the head of this step: they will hold nothing but this tile
-		if (MODE == 1) {
-			// drain the hit queues of the previous tiles right behind the DMA: the stores get the whole MFMA phase to retire
-			// (always behind a dense tile and at the head of the last step: see mark_wrapped_raw below)
-			if (j - ts < dense_end || --flush_in <= 0 || !more) {
-				flush_in = p.flush_tiles;
-				ring_fresh = true;
-#pragma unroll
-				for (int t = 0; t < QT; ++t) flush_queue<Cfg::QDEPTH>(lq0 + t * Cfg::QDEPTH * 2048, qcnt[t], seg0 + t * seg_dt, ncand[t], (uint32_t)p.capg, (uint32_t)p.I, tau[t], last_item0);
-			}
-		}
-
-		f32x16 acc[QT];
-#pragma unroll
-		for (int t = 0; t < QT; ++t)
-#pragma unroll
-			for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-		const u32x4 *tb = reinterpret_cast<const u32x4 *>(smem + cur * Cfg::TILE_BYTES);
-#pragma unroll
-		for (int s = 0; s < KSTEPS; ++s) {
-			const u32x4 w = tb[r * CPR + swz<CPR>(r, 2 * s + h)];
-			const bf16x8 a = __builtin_bit_cast(bf16x8, w);
-#pragma unroll
-			for (int t = 0; t < QT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[t][s], acc[t], 0, 0, 0);
-		}
-
-		// ---- epilogue.  C/D layout: query = lane & 31 (col), item row = (e & 3) + 8 * (e >> 2) + 4 * h
-		if (MODE == 0) {
-#pragma unroll
-			for (int t = 0; t < QT; ++t) {
-				if (GROUP == 16) {
-					float m = acc[t][0];
-#pragma unroll
-					for (int e = 1; e < 16; ++e) m = fmaxf(m, acc[t][e]);
-					if (qv[t] < p.Q) p.gmax[qv[t] * p.n_groups + (int64_t)j * 2 + h] = m;
-				} else {
-					float4 m;
-					m.x = fmaxf(fmaxf(acc[t][0], acc[t][1]), fmaxf(acc[t][2], acc[t][3]));
-					m.y = fmaxf(fmaxf(acc[t][4], acc[t][5]), fmaxf(acc[t][6], acc[t][7]));
-					m.z = fmaxf(fmaxf(acc[t][8], acc[t][9]), fmaxf(acc[t][10], acc[t][11]));
-					m.w = fmaxf(fmaxf(acc[t][12], acc[t][13]), fmaxf(acc[t][14], acc[t][15]));
-					if (qv[t] < p.Q) *reinterpret_cast<float4 *>(p.gmax + qv[t] * p.n_groups + ((int64_t)j * 2 + h) * 4) = m;
-				}
-			}
-		} else {
-			const uint32_t item0 = (uint32_t)tile * TILE_I + 4 * h;
-#pragma unroll
-			for (int t = 0; t < QT; ++t) {
-				filter_queue<Cfg::QDEPTH>(acc[t], tau[t], item0, lq0 + t * Cfg::QDEPTH * 2048, qcnt[t]);
-				// (uniform) a raw ring must be drained before the next tile's filter: the next step drains when this tile is dense; the
-				// last tile is followed by the final drain
-				if (ring_fresh && (j < dense_end || !more || every_tile)) mark_wrapped_raw<Cfg::QDEPTH>(acc[t], lq0 + t * Cfg::QDEPTH * 2048, qcnt[t]);
-			}
-			last_item0 = item0;
-		}
-		__builtin_amdgcn_s_waitcnt(0x0F70);  // the DMA of tile j+1 (and the queue stores issued with it) have landed
-		__syncthreads();
 	}
-	}  // plain loop
+#undef SWEEP_STEP_HEAD
+#undef SWEEP_STEP_TAIL
 
-#undef tile_of
-	if (MODE == 1) {
 #pragma unroll
-		for (int t = 0; t < QT; ++t) {
-			flush_queue<Cfg::QDEPTH, FLUSH_BATCH>(lq0 + t * Cfg::QDEPTH * 2048, qcnt[t], seg0 + t * seg_dt, ncand[t], (uint32_t)p.capg, (uint32_t)p.I, tau[t], last_item0);
-			if (qv[t] < p.Q) p.seg_cnt[qv[t] * p.nseg + h * p.S + split] = ncand[t];
-		}
+	for (int t = 0; t < QT; ++t) {
+		flush_queue<Cfg::QDEPTH, FLUSH_BATCH>(lq0 + t * Cfg::QDEPTH * 2048, qcnt[t], seg0 + t * seg_dt, ncand[t], (uint32_t)p.capg, (uint32_t)p.I, tau[t], last_item0);
+		if (qv[t] < p.Q) p.seg_cnt[qv[t] * p.nseg + h * p.S + split] = ncand[t];
 	}
 }
 
@@ -1049,7 +971,7 @@ __global__ __launch_bounds__(256, 2) void error_lds_kernel(const FusedParams p, 
 		}
 #endif
 	};
-	__builtin_amdgcn_s_waitcnt(0x0F70);  // see score_kernel: keeps vmcnt(0) out of the tile loop
+	__builtin_amdgcn_s_waitcnt(0x0F70);  // see score_sweep_kernel: keeps vmcnt(0) out of the tile loop
 
 	float se[QT], sn[QT];
 #pragma unroll
@@ -1139,7 +1061,7 @@ __global__ __launch_bounds__(256, 2) void error_kernel(const FusedParams p, cons
 			xb[t][s] = __builtin_bit_cast(bf16x8, w);
 		}
 	}
-	__builtin_amdgcn_s_waitcnt(0x0F70);  // see score_kernel: keeps vmcnt(0) out of the tile loop
+	__builtin_amdgcn_s_waitcnt(0x0F70);  // see score_sweep_kernel: keeps vmcnt(0) out of the tile loop
 
 	const int j_begin = split * p.tiles_per_split, j_end = min(j_begin + p.tiles_per_split, p.n_tiles);
 	float se[QT], sn[QT];
@@ -1670,7 +1592,7 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, const PlanOpts &opts) 
 	if (!plan_sample(P, k, 2, 4)) return P;   // two groups of 16 per sampled tile (the sub-tile rows with bit 2 clear / set)
 	int slots = ((P.QT == 1 && KP <= 256) ? 3 : 2) * num_cu();
 	// Dynamic tile schedule (staggered 32x32x16 sweep, Kp <= 256): tickets of CHUNK_TILES tiles per query row block instead of fixed shares
-	// (score_kernel).  Workgroups per row block: enough to fill every slot (rounded UP -- a workgroup that finds no ticket left ends at
+	// (score_sweep_kernel).  Workgroups per row block: enough to fill every slot (rounded UP -- a workgroup that finds no ticket left ends at
 	// once), at most 32 so that the 2 S segments of a query fit the wave-level select.
 	// Kp = 512: the body with the wave-level queue (score_q16.hpp: queue + counters + ticket words fit the 16 KB the rings took) unless
 	// ANNCUR_TOPK_MFMA32 asks for the per-lane-ring body (static shares: no LDS left for its ticket words) or I >= 2^26.  (16x16x32 MFMAs
@@ -1982,14 +1904,13 @@ template <int KP, int QTV = FusedCfg<KP>::QT>
 int launch_fused(const FusedPlan &P, const TopkCall &c) {
 	using Cfg = FusedCfg<KP, QTV>;
 	unsigned char *const ws = c.ws; const hipStream_t st = c.st; const EvalArgs *const ea = c.ea;
-	FusedParams p{};   // (the fields no kernel reads stay zero)
+	FusedParams p{};
 	p.X = (const uint16_t *)c.X; p.ldx = c.ldx; p.Et = (const uint16_t *)c.Et; p.Q = c.Q; p.I = c.I;
 	p.n_tiles = P.n_tiles; p.n_full_tiles = P.n_full; p.S = P.S; p.tiles_per_split = P.tiles_per_split;
 	p.tile_begin = 0; p.tile_end = P.n_tiles; p.carry = 0; p.tile_step = 1;
 	p.n_st = P.n_st; p.S0 = P.S0; p.st_per_split = P.st_per_split; p.sample_leading = P.leading;
 	p.gmax = (float *)(ws + P.off_gmax); p.n_groups = P.n_groups;
 	p.cand = (uint2 *)(ws + P.off_cand); p.seg_cnt = (uint32_t *)(ws + P.off_segcnt); p.capg = P.capg; p.flush_tiles = P.flush_tiles;
-	p.tau_bias = 0.f;
 	p.nfb = (uint32_t *)ws; p.nseg = P.nseg;
 	p.ladder_on = P.ladder ? 1 : 0; p.ladder_k = (uint32_t)c.k; p.ladder_mask = (uint32_t)(LADDER_PERIOD - 1);
 	p.ladder = (const float *)(ws + P.off_lvl); p.ladder_cnt = (uint32_t *)(ws + P.off_lcnt); p.tau_final = (float *)(ws + P.off_tau2);
@@ -2024,9 +1945,9 @@ int launch_fused(const FusedPlan &P, const TopkCall &c) {
 			}
 		}
 		if (P.group == 16)
-			hipLaunchKernelGGL((score_kernel<KP, 0, 16, false, false, QTV>), dim3(p.n_wg), dim3(256), 2 * Cfg::TILE_BYTES, st, pp);
+			hipLaunchKernelGGL((score_prepass_kernel<KP, 16, QTV>), dim3(p.n_wg), dim3(256), 2 * Cfg::TILE_BYTES, st, pp);
 		else
-			hipLaunchKernelGGL((score_kernel<KP, 0, 4, false, false, QTV>), dim3(p.n_wg), dim3(256), 2 * Cfg::TILE_BYTES, st, pp);
+			hipLaunchKernelGGL((score_prepass_kernel<KP, 4, QTV>), dim3(p.n_wg), dim3(256), 2 * Cfg::TILE_BYTES, st, pp);
 		return ANNCUR_OK;
 	};
 	auto launch_stage = [&](int stg, int prev) -> int {
@@ -2035,9 +1956,9 @@ int launch_fused(const FusedPlan &P, const TopkCall &c) {
 		p.flush_tiles = P.stage_flush[stg]; p.carry = stg > 0;
 		p.tile_step = tile_step;
 		if (chunk > 0) {
-			// (row-block-major work ids -- the workgroups of a row block on ONE XCD -- were measured for the ticket schedule, round 3, one box:
-			//  cfg4 shape sweep 5.13 -> 6.28 ms and L2-miss traffic 9.0 -> 13.0 GB per launch, cfg2 0.451 -> 0.480 ms: split-major stays)
-			p.rb_major = 0;
+			// (work ids are split-major in every kernel: split = wid / n_rb.  Row-block-major ids -- the workgroups of a row block on ONE XCD -- were
+			//  measured for the ticket schedule, round 3, one box: cfg4 shape sweep 5.13 -> 6.28 ms and L2-miss traffic 9.0 -> 13.0 GB per launch,
+			//  cfg2 0.451 -> 0.480 ms)
 			p.chunk_tiles = chunk; p.n_chunks = (p.tile_end - p.tile_begin + chunk - 1) / chunk;
 			// XCD-sliced tickets: the wave-queue bodies (Kp = 512: the shape whose sweep was close to the fabric's bandwidth; Kp <= 256: traffic only); [row block][slice] counters
 			// (Kp <= 256: measured at cfg2, one process, interleaved -- sweep launches 0.5030 ms sliced vs 0.4914 unsliced, bare loops level:
@@ -2065,9 +1986,9 @@ int launch_fused(const FusedPlan &P, const TopkCall &c) {
 			if (P.body16) return launch(score16_kernel<KP>, Fused16Cfg<KP>::LDS_BYTES);
 		}
 		if constexpr (Cfg::QT == 2) {  // the exec-mask filter (the branch-free filter lives in the staggered path)
-			if (P.stage_pred[stg]) return launch(score_kernel<KP, 1, 16, true, false, QTV>, Cfg::LDS_BYTES);
+			if (P.stage_pred[stg]) return launch(score_sweep_kernel<KP, true, QTV>, Cfg::LDS_BYTES);
 		}
-		return launch(score_kernel<KP, 1, 16, false, false, QTV>, Cfg::LDS_BYTES);
+		return launch(score_sweep_kernel<KP, false, QTV>, Cfg::LDS_BYTES);
 	};
 	return run_pipeline(P, c, stages, 1, p.tau, p.tau_stride, launch_prepass, launch_stage);
 }
@@ -2114,7 +2035,6 @@ int launch_wide(const FusedPlan &P, const TopkCall &c) {
 	p.n_st = P.n_st; p.S0 = P.S0; p.st_per_split = P.st_per_split; p.sample_leading = P.leading; p.n_bt_full = P.n_full;
 	p.gmax = (float *)(ws + P.off_gmax); p.n_groups = P.n_groups;
 	p.cand = (uint2 *)(ws + P.off_cand); p.seg_cnt = (uint32_t *)(ws + P.off_segcnt); p.capg = P.capg;
-	p.tau_bias = 0.f;
 	if (const int rc = anncur_ensure_dyn_lds((const void *)wide_kernel<1, 16>, W_LDS_TOTAL)) return rc;
 	ANNCUR_HIP_OK(hipMemsetAsync(ws, 0, 256, st));   // (the wide prepass does not clear the header)
 	// prepass over the sampled block tiles
@@ -2326,7 +2246,7 @@ enum PlanWord {
 	PW_STAGE_FLUSH = 14,     // [3] ring drain period
 	PW_LADDER = 17, PW_LADDER_K2, PW_LADDER_PERIOD,   // threshold ladder (1: the sweep raises its thresholds in-launch, score16.hpp; 0: staged), rank of its top level, LADDER_PERIOD
 	PW_GMAX_OFF256, PW_N_GROUPS,   // workspace offset of the prepass' group maxima in 256-byte units, group maxima per query (row pitch of that array)
-	PW_PREPASS16, PW_S0,     // prepass kernel (1: prepass16_kernel, the sweep's 16x16x32 body; 0: score_kernel<KP, 0, ..>), prepass item splits
+	PW_PREPASS16, PW_S0,     // prepass kernel (1: prepass16_kernel, the sweep's 16x16x32 body; 0: score_prepass_kernel<KP, ..>), prepass item splits
 	PW_N_EX = 24,            // anncur_score_topk_plan_ex returns the words up to here
 	PW_STAGE_TPS = 24,       // [3] tiles per item split of each stage: anncur_eval_fused_plan returns them too
 	PW_N = 27

@@ -1,5 +1,5 @@
 // Sweep kernel for Kp = 512 with the wave-level candidate queue and the dynamic tile schedule (round 3).  The Kp = 512 body of
-// score_kernel (one 32-query sub-tile per wave -- the query operand alone takes 128 VGPRs --, cross-tile software pipeline: while the
+// score_sweep_kernel (one 32-query sub-tile per wave -- the query operand alone takes 128 VGPRs --, cross-tile software pipeline: while the
 // MFMA chain of tile j runs, the filter of tile j-1's accumulator is issued in its shadow) uses exactly 80 KB of LDS per workgroup, 64 KB
 // of tile buffers and 16 KB of per-lane candidate rings: no room for the two ticket words of the dynamic schedule (16 bytes more halved
 // the occupancy: -20 %).  With the candidates in ONE queue per wave (score16.hpp: WaveQueue, wq_drain, filter16_one) the queues take
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 	const int c16 = lane & 15, g4 = lane >> 4;
 	const int wid = xcd_remap(blockIdx.x, p.n_wg);
 	const int n_rb = (int)((p.Q + C::BQ - 1) / C::BQ);
-	const int split = p.rb_major ? wid % p.S : wid / n_rb, rb = p.rb_major ? wid / p.S : wid - split * n_rb;
+	const int split = wid / n_rb, rb = wid - split * n_rb;
 
 	// ---- this lane's two queries: B operand fragments, resident for the whole kernel.  B[k = 8 (lane >> 4) + j][col = lane & 15]
 	bf16x8 xb[2][KS32];
@@ -94,10 +94,10 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 			xb[t][s] = __builtin_bit_cast(bf16x8, wv);
 		}
 	}
-	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see score_kernel
+	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see score_sweep_kernel
 
-	const float tau0 = qv[0] < p.Q ? p.tau[qv[0] * p.tau_stride] + p.tau_bias : INFINITY;
-	const float tau1 = qv[1] < p.Q ? p.tau[qv[1] * p.tau_stride] + p.tau_bias : INFINITY;
+	const float tau0 = qv[0] < p.Q ? p.tau[qv[0] * p.tau_stride] : INFINITY;
+	const float tau1 = qv[1] < p.Q ? p.tau[qv[1] * p.tau_stride] : INFINITY;
 	// candidate path: the wave's queue, its 32 per-query counts (lane l < 32 <-> local query l = 16 * sub-tile + (lane & 15))
 	const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 	const uint32_t lds_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(smem));
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 		lds_write_u32(w.cnt + (uint32_t)lane * 4u, q < p.Q ? (p.carry ? p.seg_cnt[q * p.nseg + split] : 0u) : PAD_ROW_COUNT);
 	}
 
-	// ---- tile schedule: tickets (see score_kernel), or a static contiguous share
+	// ---- tile schedule: tickets (see score_sweep_kernel), or a static contiguous share
 	const int j_begin = p.tile_begin + split * p.tiles_per_split, j_end = min(j_begin + p.tiles_per_split, p.tile_end);
 	int t_cur = j_begin < j_end ? j_begin : -1, t_cend = j_end, t_next_chunk = -1;
 	bool ticket_pending = false;

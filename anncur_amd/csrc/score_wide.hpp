@@ -6,7 +6,7 @@
 //   workgroup = 8 waves = 256 queries x one item split; block tile = 256 items x 256 queries, K streamed in 64-wide k-tiles
 //   through two 64 KiB LDS stages (items 32 KiB + queries 32 KiB, filled by global_load_lds_dwordx4, one barrier per k-tile);
 //   wave (wi, wq) owns items [128 wi, +128) x queries [64 wq, +64): 4 x 2 accumulators of v_mfma_f32_32x32x16_bf16 (128 VGPRs).
-// Orientation as in score_kernel: D[item][query], the query sits on the LANE, so the threshold compare is lane-local.  After
+// Orientation as in score_sweep_kernel: D[item][query], the query sits on the LANE, so the threshold compare is lane-local.  After
 // the last k-tile of a block tile the 128 accumulator registers are filtered against the lane's threshold; survivors are
 // appended straight to the lane's private candidate segment in HBM -- segment (query, lane half h, wave item half wi, item
 // split): written by exactly one lane of one workgroup, no atomics.  One compare per Kp/16 MFMAs: the filter is amortised
@@ -35,7 +35,6 @@ struct WideParams {
 	const float *tau; int tau_stride;
 	uint2 *cand; uint32_t *seg_cnt; int capg;
 	int n_wg;
-	float tau_bias;  // always 0 (read by wide_kernel: a tuning offset of the threshold, no longer set)
 };
 
 // work id -> (query block, item split).  Consecutive ids (= one XCD after xcd_remap) cover a compact rectangle of
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(512, 2) void wide_kernel(const WideParams p) {
 	for (int t = 0; t < 2; ++t) {
 		qv[t] = qb + wq * 64 + 32 * t + r;
 		const bool ok = qv[t] < p.Q;
-		tau[t] = (MODE == 1 && ok) ? p.tau[qv[t] * p.tau_stride] + p.tau_bias : INFINITY;
+		tau[t] = (MODE == 1 && ok) ? p.tau[qv[t] * p.tau_stride] : INFINITY;
 		ncand[t] = ok ? ((MODE == 1 && p.carry) ? p.seg_cnt[qv[t] * nseg + sg] : 0u) : PAD_ROW_COUNT;
 		segoff[t] = (uint32_t)(((wq * 64 + 32 * t + r) * nseg + sg) * p.capg) * 8u;
 	}

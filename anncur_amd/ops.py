@@ -410,7 +410,7 @@ def rowwise_topk_gather(A, k, tables, out=None, cq_out=None):
 	return TopK(val, idx), cq
 
 
-_KP_CHOICES = (64, 128, 256, 512)   # query operand resident in registers (score_kernel)
+_KP_CHOICES = (64, 128, 256, 512)   # query operand resident in registers (score_sweep_kernel)
 _KP_WIDE_MAX = 4096                  # beyond: LDS-tiled K-general kernel (wide_kernel), Kp a multiple of 128
 
 

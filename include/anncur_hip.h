@@ -327,10 +327,10 @@ int anncur_score_topk_plan(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t 
 /* The plan a call with `flags` (ANNCUR_TOPK_*) would run: out[0 .. n_out), n_out <= 24 = {sample tiles, item tiles, item splits S,
  * segment capacity, group size, candidate segments per (query, item split) -- 2: 32x32x16 sweep, 1: 16x16x32 sweep, 4: wide
  * kernel --, 32-query sub-tiles per wave, number of sweep stages, stage_end[3] (tiles), body per stage[3] (0: 32x32x16 with the ballot
- * filter, 1: 32x32x16 with the exec-mask filter, 2: 16x16x32, 3 / 4: the Kp = 512 body with the wave-level queue on 32x32x16 / 16x16x32 MFMAs), ring
+ * filter, 1: 32x32x16 with the exec-mask filter, 2: 16x16x32, 4: the Kp = 512 body with the wave-level queue on 16x16x32 MFMAs), ring
  * drain period per stage[3], threshold ladder (1: in-launch ladder, 0: none), rank of the ladder's top level among the sampled group
  * maxima, tiles between two fetches of a wave's ladder counters, workspace offset of the prepass' group maxima (256-byte units), group
- * maxima per query, prepass kernel (1: prepass16_kernel on the sweep's 16x16x32 body, 0: score_kernel<Kp, 0, ..>), prepass item splits}.  Lets a caller (and the parity tests) see that a variant flag was
+ * maxima per query, prepass kernel (1: prepass16_kernel on the sweep's 16x16x32 body, 0: score_prepass_kernel<Kp, ..>), prepass item splits}.  Lets a caller (and the parity tests) see that a variant flag was
  * honoured for the shape. */
 int anncur_score_topk_plan_ex(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t flags, int32_t *out, int32_t n_out);
 /* The plan anncur_eval_fused(_ex) runs for a cell (read-only, host code, no device needed): out[0 .. n_out), n_out <= 27 = the 24 words of

@@ -1,7 +1,7 @@
 """Static check of the sweep kernels' inline-asm LDS reads: no instruction may touch the destination registers of a
 `ds_read_*` that a preceding `s_waitcnt lgkmcnt(n)` has not yet retired.
 
-The fragment reads of score_kernel / score16_kernel / wide_kernel are inline asm with COUNTED waits; hipcc does not know that the
+The fragment reads of score_sweep_kernel / score16_kernel / wide_kernel are inline asm with COUNTED waits; hipcc does not know that the
 asm's output register is still in flight after the statement, so nothing but the source's own wait statements stops it from
 copying, spilling or consuming such a register early (the hardware has no interlock: the instruction reads stale data).  LDS
 instructions of one wave return in order, so the check is a FIFO walk over the disassembly: every DS instruction enters the queue,

@@ -8,12 +8,17 @@ top-k -- values descending, ties by ascending row -- bit for bit.  Where the pla
   (b) tau0 <= tau_final <= the true k-th score;
   (c) the levels ascend and start at or above tau0.
 Needs an MI355X."""
+import functools
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 from hypothesis import HealthCheck, given, settings, strategies as st
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fused_exact_cases as fx  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 # Deterministic by default (the same examples every run); ANNCUR_FUZZ=1 draws fresh ones and ANNCUR_FUZZ_EXAMPLES=n draws more.
@@ -157,6 +162,64 @@ def test_fused_all_negative_scores_with_a_ragged_tail(ops, body, tail, k):
 		from anncur_amd import _lib
 		with pytest.raises(_lib.AnncurHipError, match="no threshold ladder"):
 			ops.fused_ladder_state(ws, Q, I, Kp, k, **kw)
+
+
+# ------------------------------------------------------------------ qt1: one sub-tile per wave on the sweep's shared tile schedule
+_QT1_Q, _QT1_I, _QT1_K, _QT1_SPLITS = 130, 33011, 100, 207
+# split s sweeps the tiles s, s + 207, ...: 1032 tiles = 204 splits of five (the last tile ends in the first accumulator) and three of four.
+# Hot tiles, every item of which is every query's best score: the first tile of a split, the last of a five-tile and of a four-tile split.
+_QT1_HOT = (100, 10 + 4 * _QT1_SPLITS, 205 + 3 * _QT1_SPLITS)
+
+
+@functools.lru_cache(maxsize=2)
+def _qt1_case(K):
+	def plant(E, g):
+		for t in _QT1_HOT:
+			E[:, t * 32:(t + 1) * 32] = 8
+	X, E, S = fx.sparse_case(_QT1_Q, _QT1_I, K, seed=K, plant=plant)
+	return X, E, S, fx.reference_topk(S, _QT1_K)
+
+
+@pytest.mark.parametrize("leading", [False, True], ids=["strided", "leading"])
+@pytest.mark.parametrize("Kp", [128, 256])
+def test_fused_qt1_static_shares_of_both_parities(ops, Kp, leading):
+	"""ANNCUR_TOPK_QT1 (score_sweep_kernel<Kp, false, 1>: stagger1_tile on the schedule it shares with the Kp = 512 ring body, static interleaved
+	shares).  Q = 130: two row blocks, the second almost all padding; 1032 tiles over 207 splits, so workgroups end on either accumulator;
+	a ragged tail of 19.  Three whole tiles score every query's maximum: each lane finds sixteen survivors in one tile, more than its ring
+	holds, and hands the raw accumulator to the next step's drain (or, for a split's last tile, to the final one).  THE top-k bit for bit,
+	no fallback (no segment overflows: checked on the host scores), and the sweep offers exactly the items at or above the thresholds.
+	Mutation (a build of its own, on an MI355X): the step's drain given the previous tile's first item for a raw ring instead of the
+	one before it -- all four cases fail on the ids."""
+	Q, I, k = _QT1_Q, _QT1_I, _QT1_K
+	kw = dict(qt1=True, leading_sample=leading)
+	plan = ops.fused_plan(Q, I, Kp, k, **kw)
+	assert plan["QT"] == 1 and plan["lg"] == 2 and not plan["ladder"] and plan["n_stages"] == 1, plan
+	S_, n_tiles = plan["splits"], plan["n_tiles"]
+	assert S_ == _QT1_SPLITS and n_tiles == 1032 and n_tiles % S_ != 0 and n_tiles // S_ >= 3 and (n_tiles // S_) % 2 == 0, plan
+	tiles = fx.sample_tiles(plan, I, leading, False)
+	assert not set(_QT1_HOT) & set(tiles.tolist())
+	X, E, S, (want_v, want_rows) = _qt1_case(Kp - 6)   # (K = 122 / 250: every k-step of the chain carries data)
+	assert set((want_rows[0] // 32).tolist()) >= set(_QT1_HOT)   # every hot tile is in the answer
+	Xp, Etp = fx.device_operands(ops, X, E.t(), Kp)
+	ws = fx.poisoned_workspace(ops, Q, I, Kp, k)
+	(v, i), nfb = ops.score_topk_fused(Xp, Etp, I, k, return_fallbacks=True, workspace=ws, **kw)
+	got_i = i.cpu().long()
+	assert ((got_i >= 0) & (got_i < I)).all()
+	assert torch.equal(v.cpu().double(), want_v.double())
+	assert torch.equal(got_i, want_rows)
+	# the threshold the sweep ran with (the k-th largest sampled group maximum, cut to its 16-bit key prefix) and who passes it
+	gm = fx.reference_gmax(S, tiles, plan["group"])
+	assert gm.shape[1] <= 4096
+	tau = fx.coarse_floor(torch.topk(gm, k, dim=1).values[:, -1].numpy())
+	hit = S.float() >= torch.from_numpy(tau)[:, None]
+	# candidate segment of an item: (split = tile % splits, lane half = bit 2 of its row in the tile)
+	item = torch.arange(I)
+	seg = ((item // 32) % S_) * 2 + ((item % 32) >> 2 & 1)
+	per_seg = torch.zeros(Q, 2 * S_, dtype=torch.int64).index_add_(1, seg, hit.long())
+	assert int(per_seg.max()) <= plan["segment_capacity"] and int(per_seg.max()) >= 16, int(per_seg.max())
+	assert int(nfb.item()) == 0, f"{int(nfb.item())} queries fell back although no segment overflows"
+	surv = ops.fused_survivors(ws, Q, I, Kp, k, **kw) * Q
+	assert round(surv) == int(hit.sum()) and abs(surv - round(surv)) < 1e-3, (surv, int(hit.sum()))
 
 
 # ------------------------------------------------------------------ exact-integer fuzz
