@@ -34,6 +34,21 @@
 // its own threshold is there; after the k-th count of a level each of the S waves of the query adds at most one fetch period, the lag tile,
 // the last tile's tail and what its queue still holds ahead of a drain: (LADDER_PERIOD + 2) * TILE_I + DRAIN_AT per query.  plan_fused
 // (score_fused.hip) runs the ladder only while k + S * that stays <= 32768, half a field (or I < 65536), and derives the bound in full.
+//
+// SAMPLED TILES LAST (ladder plans whose prepass scored the leading tiles of a norm-ordered index on this body: P.sample_last).  In item order the
+// sweep met the prepass' sample first: the hit-densest tiles, against tau0, the loosest threshold of the launch -- every sampled item at or above
+// tau0 (>= k of them by construction, ~111 at the headline shape) became a candidate a second time, and the counters started from zero although
+// the threshold kernel had just seen how many sampled items lie at or above each level.  Now (a) the threshold kernel PRE-CREDITS the counter
+// words with the group maxima per highest level reached (topk.hip, kth_value_wave_kernel: each is the score of a distinct sampled item,
+// bit-equal to this kernel's score of it), and (b) chunk id c covers the tiles of chunk (c + r) mod n_chunks, r = the chunks that hold the
+// sample (chunk_pos, score_fused.hip): tickets, the owner map and the repair walk keep indexing by chunk id, the sampled chunks are the last
+// tickets of a row block and meet thresholds that have risen.
+// The ONE condition this adds to 'valid whatever the timing': a sampled item must not be counted twice -- by the pre-credit and again by a
+// drain -- or a threshold could rise on fewer than k DISTINCT items.  Tickets are handed out in ascending order, so a workgroup's chunks are
+// unsampled ones first, then sampled ones: when its next chunk is the first sampled one it drains its queues once more with counting, then
+// clears WaveQueue::lad_on (a wave-uniform scalar) and every later drain -- in the tile loop and after it -- counts nothing.  What is still in
+// flight from the last unsampled tile (sub-tiles {2,3}, filtered a tile later) goes uncounted: that only delays a move.  The refresh goes on:
+// the sampled tiles are filtered against whatever the other workgroups' counts allow.
 #pragma once
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -269,6 +284,7 @@ __device__ __forceinline__ void stagger16_tile(const uint32_t (&aoff)[Frag16Addr
 }
 
 #define S16_SLICED (p.sliced)
+#define S16_CHUNK_TILE(c) (p.tile_begin + chunk_pos((int)(c), p.chunk_rot, p.n_chunks) * p.chunk_tiles)   // first tile of chunk id c (uniform)
 template <int KP, int NW = 4>
 __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p) {
 	using C = Fused16Cfg<KP, NW>;
@@ -367,9 +383,10 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 		}
 		__syncthreads();
 		const uint32_t c = lds_load_u32_uniform(ticket_slot + 8u), c1 = lds_load_u32_uniform(ticket_slot + 12u);
-		t_cur = c < (uint32_t)p.n_chunks ? p.tile_begin + (int)c * p.chunk_tiles : -1;
+		t_cur = c < (uint32_t)p.n_chunks ? S16_CHUNK_TILE(c) : -1;
 		t_cend = min(t_cur + p.chunk_tiles, p.tile_end);
-		t_next_chunk = c1 < (uint32_t)p.n_chunks ? p.tile_begin + (int)c1 * p.chunk_tiles : -1;
+		t_next_chunk = c1 < (uint32_t)p.n_chunks ? S16_CHUNK_TILE(c1) : -1;
+		if (t_cur >= 0 && t_cur < p.sample_end) w.lad_on = 0u;   // (uniform) the first ticket is a sampled chunk already: nothing this workgroup keeps is counted
 	}
 	// DMA: piece wave * PIECES + i of a tile covers LDS chunks piece * 64 + lane of the tile image (swizzle on the source address: tile_dma_offsets)
 	uint32_t dma_off[C::PIECES];
@@ -437,8 +454,8 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 		const int J = t_cur;                                                                                                    \
 		if (ticket_pending) {                                                                                                   \
 			const uint32_t c = lds_load_u32_uniform(ticket_slot);                                                               \
-			t_next_chunk = c < (uint32_t)p.n_chunks ? p.tile_begin + (int)c * p.chunk_tiles : -1;                               \
-			ticket_pending = false;                                                                                             \
+			t_next_chunk = c < (uint32_t)p.n_chunks ? S16_CHUNK_TILE(c) : -1;                                                   \
+			ticket_pending = false;                                                                                          \
 			ticket_slot ^= 4u;                                                                                                  \
 		}                                                                                                                       \
 		int nx = J + 1;                                                                                                         \
@@ -462,7 +479,9 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 			}                                                                                                                   \
 			ticket_pending = true;                                                                                              \
 			t_cend = min(nx + p.chunk_tiles, p.tile_end);                                                                       \
-		}                                                                                                                       \
+			/* (uniform, once per workgroup) the next chunk is the first SAMPLED one: count what the queue holds, then stop counting */ \
+			if (w.lad_on && nx < p.sample_end) { wq_drain<true>(w, fill); w.lad_on = 0u; }                                      \
+		}                                                                                                                \
 		__syncthreads();                                                                                                        \
 		t_cur = nx;                                                                                                             \
 	} while (0)

@@ -99,6 +99,9 @@ struct FusedParams {
 	uint32_t *chunk_ctr;              // [n row blocks], zero at launch
 	uint8_t *chunk_owner;             // [n row blocks x n_chunks]: which item split swept the chunk (the repair path's map)
 	int sliced, chunks_per_slice;     // XCD-sliced tickets: chunk_ctr is [row block][N_SLICES], slice s = chunks [s * chunks_per_slice, + chunks_per_slice)
+	// score16_kernel, ladder plans with the leading sample: chunk id c covers the tiles of chunk chunk_pos(c, chunk_rot, n_chunks) -- the sampled
+	// tiles [tile_begin, sample_end) come LAST and are not counted for the ladder (score16.hpp).  0 / 0: chunk id = position, no sampled tiles
+	int chunk_rot, sample_end;
 	// threshold ladder of score16_kernel (score16.hpp): levels [n_rb x BQ][LADDER_LEVELS], counter words [n_rb x BQ][4] (zero at launch),
 	// the cell each wave raises to the threshold it ended with (initialised to tau0 by the threshold kernel), k
 	int ladder_on; uint32_t ladder_k, ladder_mask;   // ladder_mask = period - 1 (a power of two): tiles between two fetches of a wave's counter words
@@ -106,6 +109,12 @@ struct FusedParams {
 	uint32_t *nfb;                    // workspace word 0 (zero_ws_header)
 	uint32_t zero_bytes;              // prepass kernels: workspace bytes [0, zero_bytes) to clear (a multiple of 16; 0: none) -- see zero_ws_header
 };
+
+// Where chunk id c of a ticketed sweep lies among the stage's chunks of consecutive tiles: its tiles are those of position (c + rot) mod n_chunks.
+// Chunk ids stay what tickets, the owner map and the repair walk index by; only this map from id to tiles is rotated (rot = 0: identity).
+// rot = the chunks that hold the prepass' sampled tiles (the chunk that straddles the sample's end counts as sampled): ids n_chunks - rot ..
+// n_chunks - 1, the LAST tickets of a row block, cover them.  0 <= c < n_chunks, 0 <= rot < n_chunks.
+__host__ __device__ __forceinline__ constexpr int chunk_pos(int c, int rot, int n_chunks) { return c + rot >= n_chunks ? c + rot - n_chunks : c + rot; }
 
 // Contiguous work ids per XCD (blocks b and b+8 share an XCD's L2): speed only, never correctness.
 __device__ __forceinline__ int xcd_remap(int b, int n) {
@@ -1134,10 +1143,11 @@ __global__ __launch_bounds__(256, 2) void error_kernel(const FusedParams p, cons
 // Item-tile ranges of the sweep stages (which tiles item split s swept in stage g): [begin[g] + s*tps[g], + tps[g]) below end[g].
 // stride > 1: interleaved instead (split s swept begin[g] + s, + stride, ... below end[g]).
 // chunk > 0: dynamic schedule -- stage g's tiles were swept in chunks of `chunk` tiles, chunk c of query row block rb by the item
-// split owner[g][rb * n_chunks[g] + c] (row block = q / bq).
+// split owner[g][rb * n_chunks[g] + c] (row block = q / bq); chunk id c covers the tiles of position chunk_pos(c, rot, n_chunks[g]) (rot > 0:
+// score16_kernel met the sampled tiles last; one stage).
 struct SweepStages {
 	int n, begin[3], end[3], tps[3], stride;
-	int chunk, bq, n_chunks[3];
+	int chunk, bq, n_chunks[3], rot;
 	const uint8_t *owner[3];
 };
 
@@ -1229,8 +1239,9 @@ __global__ __launch_bounds__(SEL_THREADS) void select_candidates_kernel(
 					int it = 0;
 					for (int c = 0; c < stg.n_chunks[g]; ++c) {
 						if (own[c] != (uint8_t)sp) continue;  // (uniform: every thread reads the same byte)
-						const int64_t i_beg = (int64_t)(stg.begin[g] + c * stg.chunk) * TILE_I;
-						const int64_t i_end = (int64_t)min(stg.begin[g] + (c + 1) * stg.chunk, stg.end[g]) * TILE_I;
+						const int cp = chunk_pos(c, stg.rot, stg.n_chunks[g]);
+						const int64_t i_beg = (int64_t)(stg.begin[g] + cp * stg.chunk) * TILE_I;
+						const int64_t i_end = (int64_t)min(stg.begin[g] + (cp + 1) * stg.chunk, stg.end[g]) * TILE_I;
 						for (int64_t i0 = i_beg; i0 < i_end; i0 += SEL_THREADS, ++it) {
 							const int64_t i = i0 + tid;
 							const bool in = i < i_end && i < I;
@@ -1432,6 +1443,8 @@ struct FusedPlan {
 	int chunk;  // dynamic tile schedule of the sweep stages: tiles per ticket (0: static shares)
 	bool ladder;  // score16_kernel moves its thresholds up a ladder of levels inside ONE sweep launch (score16.hpp): no stages, no refinement launches
 	int ladder_k2; // rank (in the prepass sample's group maxima) of the ladder's top level
+	int sample_last;  // ladder plans with the leading sample, prepass on the sweep's body: the chunks that hold the sampled tiles; the sweep meets them last
+	                  // and starts its counters from the prepass (score16.hpp 'SAMPLED TILES LAST').  0: item order, counters from zero
 	size_t off_lcnt, off_lvl, off_tau2;
 	size_t off_gmax, off_tval, off_tidx, off_segcnt, off_cand, off_tau, off_hard, off_ctr, off_owner, total;
 };
@@ -1658,6 +1671,13 @@ FusedPlan plan_fused(int64_t Q, int64_t I, int KP, int k, const PlanOpts &opts) 
 		if (k2 > k) k2 = k;
 		P.ladder_k2 = k2;
 	}
+	// Sampled tiles last + pre-credited counters (score16.hpp): the sample must be the leading tiles, and a group maximum must be bit-equal to the
+	// sweep's score of its item -- prepass16_kernel (groups of 16), not score_prepass_kernel's 32x32x16 chain.  The ladder runs in one stage.
+	P.sample_last = 0;
+	if (P.ladder && leading && P.group == 16 && P.chunk > 0) {
+		const int r = (P.n_st + P.chunk - 1) / P.chunk, n_chunks = (P.n_tiles + P.chunk - 1) / P.chunk;
+		if (r < n_chunks) P.sample_last = r;
+	}
 	plan_stages(P, Q, k, exp_hits, !P.ladder && (k <= WQ_K2 ? P.nseg <= WAVE : true) && P.n_tiles >= 24 * P.S, 4.0 * P.S / P.n_tiles, TILE_I);
 	plan_workspace(P, Q, k, (size_t)P.n_rb * 3 * 4 * N_SLICES, (size_t)3 * P.n_rb * (size_t)(P.n_tiles / (P.chunk > 0 ? P.chunk : P.n_tiles) + 2));
 	return P;
@@ -1745,7 +1765,8 @@ int launch_select(const FusedPlan &P, const SweepStages &stages, const uint2 *ca
 int launch_threshold(const FusedPlan &P, const float *gmax, int64_t Q, int k, unsigned char *ws, const float *&tau, int &tau_stride, hipStream_t st) {
 	if (P.n_groups <= 4096) {  // one wave per query, keys in LDS (kth_value_wave_kernel)
 		float *t = (float *)(ws + P.off_tau);
-		const int rc = P.ladder ? anncur_internal_kth_value(gmax, Q, P.n_groups, P.n_groups, k, t, 1, st, /*coarse=*/1, (float *)(ws + P.off_lvl), P.ladder_k2, (float *)(ws + P.off_tau2))
+		const int rc = P.ladder ? anncur_internal_kth_value(gmax, Q, P.n_groups, P.n_groups, k, t, 1, st, /*coarse=*/1, (float *)(ws + P.off_lvl), P.ladder_k2, (float *)(ws + P.off_tau2),
+														 P.sample_last > 0 ? (uint32_t *)(ws + P.off_lcnt) : (uint32_t *)nullptr)   // (pre-credit: score16.hpp)
 								: anncur_internal_kth_value(gmax, Q, P.n_groups, P.n_groups, k, t, 1, st, /*coarse=*/1);   // (any lower bound on the k-th best will do)
 		tau = t; tau_stride = 1;
 		return rc;
@@ -1923,7 +1944,7 @@ int launch_fused(const FusedPlan &P, const TopkCall &c) {
 	// (score16_kernel keeps contiguous ranges)
 	const int tile_step = (!P.body16 && !P.bodyq16 && !P.bodyef && P.S > 1 && chunk == 0) ? P.S : 1;
 	SweepStages stages{};
-	stages.stride = tile_step; stages.chunk = chunk; stages.bq = P.BQ;
+	stages.stride = tile_step; stages.chunk = chunk; stages.bq = P.BQ; stages.rot = chunk > 0 ? P.sample_last : 0;
 	for (int g = 0, prev = 0; g < P.n_stages; prev = P.stage_end[g], ++g) {
 		stages.n_chunks[g] = chunk > 0 ? (P.stage_end[g] - prev + chunk - 1) / chunk : 0;
 		stages.owner[g] = (const uint8_t *)(ws + P.off_owner) + (size_t)g * owner_stride;
@@ -1968,6 +1989,8 @@ int launch_fused(const FusedPlan &P, const TopkCall &c) {
 			p.chunks_per_slice = (p.n_chunks + N_SLICES - 1) / N_SLICES;
 			p.chunk_ctr = (uint32_t *)(ws + P.off_ctr) + (size_t)stg * P.n_rb * N_SLICES;
 			p.chunk_owner = (uint8_t *)(ws + P.off_owner) + (size_t)stg * owner_stride;
+			// sampled tiles last (one-stage ladder plans only; read by score16_kernel)
+			p.chunk_rot = P.sample_last; p.sample_end = P.sample_last * chunk < p.tile_end ? P.sample_last * chunk : p.tile_end;
 		}
 		// the first body that applies (`if constexpr`: a body is instantiated only for the KP / QTV it exists for)
 		auto launch = [&](auto kernel, int lds, auto... more) -> int {

@@ -566,9 +566,16 @@ __device__ __forceinline__ void kth2_coarse(const WaveSel &w, uint32_t *hist2, c
 // counted k candidates at or above one of them.  Any values would be valid there (the count makes the move valid, not the level); value-linear
 // spacing between two order statistics of the sample puts roughly geometric rank spacing on a score tail.  tau2[q] = tau (the cell the sweep's
 // waves raise to the threshold they ended with: the select's prefilter).
+// PRE-CREDIT (ladder_cnt != nullptr: the plans whose sweep meets the sampled tiles LAST, score16.hpp): the query's four counter words start from
+// the sample instead of zero -- field j = the number of group maxima whose highest reached level is j (the convention of wq_drain<true>: a
+// candidate is counted once, at the highest level it reaches), capped at k (a cumulative count >= k already moves the threshold, and the cap
+// keeps plan_fused's no-wrap bound on a field: it holds <= k when the k-th count at or above its level arrives).  A NaN maximum (key 0)
+// counts nowhere.  Each group maximum is the score of a distinct sampled item, bit-equal to the sweep's own score of it (prepass16_kernel),
+// so a pre-credited count is a count of distinct items at or above the level; the sweep must then not count the sampled tiles' items again.
+// The words are zeroed by the prepass (zero_ws_header), overwritten here, read by the sweep: stream order, no extra launch.
 __global__ __launch_bounds__(256) void kth_value_wave_kernel(const float *__restrict__ G, int64_t Q, int n, int64_t ldg, uint32_t k,
 															  float *__restrict__ out, int64_t out_stride, int n_pad, int coarse,
-															  float *__restrict__ ladder, uint32_t k2, float *__restrict__ tau2) {
+															  float *__restrict__ ladder, uint32_t k2, float *__restrict__ tau2, uint32_t *__restrict__ ladder_cnt) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char kth_smem[];
 	const uint32_t lane = (uint32_t)lane_id();
 	const int wave = threadIdx.x >> 6;
@@ -600,8 +607,36 @@ __global__ __launch_bounds__(256) void kth_value_wave_kernel(const float *__rest
 		const float t0 = f32_unsortable(kk), g = f32_unsortable(gk);
 		float d = g - t0;
 		if (!(d > 0.f) || !(d < INFINITY)) d = 0.f;   // (ties, +-inf: a flat ladder -- every level equals tau, which nothing can be counted against wrongly)
-		if (lane < (uint32_t)LADDER_LEVELS) ladder[q * LADDER_LEVELS + lane] = t0 + d * ((float)(lane + 1) * (1.0f / LADDER_LEVELS));
+		const float lvl = t0 + d * ((float)((lane & (LADDER_LEVELS - 1)) + 1) * (1.0f / LADDER_LEVELS));
+		if (lane < (uint32_t)LADDER_LEVELS) ladder[q * LADDER_LEVELS + lane] = lvl;
 		if (lane == 0 && tau2) tau2[q] = t0;
+		if (ladder_cnt) {   // (uniform) PRE-CREDIT: the sweep's counter words start from what the sample already shows (see the comment above)
+			// Counted in KEY space against the stored levels' own keys (wave-uniform scalars): one compare per key and level straight into a lane
+			// mask, popcount and add on the scalar unit -- ten waves share a SIMD here, so what this costs is its vector instructions.  At or
+			// above level j in key order implies v >= level j as the sweep compares floats (the orders differ only in -0 < +0: a count less, never
+			// one more); key 0 (a NaN maximum, a lane past n) is below every level's key, and a NaN level takes the key nothing reaches.
+			uint32_t lk[LADDER_LEVELS], ge[LADDER_LEVELS];   // ge[j]: maxima at or above level j + 1 (the levels ascend)
+#pragma unroll
+			for (int j = 0; j < LADDER_LEVELS; ++j) {
+				const float lj = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(lvl), j));
+				lk[j] = (lj == lj) ? f32_sortable(lj) : 0xffffffffu;
+				ge[j] = 0u;
+			}
+			for (uint32_t j0 = 0; j0 < (uint32_t)n; j0 += WAVE) {
+				const uint32_t j = j0 + lane, key = j < (uint32_t)n ? keys[j] : 0u;
+#pragma unroll
+				for (int i = 0; i < LADDER_LEVELS; ++i) ge[i] += (uint32_t)__builtin_popcountll(__ballot(key >= lk[i]));
+			}
+			if (lane < (uint32_t)(LADDER_LEVELS / 2)) {
+				uint32_t word = 0;
+#pragma unroll
+				for (int i = 0; i < LADDER_LEVELS / 2; ++i) {   // fields 2 i, 2 i + 1 = maxima whose HIGHEST level is 2 i + 1, 2 i + 2, each capped at k
+					const uint32_t a = ge[2 * i] - ge[2 * i + 1], b = 2 * i + 2 < LADDER_LEVELS ? ge[2 * i + 1] - ge[2 * i + 2] : ge[2 * i + 1];
+					word = lane == (uint32_t)i ? ((a < k ? a : k) | ((b < k ? b : k) << 16)) : word;
+				}
+				ladder_cnt[q * (LADDER_LEVELS / 2) + lane] = word;
+			}
+		}
 	}
 }
 
@@ -787,14 +822,15 @@ int kmax_class(int k) { return k <= 128 ? 128 : (k <= 512 ? 512 : 2048); }
 
 // internal (not part of the C ABI): tau[q] = k-th largest of G[q, :n], n <= 2048
 int anncur_internal_kth_value(const float *G, int64_t Q, int n, int64_t ldg, int k, float *out, int64_t out_stride, hipStream_t st, int coarse,
-							  float *ladder, int k2, float *tau2) {
+							  float *ladder, int k2, float *tau2, uint32_t *ladder_cnt) {
 	ANNCUR_REQUIRE(n >= 1 && n <= KTH_MAX_N && k >= 1 && k <= n, ANNCUR_E_INVALID, "kth_value: need 1 <= k <= n <= 4096");
 	const unsigned grid = (unsigned)ceil_div64(Q, 4);
 	const int n_pad = (n + 63) & ~63;
 	const int lds = 4 * (256 + n_pad + (ladder ? 256 : 0)) * 4;  // (<= 72 KB: above the 64 KB default only for n > 3584)
 	int rc;
 	if (lds > 64 * 1024 && (rc = anncur_ensure_dyn_lds((const void *)kth_value_wave_kernel, lds)) != ANNCUR_OK) return rc;
-	hipLaunchKernelGGL(kth_value_wave_kernel, dim3(grid), dim3(256), lds, st, G, Q, n, ldg, (uint32_t)k, out, out_stride, n_pad, coarse, ladder, (uint32_t)(k2 < 1 ? 1 : k2), tau2);
+	hipLaunchKernelGGL(kth_value_wave_kernel, dim3(grid), dim3(256), lds, st, G, Q, n, ldg, (uint32_t)k, out, out_stride, n_pad, coarse, ladder, (uint32_t)(k2 < 1 ? 1 : k2), tau2,
+					   ladder ? ladder_cnt : (uint32_t *)nullptr);
 	ANNCUR_LAUNCH_OK();
 	return ANNCUR_OK;
 }

@@ -22,6 +22,7 @@ ap.add_argument("--streams", type=int, default=2, choices=[1, 2])
 ap.add_argument("--Q", type=int, default=10000)
 ap.add_argument("--I", type=int, default=100000)
 ap.add_argument("--k", type=int, default=100)
+ap.add_argument("--leading", action="store_true", help="pass leading_sample=True: the plan that sweeps the sampled tiles last (score16.hpp)")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -38,14 +39,14 @@ streams = [torch.cuda.Stream(device=dev) for _ in range(args.streams)]
 streams = [streams[s % args.streams] for s in range(2)]
 wss = [ops.fused_workspace(Q, I, Kp, k, dev) for _ in range(2)]
 done = [torch.cuda.Event() for _ in range(2)]
-plan = ops.fused_plan(Q, I, Kp, k)
+plan = ops.fused_plan(Q, I, Kp, k, leading_sample=args.leading)
 assert plan["lg"] == 1 and plan["ladder"], plan
 
 
 def chain(slot):
 	with torch.cuda.stream(streams[slot]):
 		Xq = ops.gather_cols(A, anc)
-		top = ops.score_topk_fused(Xq, Etp, I, k, workspace=wss[slot])
+		top = ops.score_topk_fused(Xq, Etp, I, k, workspace=wss[slot], leading_sample=args.leading)
 		ops.overlap_counts(exact_idx, top.indices, cells)
 		done[slot].record(streams[slot])
 

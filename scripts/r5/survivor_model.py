@@ -10,6 +10,11 @@ Prints, for the first --q queries of the bench workload:
   * survivors per query of a two-stage plan (stage end 689 tiles) under each, of three- and four-stage plans, and of a threshold
     refreshed every T tiles (the limit an in-sweep refinement could reach);
   * hit rates of the 64-lane compares (4 items x 16 queries of one accumulator register) per stage.
+
+  python scripts/r5/survivor_model.py --cpu [--q 1024]
+
+needs neither a GPU nor the library: the tile-ORDER model alone (order_model) -- candidates per query of the ladder sweep in item order
+against the sampled tiles last with pre-credited counters (csrc/score16.hpp) -- on protocol-B data from torch's CPU generator.
 """
 import argparse
 import json
@@ -23,12 +28,110 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 
+def cpu_scores(cfg, Q, seed):
+	"""The score matrix of the bench workload's first Q queries, item axis in the index's norm order, without the library: protocol-B
+	matrices from torch's CPU generator (same model and seed as the bench, another random stream), the CUR index in torch (fp64
+	pseudo-inverse, bf16 operands, fp32 scores), rows ordered by descending norm in 256 buckets like ops.descending_norm_order."""
+	from anncur_amd.synth import protocol_b
+	I, Ki = cfg["I"], cfg["Ki"]
+	A_train, A_test = protocol_b(cfg["Kq"], Q, I, torch.device("cpu"), seed=seed)
+	rng = np.random.default_rng(seed)
+	anc = torch.as_tensor(np.asarray(sorted(rng.choice(I, size=Ki, replace=False))))
+	U = torch.linalg.pinv(A_train[:, anc].double())                        # [Ki, Kq]
+	Et = (U @ A_train.double()).t().float().bfloat16().float()           # [I, Ki] as the packed operand holds it
+	nrm = Et.norm(dim=1)
+	lo, hi = nrm.min(), nrm.max()
+	bucket = ((hi - nrm) / (hi - lo) * 255.999).long()
+	order = torch.sort(bucket, stable=True).indices
+	Xq = A_test[:, anc].float()
+	return (Xq @ Et[order].t()).contiguous()
+
+
+def order_model(S, k, n_st, k2, TI=32, chunk=4, abreast=13, period=16, levels=8):
+	"""Candidates per query of score16_kernel's ladder sweep, today's tile order against the sampled tiles LAST with the ladder's
+	counters pre-credited from the prepass (fused top-k: 'sweep the sampled tiles last').  S [Q, I] in sweep order.  The model: a
+	row block's `abreast` workgroups draw chunks of `chunk` tiles in ticket order and run in step, one chunk each per round; every
+	period / chunk rounds each wave moves its queries' thresholds to the highest level at or above which k candidates had been
+	counted when the previous round ended; a kept candidate is counted once, at the highest level it reaches, if that level is
+	above the threshold's.  tau0 = k-th largest group maximum, level j = tau0 + (g - tau0) j / levels, g = the group maximum of rank k2.
+	Rotated order: chunk id c covers the tiles of chunk (c + r) mod n_chunks, r = ceil(n_st / chunk); the counters start at the number
+	of group maxima per highest level reached (each field capped at k) and the sampled chunks' candidates are not counted."""
+	Q, I = S.shape
+	n_tiles = (I + TI - 1) // TI
+	n_chunks = (n_tiles + chunk - 1) // chunk
+	r = (n_st + chunk - 1) // chunk
+	# group maxima as the prepass forms them: rows with (row >> 2) & 1 == g of each sampled tile
+	samp = S[:, :n_st * TI].view(Q, n_st, 4, 2, 4).permute(0, 1, 3, 2, 4).reshape(Q, n_st * 2, 16)
+	gmax = samp.max(dim=2).values
+	gs = torch.sort(gmax, dim=1, descending=True).values
+	tau0, g = gs[:, k - 1], gs[:, k2 - 1]
+	lv = tau0[:, None] + (g - tau0)[:, None] * (torch.arange(1, levels + 1, dtype=S.dtype) / levels)[None, :]   # [Q, L] ascending
+
+	def highest(vals):   # number of levels each value reaches (0: none)
+		return (vals[:, :, None] >= lv[:, None, :]).sum(dim=2)
+
+	def run(rotated):
+		counts = torch.zeros(Q, levels + 1)            # counts[:, j]: counted with j as the highest level reached (column 0 unused)
+		if rotated:
+			hj = highest(gmax)
+			for j in range(1, levels + 1):
+				counts[:, j] = (hj == j).sum(dim=1).clamp(max=k).float()
+		jcur = torch.zeros(Q, dtype=torch.long)
+		tau = tau0.clone()
+		tot = torch.zeros(Q)
+		from_sample = torch.zeros(Q)
+		first_move = torch.full((Q,), float("nan"))
+		rounds = (n_chunks + abreast - 1) // abreast
+		seen = counts.clone()
+		for t in range(rounds):
+			if t > 0 and t % max(period // chunk, 1) == 0:
+				cum = torch.flip(torch.cumsum(torch.flip(seen[:, 1:], dims=[1]), dim=1), dims=[1])   # cum[:, j - 1] = counted at or above level j
+				ok = cum >= k
+				jn = (ok * torch.arange(1, levels + 1)[None, :]).max(dim=1).values
+				moved = jn > jcur
+				first_move = torch.where(moved & torch.isnan(first_move), torch.full_like(first_move, float(t * abreast * chunk)), first_move)
+				jcur = torch.maximum(jcur, jn)
+				tau = torch.where(jcur > 0, lv.gather(1, (jcur - 1).clamp(min=0)[:, None])[:, 0], tau0)
+			for c in range(t * abreast, min((t + 1) * abreast, n_chunks)):
+				tc = (c + r) % n_chunks if rotated else c
+				blk = S[:, tc * chunk * TI:min((tc + 1) * chunk * TI, I)]
+				keep = blk >= tau[:, None]
+				n = keep.sum(dim=1).float()
+				tot += n
+				sampled = tc < r
+				if sampled:
+					from_sample += n
+				if not (rotated and sampled):
+					hj = highest(blk) * keep
+					for j in range(1, levels + 1):
+						counts[:, j] += ((hj == j) & (jcur < j)[:, None]).sum(dim=1).float()
+			seen = counts.clone()
+		exact = torch.topk(S, k, dim=1).values[:, k - 1]
+		return {"candidates_per_query": tot.mean().item(), "of_which_from_sampled_tiles": from_sample.mean().item(),
+				"first_threshold_move_at_tile_median": float(np.nanmedian(first_move.numpy())),
+				"final_level_mean": jcur.float().mean().item(), "valid": bool((tau <= exact).all().item())}
+
+	return {"n_chunks": n_chunks, "rotation_chunks": r, "abreast": abreast, "period_tiles": period, "k2": k2,
+			"item_order": run(False), "sampled_last_precredited": run(True)}
+
+
 def main():
 	ap = argparse.ArgumentParser()
 	ap.add_argument("--q", type=int, default=2048)
 	ap.add_argument("--seed", type=int, default=0)
 	ap.add_argument("--out", default=None)
+	ap.add_argument("--cpu", action="store_true", help="the tile-order model alone (order_model), on CPU-generated protocol-B data: no GPU, no library")
 	args = ap.parse_args()
+	if args.cpu:
+		cfg = dict(Q=10000, I=100000, Ki=256, Kq=512, k=100, k_retvr=100)   # bench.py's cfg2
+		S = cpu_scores(cfg, args.q, args.seed)
+		out = {"Q": args.q, "I": cfg["I"], "k": cfg["k_retvr"], "data": "protocol B, torch CPU generator",
+			   "order_model": order_model(S, cfg["k_retvr"], 256, 16)}
+		print(json.dumps(out, indent=1))
+		if args.out:
+			with open(args.out, "w") as f:
+				json.dump(out, f, indent=1)
+		return
 	import bench
 	from anncur_amd import ops
 	from anncur_amd.cur import CURApprox
