@@ -1853,8 +1853,10 @@ void co_abort(CoScan *co, hipStream_t st) {
 
 // error_lds_kernel / evalf_kernel address the workgroup's tile of the exact matrix as a uniform 64-bit base + a 32-bit byte offset per lane,
 // (row within the row block) x pitch x 2 + chunk: the routes that use them are taken only while the last row's offset stays below 2^32
-// (bq = 256 rows: pitch < 8 421 504 elements).  ADVICE r4: unchecked, a longer pitch read the wrong rows silently.
+// (bq = 256 rows: pitch <= 8 421 504 elements).  ADVICE r4: unchecked, a longer pitch read the wrong rows silently.
 bool exact_tile_offsets_fit(int64_t lda, int bq) { return lda >= 0 && (uint64_t)(bq - 1) * (uint64_t)lda * 2u + 64u < ((uint64_t)1 << 32); }
+// wide_kernel (score_wide.hpp) addresses its query rows the same way: rows of the 256-query block x ldx x 2 + chunk in 32 bits.
+bool wide_query_offsets_fit(int64_t ldx) { return exact_tile_offsets_fit(ldx, WBN); }
 
 // anncur_eval_fused: the exact matrix and the two per-row sums the sweep stages also produce (evalf_kernel)
 struct EvalArgs { const uint16_t *A; int64_t lda; float *err_sq, *norm_sq; const uint16_t *Et_hint; };   // Et_hint: see anncur_eval_fused_ex (may be null)
@@ -2129,6 +2131,9 @@ static int score_topk_impl(const void *X, int64_t ldx, const void *Et, int64_t l
 	ANNCUR_REQUIRE(X && Et && out_val && out_idx, ANNCUR_E_INVALID, "score_topk: null pointer");
 	ANNCUR_REQUIRE(lde == Kp, ANNCUR_E_INVALID, "score_topk: Et must be packed (lde == Kp), got lde=%lld", (long long)lde);
 	ANNCUR_REQUIRE(ldx >= Kp && (ldx % 8) == 0, ANNCUR_E_INVALID, "score_topk: ldx must be >= Kp and a multiple of 8");
+	ANNCUR_REQUIRE(!P.wide || wide_query_offsets_fit(ldx), ANNCUR_E_UNSUPPORTED,
+				   "score_topk: query pitch ldx = %lld is too long for the wide kernel's 32-bit row offsets (Kp = %d > 512: 255 rows x ldx x 2 bytes must stay below 2^32, "
+				   "ldx <= 8421504): pass a compact copy of X", (long long)ldx, Kp);
 	ANNCUR_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)Et % 16) == 0, ANNCUR_E_INVALID, "score_topk: X and Et must be 16-byte aligned");
 	ANNCUR_REQUIRE(workspace && workspace_bytes >= P.total && ((uintptr_t)workspace % 256) == 0, ANNCUR_E_WORKSPACE,
 				   "score_topk: workspace of %zu bytes (256-byte aligned) required, got %zu", P.total, workspace_bytes);

@@ -76,6 +76,15 @@ def _ld(t):
 	return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
 
 
+def _wide_queries(Xp):
+	"""The fused path's query operand for the wide kernel (Kp > 512): its query rows are addressed with 32-bit offsets inside a 256-row
+	block (255 rows x pitch x 2 bytes, csrc/score_fused.hip wide_query_offsets_fit), which anncur_score_topk refuses beyond; a longer pitch
+	(a column slice of a very wide matrix) is passed as a compact copy [Q x Kp]."""
+	if Xp.shape[1] > 512 and 255 * _ld(Xp) * 2 + 64 >= 1 << 32:
+		return Xp.contiguous()
+	return Xp
+
+
 def as_index(idx, device, n=None):
 	"""Python list / numpy / tensor of indices -> int32 device tensor.  With `n` (the size of the indexed dimension) host-side
 	indices get torch's indexing semantics: negative values wrap, anything outside [-n, n) raises IndexError (the kernels' own
@@ -715,7 +724,7 @@ def score_topk_fused(Xp, Etp, I, k, return_fallbacks=False, workspace=None, lead
 	Q, Kp = Xp.shape
 	if Etp.shape[1] != Kp or not Etp.is_contiguous() or Etp.shape[0] < -(-I // 32) * 32:
 		raise ValueError("Et must be packed [ceil(I/32)*32 x Kp]")
-	Xp = _rowmajor(Xp)
+	Xp = _wide_queries(_rowmajor(Xp))
 	lib = _lib.load()
 	nbytes = lib.anncur_score_topk_workspace_bytes(Q, I, Kp, k)
 	if nbytes == 0:
@@ -811,7 +820,7 @@ def eval_topk(A, k, Xp, Etp, I, k_retvr, workspace=None, leading_sample=False, i
 	Q, Kp = Xp.shape
 	if A.shape[0] != Q or A.shape[1] != I or Etp.shape[1] != Kp or not Etp.is_contiguous() or Etp.shape[0] < -(-I // 32) * 32:
 		raise ValueError("eval_topk: A must be [Q x I], Et packed [ceil(I/32)*32 x Kp]")
-	Xp = _rowmajor(Xp)
+	Xp = _wide_queries(_rowmajor(Xp))
 	lib = _lib.load()
 	nbytes = lib.anncur_score_topk_workspace_bytes(Q, I, Kp, k_retvr)
 	if nbytes == 0:
@@ -842,6 +851,7 @@ def score_topk_fused_timed(Xp, Etp, I, k, leading_sample=False, item_ids=None, m
 	ms, from HIP events on the launch stream."""
 	_dev(Xp, Etp)
 	Q, Kp = Xp.shape
+	Xp = _wide_queries(_rowmajor(Xp))
 	lib = _lib.load()
 	nbytes = lib.anncur_score_topk_workspace_bytes(Q, I, Kp, k)
 	if nbytes == 0:

@@ -203,6 +203,9 @@ int anncur_rowwise_topk_gather(const void *A, int dtype, int64_t Q, int64_t I, i
  * X makes that query's result k pads; a NaN row of Et is never returned and costs no other item or query its place (the prepass' group
  * maxima skip NaN; a query whose sample holds fewer than k non-NaN maxima, or whose k-th maximum is -inf, sweeps without a threshold and
  * its row is rescanned by the select).
+ * ldx: the pitch of X in elements, >= Kp and a multiple of 8.  On the wide route (Kp > 512) the kernel addresses the queries of a 256-row
+ * block with 32-bit byte offsets: 255 x ldx x 2 + 64 < 2^32, i.e. ldx <= 8 421 504; a longer pitch is refused (ANNCUR_E_UNSUPPORTED, also by
+ * anncur_score_topk_ex / _timed and anncur_eval_topk; anncur_score_topk_supported does not see the pitch): pass a compact copy of X.
  * out_val float[Q x k], out_idx int32[Q x k]. */
 size_t anncur_score_topk_workspace_bytes(int64_t Q, int64_t I, int32_t Kp, int32_t k);
 int anncur_score_topk_supported(int64_t Q, int64_t I, int32_t Kp, int32_t k);   /* 1 / 0 */
