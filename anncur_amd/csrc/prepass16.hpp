@@ -28,7 +28,7 @@
 //    A lane takes the max over its eight registers of a sub-tile; ONE v_permlane32_swap per PAIR of sub-tiles then brings the partner
 //    quarter's value of sub-tile 2 i to lanes 0-31 and of sub-tile 2 i + 1 to lanes 32-63: every lane ends with one finished maximum per
 //    pair, two stores per lane and tile with all 64 lanes active.
-//  * it zeroes the workspace header (zero_ws_header, score_fused.hip) like the other prepass.
+//  * it zeroes the workspace header (zero_ws_header, sweep_common.hpp) like the other prepass.
 #pragma once
 
 template <int KP>
@@ -77,7 +77,7 @@ __device__ __forceinline__ void prepass16_tile(const uint32_t (&aoff)[Prepass16C
 #pragma unroll
 		for (int t = 0; t < 4; ++t) acc[ih][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, xb[t][ks], acc[ih][t], 0, 0, 0);
 	}
-	// The eight chains end HERE, in eight live accumulators (see mfma_chain_done in score_fused.hip).  Left alone, hipcc sank each chain's last
+	// The eight chains end HERE, in eight live accumulators (see mfma_chain_done in score32.hpp).  Left alone, hipcc sank each chain's last
 	// MFMA into the epilogue's maxima and gave it a fresh destination that overlapped a neighbour's: MFMAs three and four issue slots apart
 	// whose destinations / accumulator inputs overlap without being one in-place chain -- what scripts/check_mfma_hazards.py refuses.
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -110,23 +110,10 @@ __global__ __launch_bounds__(256, 2) void prepass16_kernel(const FusedParams p) 
 		dq = p.n_full_tiles / p.n_st; dr = p.n_full_tiles % p.n_st;
 	}
 	int j_dma = j_begin;   // the next sample tile to fetch
-	// DMA: piece wave * PIECES + i of a tile covers LDS chunks piece * 64 + lane of the tile image (swizzle on the source address, as in the sweep)
 	uint32_t dma_off[C::PIECES];
-#pragma unroll
-	for (int i = 0; i < C::PIECES; ++i) {
-		const int pch = (wave_u * C::PIECES + i) * 64 + lane;
-		const int row = pch / CPR, cs = pch % CPR;
-		dma_off[i] = (uint32_t)(row * CPR + swz<CPR>(row, cs)) * 16u;
-	}
+	tile_dma_offsets<KP>(dma_off, wave_u, lane);
 	auto fetch = [&](int buf) {
-		const unsigned char *src = reinterpret_cast<const unsigned char *>(p.Et) + (int64_t)f_tile * C::TILE_BYTES;  // (uniform)
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-		for (int i = 0; i < C::PIECES; ++i) {
-			const uint32_t m0v = lds_base + (uint32_t)(buf * C::TILE_BYTES) + (uint32_t)(wave_u * C::PIECES + i) * 1024u;
-			asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(dma_off[i]), "s"(src) : "memory", "m0");
-		}
-#endif
+		tile_dma_s<KP>(p.Et, f_tile, lds_base + (uint32_t)(buf * C::TILE_BYTES), wave_u, dma_off);
 		f_tile += dq; f_rem += dr;
 		if (f_rem >= p.n_st) { f_rem -= p.n_st; ++f_tile; }
 		++j_dma;
@@ -137,17 +124,7 @@ __global__ __launch_bounds__(256, 2) void prepass16_kernel(const FusedParams p) 
 	bf16x8 xb[4][KS32];
 	const int64_t q_wave0 = (int64_t)rb * C::BQ + wave_u * 64;
 #pragma unroll
-	for (int t = 0; t < 4; ++t) {
-		const int64_t q = q_wave0 + 16 * t + c16;
-		const bool ok = q < p.Q;
-		const u32x4 *src = reinterpret_cast<const u32x4 *>(p.X + (ok ? q : 0) * p.ldx) + g4;
-#pragma unroll
-		for (int s = 0; s < KS32; ++s) {
-			const u32x4 zero = {0u, 0u, 0u, 0u};
-			const u32x4 w = ok ? src[4 * s] : zero;
-			xb[t][s] = __builtin_bit_cast(bf16x8, w);
-		}
-	}
+	for (int t = 0; t < 4; ++t) LOAD_QUERIES16(q_wave0 + 16 * t + c16, g4, xb[t]);
 	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the queries and the first tile (see score_sweep_kernel)
 	if (j_dma < j_end) fetch(1);
 	__builtin_amdgcn_s_barrier();

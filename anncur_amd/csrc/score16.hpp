@@ -1,5 +1,5 @@
 // Sweep kernel on v_mfma_f32_16x16x32_bf16 (Kp <= 256).  Same pipeline position, operands, LDS tile image and DMA as
-// score_sweep_kernel<KP> (included by score_fused.hip); what changes is the MFMA shape and with it the lane <-> (query, item) map:
+// score_sweep_kernel<KP> (score32.hpp; both included by score_fused.hip); what changes is the MFMA shape and with it the lane <-> (query, item) map:
 //   D[16 items][16 queries] per MFMA, C/D layout col = lane & 15 = query, row = 4 (lane >> 4) + reg = item;
 //   a wave owns 64 queries as FOUR 16-query sub-tiles (the lane serves one query of each), a 32-item tile is two 16-item halves.
 // Why: under MFMA load the chip lowers its clock, and it holds a higher one on the 16x16x32 shape than on 32x32x16 at equal
@@ -41,7 +41,7 @@
 // the threshold kernel had just seen how many sampled items lie at or above each level.  Now (a) the threshold kernel PRE-CREDITS the counter
 // words with the group maxima per highest level reached (topk.hip, kth_value_wave_kernel: each is the score of a distinct sampled item,
 // bit-equal to this kernel's score of it), and (b) chunk id c covers the tiles of chunk (c + r) mod n_chunks, r = the chunks that hold the
-// sample (chunk_pos, score_fused.hip): tickets, the owner map and the repair walk keep indexing by chunk id, the sampled chunks are the last
+// sample (chunk_pos, sweep_common.hpp): tickets, the owner map and the repair walk keep indexing by chunk id, the sampled chunks are the last
 // tickets of a row block and meet thresholds that have risen.
 // The ONE condition this adds to 'valid whatever the timing': a sampled item must not be counted twice -- by the pre-credit and again by a
 // drain -- or a threshold could rise on fewer than k DISTINCT items.  Tickets are handed out in ascending order, so a workgroup's chunks are
@@ -53,10 +53,8 @@
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-template <int KP, int NW = 4>
+template <int KP>
 struct Fused16Cfg {
-	static constexpr int WAVES = NW;                 // waves per workgroup: 4 (256 queries, two workgroups per CU) or 8 (512 queries, one per CU: the tile is staged
-	                                                 // once per 512 queries -- half the DMA pieces per wave and half the L2 -> LDS traffic; round 4, see score16_kernel)
 	static constexpr int KS32 = KP / 32;             // MFMA k-steps
 	static constexpr int K = KP / 16;                // stagger steps per half = (k-step, item half) pairs
 	static constexpr int CPR = KP / 8;
@@ -64,18 +62,16 @@ struct Fused16Cfg {
 	static constexpr int QCAP = 1024;                // entries of a wave's queue
 	static constexpr int DRAIN_AT = 192;             // a step drains at its head from this fill on (three full passes; 128 / 320 measured: see DESIGN 4.1)
 	static constexpr int QUEUE_OFF = 2 * TILE_BYTES;
-	static constexpr int CNT_OFF = QUEUE_OFF + NW * QCAP * 8;       // 64 NW per-query candidate counts of this item split
-	static constexpr int TICKET_OFF = CNT_OFF + NW * 64 * 4;        // ticket words of the dynamic tile schedule (score_sweep_kernel)
-	static constexpr int PIECES = TILE_BYTES / 1024 / NW;           // DMA pieces per wave and tile
-	static_assert(PIECES >= 1, "a tile holds at least one 1 KB piece per wave");
+	static constexpr int CNT_OFF = QUEUE_OFF + 4 * QCAP * 8;        // 4 x 64 per-query candidate counts of this item split
+	static constexpr int TICKET_OFF = CNT_OFF + 4 * 64 * 4;         // ticket words of the dynamic tile schedule (tile_schedule.hpp)
 	// threshold ladder (wave-private rows, local query l of wave w at (w * 64 + l)):
 	static constexpr int LVL_OFF = TICKET_OFF + 16;                 // LADDER_LEVELS floats per query (32 bytes), DMA'd once in the prologue
-	static constexpr int LCNT_OFF = LVL_OFF + NW * 64 * 4 * LADDER_LEVELS;   // landing zone of the counter words: 16 bytes per query, refetched every LADDER_PERIOD tiles
-	static constexpr int JCUR_OFF = LCNT_OFF + NW * 64 * 16;        // the level this wave's threshold of the query has reached (0 = tau0): what the drain still counts
-	static constexpr int LDS_BYTES = JCUR_OFF + NW * 64 * 4;
-	static_assert(NW != 4 || LDS_BYTES <= 80 * 1024, "two workgroups per CU");
+	static constexpr int LCNT_OFF = LVL_OFF + 4 * 64 * 4 * LADDER_LEVELS;   // landing zone of the counter words: 16 bytes per query, refetched every LADDER_PERIOD tiles
+	static constexpr int JCUR_OFF = LCNT_OFF + 4 * 64 * 16;         // the level this wave's threshold of the query has reached (0 = tau0): what the drain still counts
+	static constexpr int LDS_BYTES = JCUR_OFF + 4 * 64 * 4;
+	static_assert(LDS_BYTES <= 80 * 1024, "two workgroups per CU");
 	static_assert(LADDER_LEVELS == 8, "two 128-bit reads per query; eight 16-bit fields in four counter words");
-	static constexpr int BQ = 64 * NW;
+	static constexpr int BQ = 256;                   // 4 waves x 64 queries
 };
 // A-fragment addresses of the tile loop: NA base registers + immediates instead of one register per stagger step.
 // Step s = (k-step s >> 1, item half s & 1) reads row 16 (s & 1) + c16, 16-byte chunk 4 (s >> 1) + g4 of the swizzled tile image (c16 = lane & 15,
@@ -83,7 +79,7 @@ struct Fused16Cfg {
 // half's 16 >> 1 = 8 falls out of the mask), so the half only adds its rows' bytes; and the XOR touches the chunk's low four bits only, so with
 // 32 chunks per row (Kp = 256) k-steps ks and ks + 4 are 16 chunks = 256 bytes apart.  Hence
 //   address(s) = base[(s >> 1) % NA] + ((s >> 1) / NA) * 256 + (s & 1) * 16 rows,   base[j] = the address of row c16, chunk 4 j + g4:
-// four registers live across the tile loop at Kp = 256 instead of sixteen.  That is what takes score16_kernel<256, 4> from 252 VGPRs (256 allocated:
+// four registers live across the tile loop at Kp = 256 instead of sixteen.  That is what takes score16_kernel<256> from 252 VGPRs (256 allocated:
 // two workgroups per CU own the whole register file) to 240, so that a small kernel of another queue fits beside it; scripts/check_kernel_resources.py
 // holds the build to it.  The identity is proven below for every lane and step.
 template <int KP>
@@ -127,6 +123,42 @@ struct WaveQueue {
 	uint32_t lad_on, lvl, jcur;
 	uint32_t *lcnt;
 };
+// The queue of wave `wave_u` in the LDS layout C (QUEUE_OFF, CNT_OFF, QCAP), its segments of item split `split` (first query q_wave0), and the
+// counts of its NQ queries (64, or 32: lanes 32..63 then hold none): where the previous stage left them (p.carry), or zero; a row past Q
+// starts at PAD_ROW_COUNT, which every store's capacity check refuses.  PUSHES: pushes of at most 64 entries the tile function makes
+// between two checks of the fill against w.limit.  The ladder fields are left to score16_kernel.
+template <typename C, int NQ, int PUSHES>
+__device__ __forceinline__ void wq_init(WaveQueue &w, uint32_t &fill, const FusedParams &p, uint32_t lds_base, int wave_u, int lane, int split, int64_t q_wave0) {
+	w.base = lds_base + (uint32_t)(C::QUEUE_OFF + wave_u * C::QCAP * 8);
+	w.limit = w.base + (uint32_t)(C::QCAP - 64 * PUSHES) * 8u;
+	w.cnt = lds_base + (uint32_t)(C::CNT_OFF + wave_u * NQ * 4);
+	w.q_stride8 = (uint32_t)p.nseg * (uint32_t)p.capg * 8u;
+	w.seg = p.cand + (q_wave0 * p.nseg + split) * (int64_t)p.capg;
+	w.capg = (uint32_t)p.capg; w.n_items = (uint32_t)p.I; w.lane = lane;
+	fill = w.base;
+	if (NQ == 64 || lane < NQ) {
+		const int64_t q = q_wave0 + lane;
+		lds_write_u32(w.cnt + (uint32_t)lane * 4u, q < p.Q ? (p.carry ? p.seg_cnt[q * p.nseg + split] : 0u) : PAD_ROW_COUNT);
+	}
+}
+// The counts back to seg_cnt, at the end of the kernel (lane l <-> local query l of the wave).
+template <int NQ>
+__device__ __forceinline__ void wq_store_counts(const WaveQueue &w, const FusedParams &p, int split, int64_t q_wave0) {
+	if (NQ == 64 || w.lane < NQ) {
+		const int64_t q = q_wave0 + w.lane;
+		uint32_t c = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+		asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(c) : "v"(w.cnt + (uint32_t)w.lane * 4u) : "memory");
+#endif
+		if (q < p.Q) p.seg_cnt[q * p.nseg + split] = c;
+	}
+}
+// An entry's item word = first item of the lane's group | (lane & 15) << 26 (item0c, per tile) + the element's code (a compile-time constant after
+// unrolling): accumulator element e of a 16x16x32 body (item half e >> 3, query sub-tile qs0 + ((e >> 2) & 1), register e & 3) -> item row within
+// the lane group | sub-tile << 30.
+__host__ __device__ __forceinline__ constexpr uint32_t wq_elem_code(int e, int qs0) {
+	return (uint32_t)(((e >> 3) * 16 + (e & 3)) | ((uint32_t)(qs0 + ((e >> 2) & 1)) << (WQ_ITEM_BITS + 4)));
+}
 
 // Drain: entry i of the queue -> lane i & 63 of pass i >> 6.  Segment address = uniform base + 32-bit byte offset (round 4; round 3 built a
 // 64-bit address per entry with two v_mad_u64_u32).  (Round 4 also tried two passes per iteration -- both entries read back to back, both
@@ -247,8 +279,7 @@ __device__ __forceinline__ void stagger16_tile(const uint32_t (&aoff)[Frag16Addr
 	// element e of a finished half: item half e >> 3, query of the pair (e >> 2) & 1, register e & 3
 #define F16_ELEM(ACC, e, QS0, TAU, ITEM0)                                                                                       \
 	filter16_one(ACC[(e) >> 3][((e) >> 2) & 1][(e) & 3],                                                                        \
-				 (uint32_t)((((e) >> 3) * 16 + ((e) & 3)) | ((uint32_t)((QS0) + (((e) >> 2) & 1)) << (WQ_ITEM_BITS + 4))),     \
-				 TAU[((e) >> 2) & 1], ITEM0, w, fill)
+				 wq_elem_code(e, QS0), TAU[((e) >> 2) & 1], ITEM0, w, fill)
 #pragma unroll
 	for (int g = 0; g < 2 * K; ++g) {
 		const int nxt = g + DIST;
@@ -283,12 +314,10 @@ __device__ __forceinline__ void stagger16_tile(const uint32_t (&aoff)[Frag16Addr
 #undef F16_READ
 }
 
-#define S16_SLICED (p.sliced)
-#define S16_CHUNK_TILE(c) (p.tile_begin + chunk_pos((int)(c), p.chunk_rot, p.n_chunks) * p.chunk_tiles)   // first tile of chunk id c (uniform)
-template <int KP, int NW = 4>
-__global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p) {
-	using C = Fused16Cfg<KP, NW>;
-	constexpr int K = C::K, KS32 = C::KS32, CPR = C::CPR;
+template <int KP>
+__global__ __launch_bounds__(256, 2) void score16_kernel(const FusedParams p) {
+	using C = Fused16Cfg<KP>;
+	constexpr int K = C::K, KS32 = C::KS32;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const int c16 = lane & 15, g4 = lane >> 4;
@@ -306,14 +335,7 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 #pragma unroll
 	for (int t = 0; t < 4; ++t) {
 		qv[t] = (int64_t)rb * C::BQ + wave * 64 + 16 * t + c16;
-		const bool ok = qv[t] < p.Q;
-		const u32x4 *src = reinterpret_cast<const u32x4 *>(p.X + (ok ? qv[t] : 0) * p.ldx) + g4;
-#pragma unroll
-		for (int s = 0; s < KS32; ++s) {
-			const u32x4 zero = {0u, 0u, 0u, 0u};
-			const u32x4 w = ok ? src[4 * s] : zero;
-			xb[t][s] = __builtin_bit_cast(bf16x8, w);
-		}
+		LOAD_QUERIES16(qv[t], g4, xb[t]);
 	}
 	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see score_sweep_kernel
 
@@ -326,23 +348,14 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 	const uint32_t lds_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(smem));
 	const int64_t q_wave0 = (int64_t)rb * C::BQ + wave_u * 64;  // (uniform) the wave's first query
 	WaveQueue w;
-	w.base = lds_base + (uint32_t)(C::QUEUE_OFF + wave_u * C::QCAP * 8);
-	w.limit = w.base + (uint32_t)(C::QCAP - 64 * (8 + 2 * (16 / K > 0 ? 16 / K : 1))) * 8u;  // see stagger16_tile: 8 + 2 EPS pushes between two checks
-	w.cnt = lds_base + (uint32_t)(C::CNT_OFF + wave_u * 256);
-	w.q_stride8 = (uint32_t)p.nseg * (uint32_t)p.capg * 8u;
-	w.seg = p.cand + (q_wave0 * p.nseg + split) * (int64_t)p.capg;
-	w.capg = (uint32_t)p.capg; w.n_items = (uint32_t)p.I; w.lane = lane;
+	uint32_t fill;
+	wq_init<C, 64, 8 + 2 * (16 / K > 0 ? 16 / K : 1)>(w, fill, p, lds_base, wave_u, lane, split, q_wave0);  // see stagger16_tile: 8 + 2 EPS pushes between two checks
 	w.lad_on = (uint32_t)p.ladder_on;
 	w.lvl = lds_base + (uint32_t)(C::LVL_OFF + wave_u * 64 * 4 * LADDER_LEVELS);
 	w.jcur = lds_base + (uint32_t)(C::JCUR_OFF + wave_u * 256);
 	w.lcnt = p.ladder_cnt + q_wave0 * 4;   // (the arrays are padded to whole row blocks: rows past Q are never counted, their thresholds are +inf)
 	const uint32_t lcnt_land = lds_base + (uint32_t)(C::LCNT_OFF + wave_u * 1024);
-	uint32_t fill = w.base;
-	{
-		const int64_t q = q_wave0 + lane;
-		lds_write_u32(w.cnt + (uint32_t)lane * 4u, q < p.Q ? (p.carry ? p.seg_cnt[q * p.nseg + split] : 0u) : PAD_ROW_COUNT);
-		lds_write_u32(w.jcur + (uint32_t)lane * 4u, 0u);
-	}
+	lds_write_u32(w.jcur + (uint32_t)lane * 4u, 0u);
 	if (p.ladder_on) {   // (uniform) the wave's 64 level rows: 2 KB = two DMA pieces, waited for with the first tile
 #if defined(__HIP_DEVICE_COMPILE__)
 		const unsigned char *lsrc = reinterpret_cast<const unsigned char *>(p.ladder + q_wave0 * LADDER_LEVELS);
@@ -356,57 +369,12 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 	uint32_t lad_tick = 0;
 	bool lad_pending = false;
 
-	// ---- tile schedule (see score_sweep_kernel): static contiguous share, or tickets of p.chunk_tiles tiles from the row block's counter
-	int t_cur = j_begin < j_end ? j_begin : -1, t_cend = j_end, t_next_chunk = -1;
-	bool ticket_pending = false;
-	const bool dyn = p.chunk_tiles > 0;
-	uint32_t ticket_slot = lds_addr(smem + C::TICKET_OFF);
-	// XCD-sliced tickets (score_fused.hip 'XCD-sliced tickets'): thread 0's slice state; unsliced = one counter per row block as in round 3
-	uint32_t *const ctr_rb = p.chunk_ctr + (S16_SLICED ? (size_t)rb * N_SLICES : (size_t)rb);
-	int slice = S16_SLICED ? xcc_id() : 0, tried = 0;
-	if (dyn) {
-		if (tid == 0) {
-			uint32_t c0, c1;
-			if (S16_SLICED) {
-				c0 = slice_resolve(atomicAdd(ctr_rb + slice, 1u), ctr_rb, p.n_chunks, p.chunks_per_slice, slice, tried);
-				c1 = c0 < (uint32_t)p.n_chunks ? slice_resolve(atomicAdd(ctr_rb + slice, 1u), ctr_rb, p.n_chunks, p.chunks_per_slice, slice, tried) : (uint32_t)p.n_chunks;
-			} else {
-				c0 = atomicAdd(ctr_rb, 2u); c1 = c0 + 1u;
-			}
-			if (p.chunk_owner) {
-				if (c0 < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c0] = (uint8_t)split;
-				if (c1 < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c1] = (uint8_t)split;
-			}
-			lds_write_u32(ticket_slot + 8u, c0);   // (the prologue's pair sits in the third and fourth ticket word)
-			lds_write_u32(ticket_slot + 12u, c1);
-			__builtin_amdgcn_s_waitcnt(0xC07F);
-		}
-		__syncthreads();
-		const uint32_t c = lds_load_u32_uniform(ticket_slot + 8u), c1 = lds_load_u32_uniform(ticket_slot + 12u);
-		t_cur = c < (uint32_t)p.n_chunks ? S16_CHUNK_TILE(c) : -1;
-		t_cend = min(t_cur + p.chunk_tiles, p.tile_end);
-		t_next_chunk = c1 < (uint32_t)p.n_chunks ? S16_CHUNK_TILE(c1) : -1;
-		if (t_cur >= 0 && t_cur < p.sample_end) w.lad_on = 0u;   // (uniform) the first ticket is a sampled chunk already: nothing this workgroup keeps is counted
-	}
-	// DMA: piece wave * PIECES + i of a tile covers LDS chunks piece * 64 + lane of the tile image (swizzle on the source address: tile_dma_offsets)
-	uint32_t dma_off[C::PIECES];
-#pragma unroll
-	for (int i = 0; i < C::PIECES; ++i) {
-		const int pch = (wave_u * C::PIECES + i) * 64 + lane;
-		const int row = pch / CPR, cs = pch % CPR;
-		dma_off[i] = (uint32_t)(row * CPR + swz<CPR>(row, cs)) * 16u;
-	}
-	auto tile_dma_w = [&](int tile, uint32_t lds_buf) {
-		const unsigned char *src = reinterpret_cast<const unsigned char *>(p.Et) + (int64_t)tile * C::TILE_BYTES;  // (uniform)
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-		for (int i = 0; i < C::PIECES; ++i) {
-			const uint32_t m0v = lds_buf + (uint32_t)(wave_u * C::PIECES + i) * 1024u;
-			asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(dma_off[i]), "s"(src) : "memory", "m0");
-		}
-#endif
-	};
-	if (t_cur >= 0) tile_dma_w(t_cur, lds_base);
+	// ---- tile schedule (tile_schedule.hpp): static contiguous share, or tickets of p.chunk_tiles tiles from the row block's counter
+	TILE_SCHEDULE_BEGIN(p.chunk_tiles > 0, p.sliced, lds_addr(smem + C::TICKET_OFF), TILE_OF_CHUNK_ROT)
+	if (dyn && t_cur >= 0 && t_cur < p.sample_end) w.lad_on = 0u;   // (uniform) the first ticket is a sampled chunk already: nothing this workgroup keeps is counted
+	uint32_t dma_off[C::TILE_BYTES / 4096];
+	tile_dma_offsets<KP>(dma_off, wave_u, lane);
+	if (t_cur >= 0) tile_dma_s<KP>(p.Et, t_cur, lds_base, wave_u, dma_off);
 	__builtin_amdgcn_s_waitcnt(0x0F70);
 	__syncthreads();
 
@@ -449,41 +417,17 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 			}                                                                                                                   \
 		}                                                                                                                       \
 	} while (0)
+	// (uniform, once per workgroup) the next chunk is the first SAMPLED one: count what the queue holds, then stop counting
+#define S16_FIRST_SAMPLED() if (w.lad_on && nx < p.sample_end) { wq_drain<true>(w, fill); w.lad_on = 0u; }
 #define STAGGER16_STEP(CUR)                                                                                                     \
 	do {                                                                                                                        \
-		const int J = t_cur;                                                                                                    \
-		if (ticket_pending) {                                                                                                   \
-			const uint32_t c = lds_load_u32_uniform(ticket_slot);                                                               \
-			t_next_chunk = c < (uint32_t)p.n_chunks ? S16_CHUNK_TILE(c) : -1;                                                   \
-			ticket_pending = false;                                                                                          \
-			ticket_slot ^= 4u;                                                                                                  \
-		}                                                                                                                       \
-		int nx = J + 1;                                                                                                         \
-		bool crossed = false;                                                                                                   \
-		if (nx >= t_cend) { nx = t_next_chunk; crossed = dyn && nx >= 0; }                                                      \
-		if (nx >= 0) tile_dma_w(nx, lds_base + ((CUR) ^ 1) * C::TILE_BYTES);                                                    \
-		uint32_t ticket = 0;                                                                                                    \
-		if (crossed && tid == 0) ticket_draw(ticket, ctr_rb + slice);                                                           \
+		TILE_STEP_HEAD(KP, CUR, TILE_OF_CHUNK_ROT, 1)                                                                           \
 		LADDER_STEP();                                                                                                          \
 		R16_DRAIN_CHECK(J);                                                                                                     \
 		const uint32_t item0 = ((uint32_t)J * TILE_I + 4 * g4) | lane_code;                                                     \
-		stagger16_tile<KP, CUR>(aoff, xb, accP, tau, tau_prev, item0, item0_prev, w, fill);                                        \
+		stagger16_tile<KP, CUR>(aoff, xb, accP, tau, tau_prev, item0, item0_prev, w, fill);                                     \
 		tau_prev[0] = tau_hi[0]; tau_prev[1] = tau_hi[1]; item0_prev = item0;                                                   \
-		ticket_wait(ticket);                                                                                                    \
-		if (crossed) {                                                                                                          \
-			if (tid == 0) {                                                                                                     \
-				if (S16_SLICED) ticket = slice_resolve(ticket, ctr_rb, p.n_chunks, p.chunks_per_slice, slice, tried);             \
-				lds_write_u32(ticket_slot, ticket);                                                                             \
-				if (p.chunk_owner && ticket < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + ticket] = (uint8_t)split; \
-				__builtin_amdgcn_s_waitcnt(0xC07F);                                                                             \
-			}                                                                                                                   \
-			ticket_pending = true;                                                                                              \
-			t_cend = min(nx + p.chunk_tiles, p.tile_end);                                                                       \
-			/* (uniform, once per workgroup) the next chunk is the first SAMPLED one: count what the queue holds, then stop counting */ \
-			if (w.lad_on && nx < p.sample_end) { wq_drain<true>(w, fill); w.lad_on = 0u; }                                      \
-		}                                                                                                                \
-		__syncthreads();                                                                                                        \
-		t_cur = nx;                                                                                                             \
+		TILE_STEP_TAIL(p.sliced, S16_FIRST_SAMPLED())                                                                           \
 	} while (0)
 	ANNCUR_PAD_HERE();
 	while (t_cur >= 0) {
@@ -492,13 +436,13 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 		STAGGER16_STEP(1);
 	}
 #undef STAGGER16_STEP
+#undef S16_FIRST_SAMPLED
 #undef LADDER_STEP
 	// drain: sub-tiles {2,3} of the last tile (16 pushes: at most the whole queue)
 	wq_drain<true>(w, fill);
 #define F16_LAST(e)                                                                                                             \
 	filter16_one(accP[(e) >> 3][((e) >> 2) & 1][(e) & 3],                                                                       \
-				 (uint32_t)((((e) >> 3) * 16 + ((e) & 3)) | ((uint32_t)(2 + (((e) >> 2) & 1)) << (WQ_ITEM_BITS + 4))),         \
-				 tau_prev[((e) >> 2) & 1], item0_prev, w, fill)
+				 wq_elem_code(e, 2), tau_prev[((e) >> 2) & 1], item0_prev, w, fill)
 	F16_LAST(0); F16_LAST(1); F16_LAST(2); F16_LAST(3); F16_LAST(4); F16_LAST(5); F16_LAST(6); F16_LAST(7);
 	F16_LAST(8); F16_LAST(9); F16_LAST(10); F16_LAST(11); F16_LAST(12); F16_LAST(13); F16_LAST(14); F16_LAST(15);
 #undef F16_LAST
@@ -524,12 +468,5 @@ __global__ __launch_bounds__(64 * NW, 2) void score16_kernel(const FusedParams p
 			}
 		}
 	}
-	{
-		const int64_t q = q_wave0 + lane;
-		uint32_t c = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-		asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(c) : "v"(w.cnt + (uint32_t)lane * 4u) : "memory");
-#endif
-		if (q < p.Q) p.seg_cnt[q * p.nseg + split] = c;
-	}
+	wq_store_counts<64>(w, p, split, q_wave0);
 }

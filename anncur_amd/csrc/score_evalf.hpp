@@ -53,13 +53,7 @@ __global__ __launch_bounds__(256, 2) void evalf_kernel(const FusedParams p, cons
 		aread[t] = lds_addr(smem) + (uint32_t)(AOFF + row * 64 + 8 * h);
 		asw[t] = (uint32_t)((row >> 2) & 3) << 4;
 		tau[t] = ok ? p.tau[qv[t] * p.tau_stride] : INFINITY;
-		const u32x4 *src = reinterpret_cast<const u32x4 *>(p.X + (ok ? qv[t] : 0) * p.ldx) + h;
-#pragma unroll
-		for (int s = 0; s < KSTEPS; ++s) {
-			const u32x4 zero = {0u, 0u, 0u, 0u};
-			const u32x4 w = ok ? src[2 * s] : zero;
-			xb[t][s] = __builtin_bit_cast(bf16x8, w);
-		}
+		LOAD_QUERIES32(qv[t], h, xb[t]);
 	}
 	// exact-tile DMA (as error_lds_kernel): piece i of this wave fills LDS chunks (wave * PA + i) * 64 + lane: row = chunk >> 2, position = chunk & 3
 	const unsigned char *abase = reinterpret_cast<const unsigned char *>(Aex + (int64_t)rb * Cfg::BQ * lda);
@@ -89,17 +83,8 @@ __global__ __launch_bounds__(256, 2) void evalf_kernel(const FusedParams p, cons
 	// candidate path: the wave's queue and its 64 per-query counts (local query 32 t + r)
 	const int64_t q_wave0 = (int64_t)rb * Cfg::BQ + wave_u * 64;
 	WaveQueue w;
-	w.base = lds_base + (uint32_t)(C::QUEUE_OFF + wave_u * C::QCAP * 8);
-	w.limit = w.base + (uint32_t)(C::QCAP - 64 * (C::CHECK_PUSHES + 1)) * 8u;
-	w.cnt = lds_base + (uint32_t)(C::CNT_OFF + wave_u * 256);
-	w.q_stride8 = (uint32_t)p.nseg * (uint32_t)p.capg * 8u;
-	w.seg = p.cand + (q_wave0 * p.nseg + split) * (int64_t)p.capg;
-	w.capg = (uint32_t)p.capg; w.n_items = (uint32_t)p.I; w.lane = lane;
-	uint32_t fill = w.base;
-	{
-		const int64_t q = q_wave0 + lane;
-		lds_write_u32(w.cnt + (uint32_t)lane * 4u, q < p.Q ? (p.carry ? p.seg_cnt[q * p.nseg + split] : 0u) : PAD_ROW_COUNT);
-	}
+	uint32_t fill;
+	wq_init<C, 64, C::CHECK_PUSHES + 1>(w, fill, p, lds_base, wave_u, lane, split, q_wave0);
 
 	const int j_begin = p.tile_begin + split * p.tiles_per_split, j_end = min(j_begin + p.tiles_per_split, p.tile_end);
 	float se[QT], sn[QT];
@@ -172,14 +157,7 @@ __global__ __launch_bounds__(256, 2) void evalf_kernel(const FusedParams p, cons
 	}
 #undef EVALF_STEP
 	wq_drain(w, fill);
-	{
-		const int64_t q = q_wave0 + lane;
-		uint32_t c = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-		asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(c) : "v"(w.cnt + (uint32_t)lane * 4u) : "memory");
-#endif
-		if (q < p.Q) p.seg_cnt[q * p.nseg + split] = c;
-	}
+	wq_store_counts<64>(w, p, split, q_wave0);
 #pragma unroll
 	for (int t = 0; t < QT; ++t)
 		if (qv[t] < p.Q) {

@@ -43,1383 +43,17 @@ using namespace anncur;
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;  // native vector: stays in VGPRs (HIP's uint4 struct did not)
-
-constexpr int TILE_I = 32;
-constexpr int CHUNK_TILES = 4;   // dynamic tile schedule: tiles per ticket
-
-template <int KP, int QTV = ((KP <= 256) ? 2 : 1)>
-struct FusedCfg {
-	static constexpr int KSTEPS = KP / 16;
-	static constexpr int QT = QTV;                  // 32-query sub-tiles per wave (default: 2 up to Kp = 256, 1 for Kp = 512)
-	static constexpr int BQ = 4 * 32 * QT;          // queries per workgroup (4 waves)
-	static constexpr int CPR = KP / 8;              // 16-byte chunks per Et row
-	static constexpr int TILE_BYTES = TILE_I * KP * 2;
-	static constexpr int PASSES = TILE_BYTES / (256 * 16);
-	static constexpr int QDEPTH = 8;                 // lane-private LDS hit queue: entries per (lane, sub-tile)
-	static constexpr int QUEUE_BYTES = QT * QDEPTH * 256 * 8;
-	static constexpr int QUEUE_OFF = (2 * TILE_BYTES + 16383) / 16384 * 16384;  // rings are 16 KiB aligned (filter_one)
-	static constexpr int TICKET_OFF = QUEUE_OFF + QUEUE_BYTES;        // two 32-bit words: the chunk tickets thread 0 hands to its workgroup (dynamic tile schedule)
-	// (Kp = 512: two 32 KiB tile buffers + 16 KiB of rings are exactly half a CU's LDS -- 16 bytes more and only ONE workgroup fits per CU
-	//  (measured: the sweep of cfg4 20 % slower); that body keeps static tile shares and no ticket words.  Tickets are drawn by the
-	//  two-sub-tile body only: the one-sub-tile body at Kp = 128 / 256 (ANNCUR_TOPK_QT1) has the words and leaves them alone)
-	static constexpr int LDS_BYTES = TICKET_OFF + (KP >= 512 ? 0 : 16);  // the prepass kernel uses only the tile part
-	static constexpr int NAOFF = KSTEPS < 8 ? KSTEPS : 8;             // fragment address registers of the staggered sweep (see stagger_tile)
-};
-
-template <int CPR>
-__host__ __device__ __forceinline__ constexpr int swz(int row, int c) {   // (constexpr: score16.hpp proves its fragment addresses with static_asserts)
-	if (CPR >= 16) return c ^ (row & 15);
-	return c ^ ((row >> 1) & 7);  // CPR == 8 (Kp = 64): 128-byte rows, two rows per 256-byte bank line
-}
-
-struct FusedParams {
-	const uint16_t *X; int64_t ldx;
-	const uint16_t *Et;
-	int64_t Q, I;
-	int n_tiles, n_full_tiles;
-	int S, tiles_per_split;           // sweep partition of the item tiles (of the current stage)
-	int tile_begin, tile_end;         // item-tile range of the current sweep stage
-	int tile_step;                    // 1: split s sweeps the contiguous range [tile_begin + s * tiles_per_split, + tiles_per_split);
-	                                  // S: split s sweeps tile_begin + s, + S, + 2 S ... (interleaved: see launch_fused)
-	int carry;                        // 1: segment counts continue from the previous stage
-	int n_st, S0, st_per_split;       // prepass: sample tiles and their partition
-	int sample_leading;               // prepass samples the leading n_st tiles instead of a strided sample (ANNCUR_TOPK_LEADING_SAMPLE)
-	float *gmax; int n_groups;        // prepass output [Q x n_groups]
-	const float *tau; int tau_stride; // threshold per query: tau[q * tau_stride]
-	uint2 *cand; uint32_t *seg_cnt; int capg;
-	int nseg;                         // candidate segments per query (2 S: 32x32x16 body, lane halves; S: 16x16x32 body)
-	int flush_tiles;                  // wave-cooperative queue flush period (tiles)
-	int n_wg;                         // grid size (for the XCD remap)
-	// dynamic tile schedule of a sweep stage (chunk_tiles > 0): the workgroups of a query row block draw chunks of `chunk_tiles` consecutive
-	// tiles from the row block's ticket counter instead of sweeping a fixed share -- see score_sweep_kernel
-	int chunk_tiles, n_chunks;
-	uint32_t *chunk_ctr;              // [n row blocks], zero at launch
-	uint8_t *chunk_owner;             // [n row blocks x n_chunks]: which item split swept the chunk (the repair path's map)
-	int sliced, chunks_per_slice;     // XCD-sliced tickets: chunk_ctr is [row block][N_SLICES], slice s = chunks [s * chunks_per_slice, + chunks_per_slice)
-	// score16_kernel, ladder plans with the leading sample: chunk id c covers the tiles of chunk chunk_pos(c, chunk_rot, n_chunks) -- the sampled
-	// tiles [tile_begin, sample_end) come LAST and are not counted for the ladder (score16.hpp).  0 / 0: chunk id = position, no sampled tiles
-	int chunk_rot, sample_end;
-	// threshold ladder of score16_kernel (score16.hpp): levels [n_rb x BQ][LADDER_LEVELS], counter words [n_rb x BQ][4] (zero at launch),
-	// the cell each wave raises to the threshold it ended with (initialised to tau0 by the threshold kernel), k
-	int ladder_on; uint32_t ladder_k, ladder_mask;   // ladder_mask = period - 1 (a power of two): tiles between two fetches of a wave's counter words
-	const float *ladder; uint32_t *ladder_cnt; float *tau_final;
-	uint32_t *nfb;                    // workspace word 0 (zero_ws_header)
-	uint32_t zero_bytes;              // prepass kernels: workspace bytes [0, zero_bytes) to clear (a multiple of 16; 0: none) -- see zero_ws_header
-};
-
-// Where chunk id c of a ticketed sweep lies among the stage's chunks of consecutive tiles: its tiles are those of position (c + rot) mod n_chunks.
-// Chunk ids stay what tickets, the owner map and the repair walk index by; only this map from id to tiles is rotated (rot = 0: identity).
-// rot = the chunks that hold the prepass' sampled tiles (the chunk that straddles the sample's end counts as sampled): ids n_chunks - rot ..
-// n_chunks - 1, the LAST tickets of a row block, cover them.  0 <= c < n_chunks, 0 <= rot < n_chunks.
-__host__ __device__ __forceinline__ constexpr int chunk_pos(int c, int rot, int n_chunks) { return c + rot >= n_chunks ? c + rot - n_chunks : c + rot; }
-
-// Contiguous work ids per XCD (blocks b and b+8 share an XCD's L2): speed only, never correctness.
-__device__ __forceinline__ int xcd_remap(int b, int n) {
-	const int q = n >> 3, r = n & 7, x = b & 7, l = b >> 3;
-	return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + l;
-}
-
-// The workspace header -- fallback and hard-list counts (bytes 0..255), the sweep stages' ticket counters, the ladder's counter words: everything
-// in front of gmax -- must be zero when the sweep starts.  It used to be a hipMemsetAsync in front of the prepass (a fill kernel and a graph node
-// of its own, every call); the prepass workgroups clear it instead, grid-strided, 16 bytes per lane (at cfg2 165 KB over 480 x 256 lanes: at most
-// one store each).  Nothing reads the range before the threshold kernel's successors: the prepass writes only gmax, the threshold kernel tau and
-// the ladder levels; the counts are first touched by the sweep and the select, all behind the prepass on the same stream.
-__device__ __forceinline__ void zero_ws_header(const FusedParams &p) {
-	typedef __attribute__((ext_vector_type(4))) unsigned int zvec;
-	zvec *const dst = reinterpret_cast<zvec *>(p.nfb);   // (the workspace is 256-byte aligned)
-	const uint32_t n = p.zero_bytes >> 4;
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = (zvec){0u, 0u, 0u, 0u};
-}
-
-
-// One 32-item tile of E^T (contiguous 64*KP bytes in HBM) -> LDS by direct-to-LDS loads (global_load_lds_dwordx4: 1 KiB per
-// wave-instruction, LDS destination = wave-uniform base + lane*16, no staging VGPRs, no ds_write).  The bank-conflict
-// swizzle is applied on the per-lane SOURCE address (LDS chunk position p holds source chunk (row, c ^ f(row)));
-// readers apply the same involution.
-template <int KP>
-__device__ __forceinline__ void tile_dma(const uint16_t *__restrict__ Et, int tile, unsigned char *buf, int wave, int lane) {
-	constexpr int CPR = FusedCfg<KP>::CPR;
-	constexpr int PER_WAVE = FusedCfg<KP>::TILE_BYTES / 1024 / 4;
-	const unsigned char *src = reinterpret_cast<const unsigned char *>(Et + (int64_t)tile * TILE_I * KP);
-#pragma unroll
-	for (int i = 0; i < PER_WAVE; ++i) {
-		const int piece = wave * PER_WAVE + i;  // wave-uniform
-		const int pch = piece * 64 + lane;
-		const int row = pch / CPR, cs = pch % CPR;
-		const int c = swz<CPR>(row, cs);
-		__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + (row * CPR + c) * 16),
-										 (__attribute__((address_space(3))) void *)(buf + piece * 1024), 16, 0, 0);
-	}
-}
-
-// (Round 3 also issued the next tile's pieces BETWEEN the tile's MFMAs instead of in a burst at the head of the step -- the phase stamps
-//  charge the burst with 384 of the 2855 cycles of a step -- : no gain, same box, alternating (0.4802 vs 0.4792 ms per sweep): the partner
-//  wave's MFMAs cover the burst already.)
-// The same DMA for the staggered sweep, hand-placed: hipcc kept the four per-lane source offsets as 64-bit pairs plus four VGPRs of LDS
-// destinations that it then moved to M0 through v_readfirstlane (12 VGPRs and ~20 vector instructions per tile and wave in a kernel
-// that sits at the 256-register limit).  Here: one 32-bit offset register per piece (computed once), the tile's base in SGPRs
-// (saddr form), M0 from a scalar.  voff[i] = byte offset of this lane's 16 bytes of piece i inside a tile (swizzle on the source).
-template <int KP>
-__device__ __forceinline__ void tile_dma_offsets(uint32_t (&voff)[FusedCfg<KP>::TILE_BYTES / 4096], int wave_u, int lane) {
-	constexpr int CPR = FusedCfg<KP>::CPR, PER_WAVE = FusedCfg<KP>::TILE_BYTES / 4096;
-#pragma unroll
-	for (int i = 0; i < PER_WAVE; ++i) {
-		const int pch = (wave_u * PER_WAVE + i) * 64 + lane;
-		const int row = pch / CPR, cs = pch % CPR;
-		voff[i] = (uint32_t)(row * CPR + swz<CPR>(row, cs)) * 16u;
-	}
-}
-template <int KP>
-__device__ __forceinline__ void tile_dma_s(const uint16_t *__restrict__ Et, int tile, uint32_t lds_buf, int wave_u,
-											const uint32_t (&voff)[FusedCfg<KP>::TILE_BYTES / 4096]) {
-	constexpr int PER_WAVE = FusedCfg<KP>::TILE_BYTES / 4096;
-	const unsigned char *src = reinterpret_cast<const unsigned char *>(Et) + (int64_t)tile * FusedCfg<KP>::TILE_BYTES;  // (uniform)
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-	for (int i = 0; i < PER_WAVE; ++i) {
-		const uint32_t m0v = lds_buf + (uint32_t)(wave_u * PER_WAVE + i) * 1024u;  // (uniform) LDS destination of the piece: M0 + lane * 16
-		asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(voff[i]), "s"(src) : "memory", "m0");
-	}
-#endif
-}
-
-// Threshold filter of one 32x32 accumulator tile: lane = query, register e = item row (e & 3) + 8 (e >> 2) (+ 4 h in item0).
-// Survivors go to the lane's private LDS queue (slot i of lane tid at lq[i * 256]: conflict-free, no atomics); the queues
-// are drained to the lane's HBM candidate segment by flush_queue() every FLUSH_TILES tiles with ONE store instruction per
-// queue slot for the whole wave (a store per hit made the kernel store-issue bound: ~20 sparse stores per tile per wave).
-// The queue's LDS accesses are inline asm: with a direct-to-LDS load in flight hipcc cannot prove that an ordinary LDS
-// store does not alias the DMA destination and puts s_waitcnt vmcnt(0) in front of EVERY push (measured: it serialised the
-// pushes behind the next tile's DMA and the flush stores).  The queue region is disjoint from the tile buffers; LDS
-// executes one wave's instructions in order, so a slot written by ds_write_b64 is seen by the later ds_read_b64.
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-	return (uint32_t)(size_t)(__attribute__((address_space(3))) const char *)p;
-}
-__device__ __forceinline__ void lds_write_u64(uint32_t addr, uint32_t lo, uint32_t hi) {
-#if defined(__HIP_DEVICE_COMPILE__)
-	const unsigned long long d = ((unsigned long long)hi << 32) | lo;
-	asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(d) : "memory");
-#endif
-}
-__device__ __forceinline__ uint2 lds_load_u64(uint32_t addr) {
-	unsigned long long d = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(d) : "v"(addr) : "memory");
-#endif
-	return make_uint2((uint32_t)d, (uint32_t)(d >> 32));
-}
-
-__device__ __forceinline__ void lds_write_u32(uint32_t addr, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
-#endif
-}
-__device__ __forceinline__ uint32_t lds_load_u32_uniform(uint32_t addr) {  // every lane reads the same word; returned as a scalar
-	uint32_t d = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(d) : "v"(addr) : "memory");
-#endif
-	return (uint32_t)__builtin_amdgcn_readfirstlane((int)d);
-}
-// Ticket draw of the dynamic tile schedule: a RETURNING atomic add whose result is not waited for where it is issued.  (Written with
-// atomicAdd() hipcc's atomic optimiser turns the one-lane add into a wave-aggregated one and waits vmcnt(0) for it on the spot --
-// directly behind the next tile's DMA.)  The destination is in flight after the asm statement, like the fragment ring's registers:
-// ticket_wait() is the wait, and takes the register as an in/out operand so that nothing that reads it can be scheduled above it.
-__device__ __forceinline__ void ticket_draw(uint32_t &ticket, uint32_t *ctr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-	const uint32_t one = 1u;
-	asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(ticket) : "v"(ctr), "v"(one) : "memory");
-#endif
-}
-__device__ __forceinline__ void ticket_wait(uint32_t &ticket) {
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm volatile("s_waitcnt vmcnt(0)" : "+v"(ticket)::"memory");
-#endif
-}
-// Two dwords from two separate VGPRs (no 64-bit register pair has to be assembled in the hit path).
-__device__ __forceinline__ void lds_write_2x32(uint32_t addr, uint32_t lo, uint32_t hi) {
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" ::"v"(addr), "v"(lo), "v"(hi) : "memory");
-#endif
-}
-
-// One accumulator element of the filter (element index e is a compile-time constant after unrolling).  The hit path is kept
-// to the bare minimum (slot address, item id, one LDS store, count): the sweep is vector-issue bound, every instruction here is
-// paid ~0.3 times per MFMA.  The queue is a ring of D slots; what does not belong in it is sorted out at flush time
-// (items past I of the matrix' last, partial tile; a count above D = the ring wrapped = overflow).
-// Measured on cfg2 (MI355X): branch version 0.58 ms per sweep, predicated version 0.655 ms independent of the hit rate (its
-// compare -> exec -> store chain sits in front of the wave's next MFMA) -> the branch version is the one in use.
-// (plan_stages picks the variant per sweep stage from the expected hit rate: predicated above ~0.5 taken branches per compare)
-template <int D, bool FILTER_PREDICATED = false>
-__device__ __forceinline__ void filter_one(float v, int e, float tau, uint32_t item0, uint32_t lq, uint32_t &qcnt) {
-	static_assert((D & (D - 1)) == 0, "queue depth must be a power of two");
-	// qcnt is kept pre-shifted (slot stride 2048 B); lq has bits 11..13 clear (16 KiB-aligned ring), so OR == ADD
-	if (FILTER_PREDICATED) {
-		// Branch-free: no wave-level "any hit" test, the push runs under the compare's lane mask (a block this short gets no
-		// s_cbranch_execz from hipcc).  With lane = query the wave-level branch is taken by ~35 % of the compares at k = 100 and by nearly
-		// all of them at k >= 500, and a taken branch (out and back) costs more than these always-issued instructions.
-		// The compare is compiler-generated, so hipcc keeps its own MFMA -> VALU distance; the first version of this variant did the
-		// compare INSIDE an inline-asm string, 0-6 wait states behind the MFMA whose result it read, and lost a survivor now and then
-		// (found by the randomised parity run; scripts/check_mfma_hazards.py flags exactly that string).
-		if (v >= tau) {
-			lds_write_2x32((qcnt & (uint32_t)((D - 1) << 11)) | lq, __float_as_uint(v), item0 + (uint32_t)((e & 3) + 8 * (e >> 2)));
-			qcnt += 2048u;
-		}
-	} else if (__builtin_expect(__ballot(v >= tau) != 0ull, 0)) {
-		if (v >= tau) {
-			lds_write_2x32((qcnt & (uint32_t)((D - 1) << 11)) | lq, __float_as_uint(v), item0 + (uint32_t)((e & 3) + 8 * (e >> 2)));
-			qcnt += 2048u;
-		}
-	}
-}
-
-// Dense splits (norm-ordered rows: the leading splits of the first stage; their rings are drained every tile): a lane that finds
-// more than D survivors in ONE tile has wrapped its ring.  At k = 500 the prepass threshold lets about half of the leading tiles'
-// elements through and a handful of queries did this in every call -- each one a whole-split repair by the workgroup-level kernel
-// (0.26 ms per call for five queries).  The tile's accumulator is still in registers when its filter ends, and the lane's ring is
-// 8 slots x 8 bytes = 16 floats: the lane overwrites its ring with the RAW accumulator (mark_wrapped_raw) and flags its count; the
-// next flush filters those 16 scores itself.  Exact, no repair, and nothing but the accumulator, the ring address and the count is
-// live where it happens (a direct store to the segment from inside the tile function cost the headline kernel its registers: the
-// query operand went to scratch).  The ring must hold nothing but that tile's survivors, i.e. the split drains every tile.
-constexpr uint32_t RING_RAW = 0x80000000u;
-template <int D>
-__device__ __forceinline__ void mark_wrapped_raw(const f32x16 &acc, uint32_t lq, uint32_t &qcnt) {
-	static_assert(D == 8, "the raw tile (16 floats) fills the ring exactly");
-	const bool wrapped = (qcnt >> 11) > (uint32_t)D && qcnt < RING_RAW;
-	if (__builtin_expect(__ballot(wrapped) != 0ull, 0)) {
-		if (wrapped) {
-#pragma unroll
-			for (int i = 0; i < D; ++i) lds_write_2x32(lq + (uint32_t)i * 2048u, __float_as_uint(acc[2 * i]), __float_as_uint(acc[2 * i + 1]));
-			qcnt = RING_RAW;
-		}
-	}
-}
-
-// Drain the lane's ring to its HBM candidate segment: one store instruction per queue slot for the whole wave.
-// raw_item0: first item (+ 4 h) of the tile a RING_RAW ring holds (dense splits only).
-template <int D, bool BATCH = true>
-__device__ __forceinline__ void flush_queue(uint32_t lq, uint32_t &qcnt, uint2 *__restrict__ seg, uint32_t &ncand, uint32_t capg,
-											 uint32_t n_items, float tau, uint32_t raw_item0) {
-	if (__builtin_expect(__ballot(qcnt >= RING_RAW) != 0ull, 0)) {
-		if (qcnt >= RING_RAW) {
-			for (int i = 0; i < D; ++i) {
-				const uint2 w = lds_load_u64(lq + (uint32_t)i * 2048u);
-#pragma unroll
-				for (int half = 0; half < 2; ++half) {
-					const int e = 2 * i + half;
-					const float v = __uint_as_float(half ? w.y : w.x);
-					const uint32_t item = raw_item0 + (uint32_t)((e & 3) + 8 * (e >> 2));
-					if (v >= tau && item < n_items) {
-						if (ncand < capg) seg[ncand] = make_uint2(__float_as_uint(v), item);
-						ncand++;
-					}
-				}
-			}
-			qcnt = 0;
-		}
-	}
-	uint32_t n = qcnt >> 11;  // (the filter keeps the count pre-shifted by the slot stride)
-	if (__builtin_expect(__ballot(n > (uint32_t)D) != 0ull, 0)) {
-		// ring wrapped between two flushes of a multi-tile window (p ~ 1e-9 per window): poison the segment count -> the select
-		// kernel recomputes this query exactly
-		if (n > (uint32_t)D) { ncand = 0x80000000u; n = D; }
-	}
-	if constexpr (!BATCH) {  // (the three-workgroups-per-CU body of ANNCUR_TOPK_QT1 has no sixteen registers to spare: slot by slot)
-		for (uint32_t i = 0; __ballot(i < n) != 0ull; ++i) {
-			if (i < n) {
-				const uint2 w = lds_load_u64(lq + i * 2048u);
-				if (w.y < n_items) {
-					if (ncand < capg) seg[ncand] = w;
-					ncand++;
-				}
-			}
-		}
-		qcnt = 0;
-		return;
-	}
-	// Read the occupied slots back to back, wait ONCE, then store.  (Round 2 read, waited and stored slot by slot: a drain with three
-	// entries in its fullest ring paid three exposed LDS round trips -- at k = 500, where every tile is drained and the fullest of the 64
-	// rings holds 3-4 entries, that was more wave time than the tile's MFMAs.)  Slot i is read if ANY lane holds more than i entries.
-	unsigned long long e[D];
-	int n_read = 0;  // (uniform) slots read = the fullest ring's count
-#pragma unroll
-	for (int i = 0; i < D; ++i) {
-		if (__ballot((uint32_t)i < n) == 0ull) break;
-#if defined(__HIP_DEVICE_COMPILE__)
-		asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(e[i]) : "v"(lq), "n"(i * 2048));
-#endif
-		n_read = i + 1;
-	}
-#if defined(__HIP_DEVICE_COMPILE__)
-	static_assert(D == 8, "the wait below names eight slots");
-	// (the destinations are in flight until here; naming them as in/out operands keeps every use below the wait)
-	asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]), "+v"(e[4]), "+v"(e[5]), "+v"(e[6]), "+v"(e[7])::"memory");
-#endif
-#pragma unroll
-	for (int i = 0; i < D; ++i) {
-		if (i >= n_read) break;
-		if ((uint32_t)i < n) {
-			const uint2 w = make_uint2((uint32_t)e[i], (uint32_t)(e[i] >> 32));
-			if (w.y < n_items) {               // (items past I exist only in the matrix' last, partial tile)
-				if (ncand < capg) seg[ncand] = w;
-				ncand++;                        // (a poisoned count stays > capg)
-			}
-		}
-	}
-	qcnt = 0;
-}
-
-// ---- A-fragment ring of the staggered sweep.  The LDS reads are inline asm with explicit, COUNTED s_waitcnt lgkmcnt(n):
-// hipcc's own wait insertion fell back to lgkmcnt(0) in this loop (every fourth MFMA waited for a fragment requested one
-// MFMA earlier).  The compiler does not see that the destination is still in flight after the asm statement; the wait
-// statement takes the fragment as an in/out operand so that its consumer cannot be scheduled above the wait.
-template <int OFF>
-__device__ __forceinline__ void lds_read_frag(u32x4 &dst, uint32_t addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-#endif
-}
-__device__ __forceinline__ void lds_read_frag_at(u32x4 &dst, uint32_t addr, int off) {  // `off` folds to an immediate after unrolling
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off));
-#endif
-}
-__device__ __forceinline__ void lds_wait_frag(u32x4 &frag, int pending) {  // `pending` folds to a constant after unrolling
-#if defined(__HIP_DEVICE_COMPILE__)
-	if (pending >= 3) asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(frag));
-	else if (pending == 2) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(frag));
-	else if (pending == 1) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(frag));
-	else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(frag));
-#endif
-}
-
-// One 32-item tile of the staggered sweep (Kp <= 256): the wave's two 32-query sub-tiles run half a tile apart.  While the
-// MFMA chain of one sub-tile executes on the matrix pipe, the threshold filter of the OTHER sub-tile's finished accumulator
-// is issued element by element in the MFMA shadow (one accumulator register per k-step at Kp = 256):
-//   steps 0..K-1   : accA (sub-tile 0 of this tile)  ||  filter of acc1 = sub-tile 1 of the PREVIOUS tile
-//   steps K..2K-1  : acc1 (sub-tile 1 of this tile)  ||  filter of accA
-// The A fragments (same K fragments for both halves) stream through one ring of AR registers, AR-1 steps ahead, without a
-// break between the halves.  CUR = tile buffer parity (compile-time: an immediate offset of the LDS reads).
-// Fragment address of k-step s (tile buffer 0): row r, chunk (2 s + h) ^ f(r).  For Kp = 256 (32 chunks per row, f(r) = r & 15) the XOR
-// leaves bit 4 of the chunk alone, so k-steps s and s + 8 are 256 bytes apart: eight address registers plus an immediate offset serve
-// the sixteen k-steps (the eight registers this saves are what the dynamic tile schedule's ticket lives in).
-template <int KP, int CUR, bool PRED>
-__device__ __forceinline__ void stagger_tile(const uint32_t (&aoff)[FusedCfg<KP>::NAOFF], const bf16x8 (&xb)[2][FusedCfg<KP>::KSTEPS],
-											  f32x16 &acc1, float tau0, float tau1_prev, uint32_t item0, uint32_t item0_prev,
-											  uint32_t lq0, uint32_t lq1, uint32_t &q0, uint32_t &q1, bool dense) {
-	using Cfg = FusedCfg<KP>;
-	constexpr int K = Cfg::KSTEPS, AR = 5, DIST = 3, OFF = CUR * Cfg::TILE_BYTES;  // ring slots / prefetch distance in k-steps
-	constexpr int NA = Cfg::NAOFF;
-	constexpr int EPS = 16 / K > 0 ? 16 / K : 1;  // filter elements per k-step (Kp = 64: 4, 128: 2, 256: 1)
-	static_assert(K <= 16 && 2 * K >= DIST && AR >= DIST + 2, "staggered path: 2..16 k-steps; a slot is rewritten two MFMAs after its use");
-	static_assert(K <= NA || Cfg::CPR == 32, "k-steps beyond the address registers: + 256 bytes needs 32 chunks per row");
-	u32x4 ring[AR];
-#define ST_READ(slot, s) lds_read_frag_at(ring[slot], aoff[((s) % K) % NA], OFF + (((s) % K) / NA) * 256)
-#pragma unroll
-	for (int i = 0; i < DIST; ++i) ST_READ(i, i);
-	f32x16 accA = {0}, accB = {0};
-#pragma unroll
-	for (int g = 0; g < 2 * K; ++g) {
-		// the slot the new fragment lands in was consumed by the MFMA of step g-2: the asynchronous LDS return can never meet
-		// an MFMA that is still reading its operands
-		const int nxt = g + DIST;
-		if (nxt < 2 * K) ST_READ(nxt % AR, nxt);
-#if defined(__HIP_DEVICE_COMPILE__)
-		// (keeps the register allocator from handing that read the registers of the fragment the PREVIOUS MFMA was given)
-		if (g >= 1) asm volatile("" ::"v"(ring[(g - 1) % AR]));
-#endif
-		const int after = 2 * K - 1 - g;
-		lds_wait_frag(ring[g % AR], after < DIST ? after : DIST);
-		const bf16x8 a = __builtin_bit_cast(bf16x8, ring[g % AR]);
-		if (g < K) {
-			accA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[0][g], accA, 0, 0, 0);
-#pragma unroll
-			for (int e = (g == 1 ? 0 : g) * EPS; e < (g == 0 ? 0 : g + 1) * EPS; ++e)
-				filter_one<Cfg::QDEPTH, PRED>(acc1[e], e, tau1_prev, item0_prev, lq1, q1);
-			if (g == K - 1 && dense) mark_wrapped_raw<Cfg::QDEPTH>(acc1, lq1, q1);  // (uniform) the previous tile's sub-tile 1 is filtered
-		} else {
-			// no filter in the first step of the half: accA's last MFMA is still in the pipe (and the predicated filter is
-			// inline asm, invisible to the compiler's MFMA -> VALU hazard handling); step 1 takes two groups instead
-			accB = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[1][g - K], accB, 0, 0, 0);
-#pragma unroll
-			for (int e = (g - K == 1 ? 0 : g - K) * EPS; e < (g == K ? 0 : g - K + 1) * EPS; ++e)
-				filter_one<Cfg::QDEPTH, PRED>(accA[e], e, tau0, item0, lq0, q0);
-		}
-	}
-#undef ST_READ
-	if (dense) mark_wrapped_raw<Cfg::QDEPTH>(accA, lq0, q0);  // (uniform) this tile's sub-tile 0 is filtered
-	acc1 = accB;
-}
-
-// Wait states between the last MFMA of an accumulate chain and the first instruction that is not the next MFMA of that chain
-// (hipcc's own floor for the 8-pass 32x32x16 bf16 MFMA is 11).  hipcc pads this itself -- except where it does not: in the first
-// version of stagger1_tile (one accumulator, `accP = acc` at the end of the tile) it copied the accumulator EIGHT states after the
-// last MFMA on one path of the unrolled loop (MFMA, s_cbranch, v_lshl_or, s_nop 5, v_mov ...), so three registers were copied without
-// the last k-step's contribution whenever instruction fetch did not happen to supply the missing states -- which depended on where
-// the loop sat in memory: the shipped build passed every parity test, a diagnostic build with two more instructions in the prologue
-// returned wrong scores for item rows 24-26 / 28-30 of every second tile.  scripts/check_mfma_hazards.py (run by the CPU tests on the
-// built library) now walks every kernel for this; the statement below makes the distance explicit where a chain ends.
-__device__ __forceinline__ void mfma_chain_done(f32x16 &acc) {
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm volatile("s_nop 7\n\ts_nop 2" : "+v"(acc));
-#endif
-}
-
-// One 32-query sub-tile per wave (Kp = 512, where the query operand alone takes 128 VGPRs; Kp = 128 / 256 under ANNCUR_TOPK_QT1, for
-// three workgroups per CU): the same idea across TILES -- while the
-// 32-MFMA chain of tile j executes into `acc`, the filter of tile j-1's accumulator `accP` is issued in its shadow, one element every
-// second k-step; A fragments through the counted-wait register ring as in stagger_tile.  The caller alternates two accumulators
-// (no copy: see mfma_chain_done).  Fragment address of k-step s:
-// row * CPR * 16 + ((2 s + h) ^ (r & 15)) * 16 = aoff8[s & 7] + (s >> 3) * 256 (the XOR only touches the chunk's low four bits),
-// so eight address registers serve the 32 k-steps.
-template <int KP, int CUR>
-__device__ __forceinline__ void stagger1_tile(const uint32_t (&aoff8)[8], const bf16x8 (&xb)[FusedCfg<KP, 1>::KSTEPS], f32x16 &acc,
-											   const f32x16 &accP, float tau, uint32_t item0_prev, uint32_t lq, uint32_t &qcnt, bool dense) {
-	using Cfg = FusedCfg<KP, 1>;
-	constexpr int K = Cfg::KSTEPS, AR = 5, DIST = 3, OFF = CUR * Cfg::TILE_BYTES;
-	static_assert((K == 32 || K == 16 || K == 8) && Cfg::CPR >= 16, "Kp = 128, 256 or 512");
-	u32x4 ring[AR];
-#define S1_READ(slot, s) lds_read_frag_at(ring[slot], aoff8[(s) & 7], OFF + ((s) >> 3) * 256)
-	S1_READ(0, 0); S1_READ(1, 1); S1_READ(2, 2);
-#pragma unroll
-	for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-	for (int g = 0; g < K; ++g) {
-		const int nxt = g + DIST;
-		if (nxt < K) S1_READ(nxt % AR, nxt);
-#if defined(__HIP_DEVICE_COMPILE__)
-		if (g >= 1) asm volatile("" ::"v"(ring[(g - 1) % AR]));
-#endif
-		const int after = K - 1 - g;
-		lds_wait_frag(ring[g % AR], after < DIST ? after : DIST);
-		acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ring[g % AR]), xb[g], acc, 0, 0, 0);
-		if constexpr (K == 32) {  // one element every second k-step
-			if (g & 1) filter_one<Cfg::QDEPTH>(accP[g >> 1], g >> 1, tau, item0_prev, lq, qcnt);
-		} else {                  // 16 / K elements per k-step
-#pragma unroll
-			for (int e = g * (16 / K); e < (g + 1) * (16 / K); ++e) filter_one<Cfg::QDEPTH>(accP[e], e, tau, item0_prev, lq, qcnt);
-		}
-	}
-#undef S1_READ
-	mfma_chain_done(acc);
-	if (dense) mark_wrapped_raw<Cfg::QDEPTH>(accP, lq, qcnt);  // (uniform) the previous tile is filtered
-}
-
-// Prepass on the 32x32x16 body: group maxima (GROUP = 16 or 4 items per maximum) of S_hat over the sample tiles, plain double-buffered
-// tile loop with compiler-placed fragment reads.  (The plans that sweep with score16_kernel run prepass16_kernel instead.)
-template <int KP, int GROUP, int QTV = FusedCfg<KP>::QT>
-__global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_prepass_kernel(const FusedParams p) {
-	using Cfg = FusedCfg<KP, QTV>;
-	constexpr int KSTEPS = Cfg::KSTEPS, QT = Cfg::QT, CPR = Cfg::CPR;
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int r = lane & 31, h = lane >> 5;
-	zero_ws_header(p);
-	const int wid = xcd_remap(blockIdx.x, p.n_wg);
-	const int n_rb = (int)((p.Q + Cfg::BQ - 1) / Cfg::BQ);
-	const int split = wid / n_rb, rb = wid - split * n_rb;
-
-	// ---- this wave's queries: B operand fragments, resident for the whole kernel
-	bf16x8 xb[QT][KSTEPS];
-	int64_t qv[QT];
-#pragma unroll
-	for (int t = 0; t < QT; ++t) {
-		qv[t] = (int64_t)rb * Cfg::BQ + wave * 32 * QT + 32 * t + r;
-		const bool ok = qv[t] < p.Q;
-		const u32x4 *src = reinterpret_cast<const u32x4 *>(p.X + (ok ? qv[t] : 0) * p.ldx) + h;
-#pragma unroll
-		for (int s = 0; s < KSTEPS; ++s) {
-			const u32x4 zero = {0u, 0u, 0u, 0u};
-			const u32x4 w = ok ? src[2 * s] : zero;
-			xb[t][s] = __builtin_bit_cast(bf16x8, w);
-		}
-	}
-	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the fragments are complete before the tile loop (see score_sweep_kernel)
-
-	// ---- work range: sample tiles [j_begin, j_end) of p.n_st; sample tile j is the matrix' tile tile_of(j)
-	const int j_begin = split * p.st_per_split, j_end = min(j_begin + p.st_per_split, p.n_st);
-#define tile_of(j) (!p.sample_leading ? (int)(((int64_t)(j) * p.n_full_tiles) / p.n_st) : (j))
-	if (j_begin < j_end) tile_dma<KP>(p.Et, tile_of(j_begin), smem, wave, lane);
-	__builtin_amdgcn_s_waitcnt(0x0F70);
-	__syncthreads();
-	ANNCUR_PAD_HERE();
-
-	int cur = 0;
-	for (int j = j_begin; j < j_end; ++j, cur ^= 1) {
-		if (j + 1 < j_end) tile_dma<KP>(p.Et, tile_of(j + 1), smem + (cur ^ 1) * Cfg::TILE_BYTES, wave, lane);
-		f32x16 acc[QT];
-#pragma unroll
-		for (int t = 0; t < QT; ++t)
-#pragma unroll
-			for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-		const u32x4 *tb = reinterpret_cast<const u32x4 *>(smem + cur * Cfg::TILE_BYTES);
-#pragma unroll
-		for (int s = 0; s < KSTEPS; ++s) {
-			const u32x4 w = tb[r * CPR + swz<CPR>(r, 2 * s + h)];
-			const bf16x8 a = __builtin_bit_cast(bf16x8, w);
-#pragma unroll
-			for (int t = 0; t < QT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[t][s], acc[t], 0, 0, 0);
-		}
-
-		// ---- epilogue.  C/D layout: query = lane & 31 (col), item row = (e & 3) + 8 * (e >> 2) + 4 * h
-#pragma unroll
-		for (int t = 0; t < QT; ++t) {
-			if (GROUP == 16) {
-				float m = acc[t][0];
-#pragma unroll
-				for (int e = 1; e < 16; ++e) m = fmaxf(m, acc[t][e]);
-				if (qv[t] < p.Q) p.gmax[qv[t] * p.n_groups + (int64_t)j * 2 + h] = m;
-			} else {
-				float4 m;
-				m.x = fmaxf(fmaxf(acc[t][0], acc[t][1]), fmaxf(acc[t][2], acc[t][3]));
-				m.y = fmaxf(fmaxf(acc[t][4], acc[t][5]), fmaxf(acc[t][6], acc[t][7]));
-				m.z = fmaxf(fmaxf(acc[t][8], acc[t][9]), fmaxf(acc[t][10], acc[t][11]));
-				m.w = fmaxf(fmaxf(acc[t][12], acc[t][13]), fmaxf(acc[t][14], acc[t][15]));
-				if (qv[t] < p.Q) *reinterpret_cast<float4 *>(p.gmax + qv[t] * p.n_groups + ((int64_t)j * 2 + h) * 4) = m;
-			}
-		}
-		__builtin_amdgcn_s_waitcnt(0x0F70);  // the DMA of tile j+1 has landed
-		__syncthreads();
-	}
-#undef tile_of
-}
-
-// Filter sweep on the 32x32x16 body with per-lane rings (PRED: branch-free filter, for stages in which most compares find a survivor in
-// some lane -- large k).  Three tile functions on one schedule: two sub-tiles per wave staggered inside a tile (stagger_tile, Kp <= 256),
-// one sub-tile per wave pipelined across tiles (stagger1_tile: Kp = 512, and Kp = 128 / 256 under ANNCUR_TOPK_QT1).
-template <int KP, bool PRED = false, int QTV = FusedCfg<KP>::QT>
-__global__ __launch_bounds__(256, (QTV == 1 && KP <= 256) ? 3 : 2) void score_sweep_kernel(const FusedParams p) {
-	using Cfg = FusedCfg<KP, QTV>;
-	constexpr int KSTEPS = Cfg::KSTEPS, QT = Cfg::QT, CPR = Cfg::CPR;
-	static_assert(QT == 2 || (KP >= 128 && !PRED), "one sub-tile per wave: stagger1_tile (Kp >= 128, branch filter)");
-	constexpr bool FLUSH_BATCH = !(QTV == 1 && KP <= 256);   // (see flush_queue)
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int r = lane & 31, h = lane >> 5;
-	const int wid = xcd_remap(blockIdx.x, p.n_wg);
-	const int n_rb = (int)((p.Q + Cfg::BQ - 1) / Cfg::BQ);
-	const int split = wid / n_rb, rb = wid - split * n_rb;
-
-	// ---- this wave's queries: B operand fragments, resident for the whole kernel
-	bf16x8 xb[QT][KSTEPS];
-	int64_t qv[QT];
-#pragma unroll
-	for (int t = 0; t < QT; ++t) {
-		qv[t] = (int64_t)rb * Cfg::BQ + wave * 32 * QT + 32 * t + r;
-		const bool ok = qv[t] < p.Q;
-		const u32x4 *src = reinterpret_cast<const u32x4 *>(p.X + (ok ? qv[t] : 0) * p.ldx) + h;
-#pragma unroll
-		for (int s = 0; s < KSTEPS; ++s) {
-			const u32x4 zero = {0u, 0u, 0u, 0u};
-			const u32x4 w = ok ? src[2 * s] : zero;
-			xb[t][s] = __builtin_bit_cast(bf16x8, w);
-		}
-	}
-
-	// The X fragments must be complete before the tile loop: otherwise hipcc's wait-count merge at the loop header
-	// (fragment loads possibly pending + an unknown number of candidate stores on the back edge) makes it wait
-	// vmcnt(0) in front of the first MFMA of EVERY tile, i.e. right after issuing the next tile's loads.
-	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
-
-	// ---- work range
-	int j_begin, j_end;  // tile iterations
-	if (p.tile_step > 1) { j_begin = p.tile_begin + split; j_end = p.tile_end; }                                        // interleaved splits
-	else { j_begin = p.tile_begin + split * p.tiles_per_split; j_end = min(j_begin + p.tiles_per_split, p.tile_end); }  // contiguous shares
-	const int ts = p.tile_step > 1 ? p.tile_step : 1;  // distance between two tiles of this workgroup
-	// Norm-ordered rows: the survivors crowd into the leading tiles (several times the average density: about half of their elements
-	// pass the prepass threshold at large k).  The first quarter of the first stage's tiles is swept with the rings drained every
-	// tile (a ring then holds nothing but one tile: see mark_wrapped_raw); a step drains when the tile before it was such a tile.
-	const int dense_end = (p.sample_leading && !p.carry) ? p.tile_begin + (p.tile_end - p.tile_begin + 3) / 4 : p.tile_begin;
-	const bool every_tile = p.flush_tiles <= 1;  // (uniform) the whole stage drains every tile (large k): every ring holds one tile
-
-	float tau[QT];
-	uint32_t ncand[QT], qcnt[QT];
-#pragma unroll
-	for (int t = 0; t < QT; ++t) {
-		tau[t] = qv[t] < p.Q ? p.tau[qv[t] * p.tau_stride] : INFINITY;
-		ncand[t] = qv[t] < p.Q ? (p.carry ? p.seg_cnt[qv[t] * p.nseg + h * p.S + split] : 0u) : PAD_ROW_COUNT;
-		qcnt[t] = 0;
-	}
-	// candidate segment of (query, lane half, split); sub-tile t adds a wave-uniform stride
-	uint2 *seg0 = p.cand + (qv[0] * p.nseg + h * p.S + split) * (int64_t)p.capg;
-	const int64_t seg_dt = (int64_t)32 * p.nseg * p.capg;
-	const uint32_t lq0 = lds_addr(smem + Cfg::QUEUE_OFF) + (uint32_t)tid * 8u;  // slot i of sub-tile t at byte lq0 + (t*QDEPTH + i)*2048
-	static_assert(Cfg::QUEUE_OFF % (Cfg::QDEPTH * 2048) == 0 && Cfg::QDEPTH * 2048 == 16384, "ring must be 16 KiB aligned");
-	if ((lds_addr(smem) & 0x3fffu) != 0u) __builtin_trap();  // filter_one() ORs the slot offset into the address
-
-	uint32_t last_item0 = 0;  // first item (+ 4 h) of the last tile filtered: what a raw ring holds at the final flush
-	// ---- tile schedule (wave-uniform scalars).  Static: tiles j_begin, j_begin + ts, ... below j_end.
-	// Dynamic (p.chunk_tiles > 0; the two-sub-tile body only): the workgroups of a query row block draw chunks of p.chunk_tiles consecutive
-	// tiles from the row block's ticket counter, one chunk ahead of the one they sweep.  Why: the 480 workgroups of a cfg2 stage do not run at one speed --
-	// in-kernel stamps (round 2) put the ends of their tile loops between 193 and 271 us (median 234) for equal shares: 32 CUs hold one
-	// workgroup instead of two, the others differ by XCD / CU placement -- and a launch lasts as long as its slowest workgroup.  With tickets
-	// a fast workgroup simply sweeps more chunks.  Any assignment is exact: a workgroup's survivors go to its own segments whatever tiles
-	// it swept; the repair path finds a split's tiles in p.chunk_owner.  Thread 0 draws a ticket when the workgroup starts the chunk
-	// BEFORE the one the ticket is for (atomic in flight during a whole tile), hands it over through LDS at that tile's barrier.
-	// The one-sub-tile bodies run the same step with `dyn` constant-false: static shares, the ticket statements compile out (Kp = 512
-	// has no LDS left for the ticket words, see FusedCfg).
-	int t_cur = j_begin < j_end ? j_begin : -1, t_cend = j_end, t_step = ts, t_next_chunk = -1, t_prev = -1;
-	bool ticket_pending = false;
-	const bool dyn = QT == 2 && p.chunk_tiles > 0;
-	// two LDS words used in turn: a ticket is published at the end of one step and read at the head of the next, and nothing but program
-	// order separates that read from the NEXT publication (possible one step later when a chunk is a single tile)
-	uint32_t ticket_slot = lds_addr(smem + Cfg::TICKET_OFF);
-	if (dyn) {
-		if (tid == 0) {
-			const uint32_t c = atomicAdd(p.chunk_ctr + rb, 2u);   // the first chunk and the look-ahead
-			if (p.chunk_owner) {
-				if (c < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c] = (uint8_t)split;
-				if (c + 1 < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c + 1] = (uint8_t)split;
-			}
-			lds_write_u32(ticket_slot, c);
-			__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the word is in LDS before this wave reaches the barrier
-		}
-		__syncthreads();
-		const uint32_t c = lds_load_u32_uniform(ticket_slot);
-		t_step = 1;
-		t_cur = c < (uint32_t)p.n_chunks ? p.tile_begin + (int)c * p.chunk_tiles : -1;
-		t_cend = min(t_cur + p.chunk_tiles, p.tile_end);
-		t_next_chunk = c + 1 < (uint32_t)p.n_chunks ? p.tile_begin + (int)(c + 1) * p.chunk_tiles : -1;
-	}
-	const int wave_u = __builtin_amdgcn_readfirstlane(wave);             // (the compiler does not know tid >> 6 is wave-uniform)
-	const uint32_t lds_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(smem));
-	uint32_t dma_off[Cfg::TILE_BYTES / 4096];
-	tile_dma_offsets<KP>(dma_off, wave_u, lane);
-	if (t_cur >= 0) tile_dma_s<KP>(p.Et, t_cur, lds_base, wave_u, dma_off);
-	__builtin_amdgcn_s_waitcnt(0x0F70);
-	__syncthreads();
-	ANNCUR_PAD_HERE();
-
-	// One step of the schedule, around a body's drain and tile function: (head) read the pending ticket, pick the next tile, issue its DMA into
-	// the other buffer, draw the ticket of the chunk after the one that tile opens; (tail) wait, publish the ticket, barrier, advance.
-#define SWEEP_STEP_HEAD(CUR)                                                                                                    \
-		const int J = t_cur;                                                                                                    \
-		if (ticket_pending) {  /* (uniform) the ticket thread 0 drew during the previous step */                                \
-			const uint32_t c = lds_load_u32_uniform(ticket_slot);                                                               \
-			t_next_chunk = c < (uint32_t)p.n_chunks ? p.tile_begin + (int)c * p.chunk_tiles : -1;                               \
-			ticket_pending = false;                                                                                             \
-			ticket_slot ^= 4u;  /* (TICKET_OFF is 16-byte aligned) */                                                           \
-		}                                                                                                                       \
-		int nx = J + t_step;                                                                                                    \
-		bool crossed = false;  /* (uniform) the next tile opens the look-ahead chunk: draw the ticket of the one after it */    \
-		if (nx >= t_cend) { nx = t_next_chunk; crossed = dyn && nx >= 0; }                                                      \
-		if (nx >= 0) tile_dma_s<KP>(p.Et, nx, lds_base + ((CUR) ^ 1) * Cfg::TILE_BYTES, wave_u, dma_off);                       \
-		uint32_t ticket = 0;                                                                                                    \
-		if (crossed && tid == 0) ticket_draw(ticket, p.chunk_ctr + rb);  /* in flight until ticket_wait() below */
-#define SWEEP_STEP_TAIL()                                                                                                       \
-		ticket_wait(ticket);  /* vmcnt(0): the DMA of the next tile, the queue stores issued with it and the ticket have landed */ \
-		if (crossed) {                                                                                                          \
-			if (tid == 0) {                                                                                                     \
-				lds_write_u32(ticket_slot, ticket);                                                                             \
-				if (p.chunk_owner && ticket < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + ticket] = (uint8_t)split; \
-				__builtin_amdgcn_s_waitcnt(0xC07F);                                                                             \
-			}                                                                                                                   \
-			ticket_pending = true;                                                                                              \
-			t_cend = min(nx + p.chunk_tiles, p.tile_end);                                                                       \
-		}                                                                                                                       \
-		__syncthreads();                                                                                                        \
-		t_prev = J; t_cur = nx;
-
-	if constexpr (QT == 2) {
-		// ---- staggered sweep (stagger_tile): tile loop unrolled by two so that the LDS buffer parity is a compile-time offset
-		f32x16 acc1;
-#pragma unroll
-		for (int e = 0; e < 16; ++e) acc1[e] = 0.f;
-		float tau1_prev = INFINITY;  // no previous tile yet: the filter of acc1 never fires
-		uint32_t item0_prev = 0, item0_pp = 0;   // first item (+ 4 h) of the previous tile and of the one before it
-		const uint32_t lq1 = lq0 + Cfg::QDEPTH * 2048;
-		uint32_t aoff[Cfg::NAOFF];   // LDS byte address of this lane's A fragment of k-step s (< NAOFF) in tile buffer 0
-#pragma unroll
-		for (int s = 0; s < Cfg::NAOFF; ++s) aoff[s] = lds_addr(smem) + (uint32_t)(r * CPR + swz<CPR>(r, 2 * s + h)) * 16u;
-		int flush_in2 = p.flush_tiles;
-		// stagger_tile() counts LDS reads with lgkmcnt(n): no scalar load of the prologue may still be in flight (scalar loads share
-		// the counter and return out of order)
-		__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0) only
-// (Round 3 tried draining by occupancy as well -- a ballot "some lane's ring holds >= 3 / >= 4 entries" per step, beside or instead of the
-//  planned window: both cost 4 % of the sweep at cfg2, same box, alternating -- the check itself, not the drains.  The planned window stays.)
-#define STAGGER_STEP(CUR)                                                                                                       \
-		do {                                                                                                                    \
-			SWEEP_STEP_HEAD(CUR)                                                                                                \
-			if (t_prev < dense_end || --flush_in2 <= 0) {                                                                       \
-				flush_in2 = p.flush_tiles;                                                                                      \
-				/* (a raw ring holds one tile: sub-tile 0 of the previous tile, sub-tile 1 of the one before) */                \
-				flush_queue<Cfg::QDEPTH>(lq0, qcnt[0], seg0, ncand[0], (uint32_t)p.capg, (uint32_t)p.I, tau[0], item0_prev);    \
-				flush_queue<Cfg::QDEPTH>(lq1, qcnt[1], seg0 + seg_dt, ncand[1], (uint32_t)p.capg, (uint32_t)p.I, tau[1], item0_pp); \
-			}                                                                                                                   \
-			const uint32_t item0 = (uint32_t)J * TILE_I + 4 * h;                                                                \
-			stagger_tile<KP, CUR, PRED>(aoff, xb, acc1, tau[0], tau1_prev, item0, item0_prev, lq0, lq1, qcnt[0], qcnt[1], J < dense_end || every_tile); \
-			tau1_prev = tau[1]; item0_pp = item0_prev; item0_prev = item0;                                                      \
-			SWEEP_STEP_TAIL()                                                                                                   \
-		} while (0)
-		while (t_cur >= 0) {
-			STAGGER_STEP(0);
-			if (t_cur < 0) break;
-			STAGGER_STEP(1);
-		}
-#undef STAGGER_STEP
-		flush_queue<Cfg::QDEPTH>(lq1, qcnt[1], seg0 + seg_dt, ncand[1], (uint32_t)p.capg, (uint32_t)p.I, tau[1], item0_pp);  // keep one tile's hits per queue window
-#pragma unroll
-		for (int e = 0; e < 16; ++e)  // drain: sub-tile 1 of the last tile
-			filter_one<Cfg::QDEPTH>(acc1[e], e, tau1_prev, item0_prev, lq1, qcnt[1]);
-		mark_wrapped_raw<Cfg::QDEPTH>(acc1, lq1, qcnt[1]);  // (its ring was just drained: exact in every split)
-		last_item0 = item0_prev;
-	} else {
-		// ---- one sub-tile per wave, software-pipelined across tiles (stagger1_tile): tile loop unrolled by two (buffer parity =
-		// immediate offset); even steps accumulate into accA and filter accB, odd steps the other way round
-		f32x16 accA, accB;
-#pragma unroll
-		for (int e = 0; e < 16; ++e) { accA[e] = 0.f; accB[e] = 0.f; }
-		float tau_prev = INFINITY;   // no previous tile yet: the filter never fires
-		uint32_t item0_prev = 0, item0_pp = 0;
-		uint32_t aoff8[8];
-#pragma unroll
-		for (int s = 0; s < 8; ++s) aoff8[s] = lds_addr(smem) + (uint32_t)(r * CPR + ((2 * s + h) ^ (r & 15))) * 16u;
-		int flush_in2 = p.flush_tiles;
-		__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): stagger1_tile() counts LDS reads
-#define STAGGER1_STEP(CUR, ACC, ACCP)                                                                                           \
-		do {                                                                                                                    \
-			SWEEP_STEP_HEAD(CUR)                                                                                                \
-			if (t_prev < dense_end || --flush_in2 <= 0) {                                                                       \
-				flush_in2 = p.flush_tiles;                                                                                      \
-				/* (a raw ring holds the tile before the previous one, filtered during the previous step) */                    \
-				flush_queue<Cfg::QDEPTH, FLUSH_BATCH>(lq0, qcnt[0], seg0, ncand[0], (uint32_t)p.capg, (uint32_t)p.I, tau[0], item0_pp); \
-			}                                                                                                                   \
-			stagger1_tile<KP, CUR>(aoff8, xb[0], ACC, ACCP, tau_prev, item0_prev, lq0, qcnt[0], J < dense_end || every_tile);   \
-			tau_prev = tau[0]; item0_pp = item0_prev; item0_prev = (uint32_t)J * TILE_I + 4 * h;                                \
-			SWEEP_STEP_TAIL()                                                                                                   \
-		} while (0)
-		bool last_in_a = false;  // (uniform) which accumulator holds the last tile
-		while (t_cur >= 0) {
-			STAGGER1_STEP(0, accA, accB);
-			last_in_a = true;
-			if (t_cur < 0) break;
-			STAGGER1_STEP(1, accB, accA);
-			last_in_a = false;
-		}
-#undef STAGGER1_STEP
-		flush_queue<Cfg::QDEPTH, FLUSH_BATCH>(lq0, qcnt[0], seg0, ncand[0], (uint32_t)p.capg, (uint32_t)p.I, tau[0], item0_pp);
-		if (last_in_a) {  // drain: the last tile (its ring was just drained: the raw path is exact in every split)
-#pragma unroll
-			for (int e = 0; e < 16; ++e) filter_one<Cfg::QDEPTH>(accA[e], e, tau_prev, item0_prev, lq0, qcnt[0]);
-			mark_wrapped_raw<Cfg::QDEPTH>(accA, lq0, qcnt[0]);
-		} else {
-#pragma unroll
-			for (int e = 0; e < 16; ++e) filter_one<Cfg::QDEPTH>(accB[e], e, tau_prev, item0_prev, lq0, qcnt[0]);
-			mark_wrapped_raw<Cfg::QDEPTH>(accB, lq0, qcnt[0]);
-		}
-		last_item0 = item0_prev;
-	}
-#undef SWEEP_STEP_HEAD
-#undef SWEEP_STEP_TAIL
-
-#pragma unroll
-	for (int t = 0; t < QT; ++t) {
-		flush_queue<Cfg::QDEPTH, FLUSH_BATCH>(lq0 + t * Cfg::QDEPTH * 2048, qcnt[t], seg0 + t * seg_dt, ncand[t], (uint32_t)p.capg, (uint32_t)p.I, tau[t], last_item0);
-		if (qv[t] < p.Q) p.seg_cnt[qv[t] * p.nseg + h * p.S + split] = ncand[t];
-	}
-}
-
-// ---- XCD-sliced tickets (round 4).  Under round 3's schedule a row block's workgroups -- spread over all eight XCDs -- drew their chunks from
-// ONE counter per row block: every XCD ended up reading every tile of the stage (cfg4's per-GPU shape: 8.9 GB of L2 -> fabric traffic per
-// launch against 1.0 GB of E^T, 5.3 TB/s).  Now the stage's chunks are cut into eight contiguous slices, one per XCD, each with its own
-// counter per row block: a workgroup draws from the slice of the XCD it RUNS on (s_getreg XCC_ID -- measured, never assumed: placement is
-// speed only) and, once that slice is exhausted, steals from the following ones.  All the row blocks resident on an XCD walk the same
-// slice at about the same pace, so a tile crosses the fabric about once (plus the steals) instead of once per XCD, and the schedule
-// stays dynamic: a slow workgroup still draws fewer chunks, a fast one moves on to help its neighbours.  Any assignment is exact
-// (chunk ids stay global: the owner map and the repair path are unchanged).
-constexpr int N_SLICES = 8;
-__device__ __forceinline__ uint32_t slice_len(int n_chunks, int cps, int s) {
-	const int b = s * cps, e = min(b + cps, n_chunks);
-	return e > b ? (uint32_t)(e - b) : 0u;
-}
-// local ticket `l` drawn from slice `slice` of this row block -> global chunk id, or n_chunks when every slice is exhausted.  Steals (a
-// blocking atomic per exhausted slice, at most seven per workgroup and stage) happen here; `tried` = slices this workgroup found exhausted.
-__device__ __forceinline__ uint32_t slice_resolve(uint32_t l, uint32_t *ctr_rb, int n_chunks, int cps, int &slice, int &tried) {
-	for (;;) {
-		if (l < slice_len(n_chunks, cps, slice)) return (uint32_t)(slice * cps) + l;
-		if (++tried >= N_SLICES) return (uint32_t)n_chunks;
-		slice = (slice + 1) & (N_SLICES - 1);
-		l = atomicAdd(ctr_rb + slice, 1u);
-	}
-}
-__device__ __forceinline__ int xcc_id() {
-	uint32_t x = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
-#endif
-	return (int)(x & (N_SLICES - 1));
-}
-
-#include "score16.hpp"
-#include "prepass16.hpp"
-#include "score_q16.hpp"
-
-// ------------------------------------------------------------------ a11: approximation error on the same MFMA loop
-// err_sq[q] += sum_i (S_hat[q,i] - A[q,i])^2, norm_sq[q] += sum_i A[q,i]^2 over this workgroup's item tiles; S_hat is never
-// written.  Same orientation as the sweep: lane = query, so both sums are lane-local accumulators and the exact matrix is read
-// as 4 consecutive items (8 or 16 bytes) per lane and accumulator register group; the next tile's exact values are in flight
-// during the MFMAs.  One atomicAdd pair per lane at the end (2 S per query).
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4n __attribute__((ext_vector_type(4)));
-template <typename TA> struct ExactQuad;  // four consecutive items of one row of the exact matrix (native vectors: asm operands)
-template <> struct ExactQuad<uint16_t> {
-	u32x2 w;
-	__device__ __forceinline__ void load(const uint16_t *p) { w = *reinterpret_cast<const u32x2 *>(p); }
-	__device__ __forceinline__ float get(int c) const {
-		const uint32_t x = (c & 2) ? w[1] : w[0];
-		return __uint_as_float((c & 1) ? (x & 0xffff0000u) : (x << 16));
-	}
-};
-template <> struct ExactQuad<float> {
-	f32x4n w;
-	__device__ __forceinline__ void load(const float *p) { w = *reinterpret_cast<const f32x4n *>(p); }
-	__device__ __forceinline__ float get(int c) const { return w[c]; }
-};
-
-// The tile's MFMA chains with the A fragments through the counted-wait register ring of the sweep (three k-steps ahead, inline-asm
-// ds_read_b128, s_waitcnt lgkmcnt(n)): round 2's loop read two k-steps, waited lgkmcnt(0), issued four MFMAs -- eight exposed LDS
-// round trips per tile (0.24 of peak).  Both sub-tiles share the fragment.
-template <int KP, int CUR>
-__device__ __forceinline__ void error_mfma_tile(const uint32_t (&aoff)[FusedCfg<KP>::NAOFF], const bf16x8 (&xb)[FusedCfg<KP>::QT][FusedCfg<KP>::KSTEPS],
-												 f32x16 (&acc)[FusedCfg<KP>::QT]) {
-	using Cfg = FusedCfg<KP>;
-	constexpr int K = Cfg::KSTEPS, NA = Cfg::NAOFF, QT = Cfg::QT, AR = 5, DIST = 3, OFF = CUR * Cfg::TILE_BYTES;
-	static_assert(K > DIST, "at least four k-steps");
-	u32x4 ring[AR];
-#define ER_READ(slot, s) lds_read_frag_at(ring[slot], aoff[(s) % NA], OFF + ((s) / NA) * 256)
-	ER_READ(0, 0); ER_READ(1, 1); ER_READ(2, 2);
-#pragma unroll
-	for (int t = 0; t < QT; ++t)
-#pragma unroll
-		for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-#pragma unroll
-	for (int g = 0; g < K; ++g) {
-		const int nxt = g + DIST;
-		if (nxt < K) ER_READ(nxt % AR, nxt);
-#if defined(__HIP_DEVICE_COMPILE__)
-		if (g >= 1) asm volatile("" ::"v"(ring[(g - 1) % AR]));
-#endif
-		const int after = K - 1 - g;
-		lds_wait_frag(ring[g % AR], after < DIST ? after : DIST);
-		const bf16x8 a = __builtin_bit_cast(bf16x8, ring[g % AR]);
-#pragma unroll
-		for (int t = 0; t < QT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[t][g], acc[t], 0, 0, 0);
-	}
-#undef ER_READ
-#pragma unroll
-	for (int t = 0; t < QT; ++t) mfma_chain_done(acc[t]);
-}
-
-// a11 with the exact matrix staged through LDS (bf16 exact matrix, rows 16-byte aligned: lda % 8 == 0).  error_kernel reads the exact
-// values with the accumulator's orientation -- lane = query -- i.e. 8 bytes per lane from 32 different rows per load instruction:
-// 2.5 TB/s of exact matrix at cfg2 size whatever the MFMA loop does (round 3: the counted-wait fragment ring alone moved 0.84 -> 0.81 ms;
-// the time did not scale with Kp either: 0.60 ms at Kp = 128).  Here the workgroup's tile of the exact matrix -- BQ rows x 64 bytes --
-// comes in by the same direct-to-LDS loads as the item tile (16 bytes per lane, four lanes per row, 16 rows per instruction), double
-// buffered, one tile ahead; the lanes then read their four quads per sub-tile from LDS (ds_read_b64; the 16-byte chunk of a row is
-// XOR-swizzled with (row >> 2) & 3 on the DMA's source address: two-way bank conflicts instead of eight-way).
-// (The sweep's stagger with the sums in the filter's place -- sub-tile 0's sums in the shadow of sub-tile 1's chain -- was built and
-//  measured: no gain at Kp = 128 (0.460 vs 0.459 ms), 16 spilled registers at Kp = 256 (1.28 ms): the epilogue is not what bounds it.)
-template <int KP>
-__global__ __launch_bounds__(256, 2) void error_lds_kernel(const FusedParams p, const uint16_t *__restrict__ Aex, int64_t lda,
-															float *__restrict__ err_sq, float *__restrict__ norm_sq) {
-	using Cfg = FusedCfg<KP>;
-	constexpr int KSTEPS = Cfg::KSTEPS, QT = Cfg::QT, CPR = Cfg::CPR;
-	constexpr int ATILE = Cfg::BQ * 64, PA = ATILE / 4096, AOFF = 2 * Cfg::TILE_BYTES;   // exact tile bytes, DMA pieces per wave, LDS offset
-	constexpr int NAB = 2;                                                               // exact-tile buffers
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int r = lane & 31, h = lane >> 5;
-	const int wid = xcd_remap(blockIdx.x, p.n_wg);
-	const int n_rb = (int)((p.Q + Cfg::BQ - 1) / Cfg::BQ);
-	const int split = wid / n_rb, rb = wid - split * n_rb;
-
-	bf16x8 xb[QT][KSTEPS];
-	int64_t qv[QT];
-	uint32_t aread[QT], asw[QT];  // LDS byte address of this lane's row of the exact tile (+ 8 h) in buffer 0; the row's chunk swizzle
-#pragma unroll
-	for (int t = 0; t < QT; ++t) {
-		const int row = wave * 32 * QT + 32 * t + r;
-		qv[t] = (int64_t)rb * Cfg::BQ + row;
-		const bool ok = qv[t] < p.Q;
-		aread[t] = lds_addr(smem) + (uint32_t)(AOFF + row * 64 + 8 * h);
-		asw[t] = (uint32_t)((row >> 2) & 3) << 4;
-		const u32x4 *src = reinterpret_cast<const u32x4 *>(p.X + (ok ? qv[t] : 0) * p.ldx) + h;
-#pragma unroll
-		for (int s = 0; s < KSTEPS; ++s) {
-			const u32x4 zero = {0u, 0u, 0u, 0u};
-			const u32x4 w = ok ? src[2 * s] : zero;
-			xb[t][s] = __builtin_bit_cast(bf16x8, w);
-		}
-	}
-	// exact-tile DMA: piece i of this wave fills LDS chunks (wave * PA + i) * 64 + lane: row = chunk >> 2, position = chunk & 3.
-	// Source = the row block's base (uniform) + a 32-bit byte offset per piece (a row block spans at most 256 rows of the matrix)
-	const unsigned char *abase = reinterpret_cast<const unsigned char *>(Aex + (int64_t)rb * Cfg::BQ * lda);
-	uint32_t asrc[PA];
-#pragma unroll
-	for (int i = 0; i < PA; ++i) {
-		const int ch = (wave * PA + i) * 64 + lane, row = ch >> 2, pos = ch & 3;
-		const int64_t last = p.Q - 1 - (int64_t)rb * Cfg::BQ;   // rows past Q re-read the last row (their sums are dropped)
-		asrc[i] = (uint32_t)(((int64_t)row < last ? (int64_t)row : last) * lda * 2) + (uint32_t)(16 * (pos ^ ((row >> 2) & 3)));
-	}
-	// both DMAs hand-placed (tile_dma_s: SGPR base, 32-bit lane offsets, M0 from a scalar): the builtin's per-lane 64-bit pointers and LDS
-	// destinations cost ~24 VGPRs, which the staggered Kp = 256 body does not have
-	const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-	const uint32_t lds_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(smem));
-	uint32_t dma_off[Cfg::TILE_BYTES / 4096];
-	tile_dma_offsets<KP>(dma_off, wave_u, lane);
-	const int j_begin = split * p.tiles_per_split, j_end = min(j_begin + p.tiles_per_split, p.n_tiles);
-	auto adma = [&](int j, int buf) {
-		const unsigned char *src = abase + (int64_t)j * (TILE_I * 2);   // (uniform)
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-		for (int i = 0; i < PA; ++i) {
-			const uint32_t m0v = lds_base + (uint32_t)(AOFF + buf * ATILE + (wave_u * PA + i) * 1024);
-			asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(asrc[i]), "s"(src) : "memory", "m0");
-		}
-#endif
-	};
-	__builtin_amdgcn_s_waitcnt(0x0F70);  // see score_sweep_kernel: keeps vmcnt(0) out of the tile loop
-
-	float se[QT], sn[QT];
-#pragma unroll
-	for (int t = 0; t < QT; ++t) { se[t] = 0.f; sn[t] = 0.f; }
-	// (Round 4, measured and dropped: the exact tiles TWO tiles ahead in a ring of three buffers -- 80 KB at Kp = 256 -- with a counted vmcnt at
-	//  the end of a step.  Same box, warm, round robin: 0.617 vs 0.615 ms at Kp = 256, 0.472 vs 0.468 at Kp = 128.  What the exact tile costs is
-	//  not its round trip: with every DMA re-reading one L2-hot tile the kernel takes 0.505 / 0.32 ms, with the same bytes from contiguous
-	//  memory 0.59 / 0.40 -- profiles/r04_error_kernel_modes.txt.)
-	if (j_begin < j_end) {
-		tile_dma_s<KP>(p.Et, j_begin, lds_base, wave_u, dma_off);
-		adma(j_begin, 0);
-	}
-	__builtin_amdgcn_s_waitcnt(0x0F70);
-	__syncthreads();
-	uint32_t aoff[Cfg::NAOFF];
-#pragma unroll
-	for (int s = 0; s < Cfg::NAOFF; ++s) aoff[s] = lds_addr(smem) + (uint32_t)(r * CPR + swz<CPR>(r, 2 * s + h)) * 16u;
-	__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): error_mfma_tile() counts LDS reads
-	static_assert(PA <= 15, "vmcnt immediate");
-#define ERRL_STEP(ECUR, ACUR, J)                                                                                                \
-	do {                                                                                                                        \
-		if ((J) + 1 < j_end) tile_dma_s<KP>(p.Et, (J) + 1, lds_base + ((ECUR) ^ 1) * Cfg::TILE_BYTES, wave_u, dma_off);         \
-		const bool ahead = (J) + NAB - 1 < j_end;   /* (uniform) */                                                             \
-		if (ahead) adma((J) + NAB - 1, ((ACUR) + NAB - 1) % NAB);                                                               \
-		f32x16 acc[QT];                                                                                                         \
-		error_mfma_tile<KP, ECUR>(aoff, xb, acc);                                                                               \
-		ExactQuad<uint16_t> ex[QT][4];  /* items 32 j + 8 g + 4 h + {0..3}, g = 0..3, of the lane's query */                   \
-		_Pragma("unroll") for (int t = 0; t < QT; ++t)                                                                          \
-			_Pragma("unroll") for (int g = 0; g < 4; ++g)                                                                       \
-				asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(ex[t][g].w) : "v"(aread[t] + (((uint32_t)g << 4) ^ asw[t])), "n"((ACUR) * ATILE)); \
-		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                      \
-		_Pragma("unroll") for (int t = 0; t < QT; ++t)                                                                          \
-			_Pragma("unroll") for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(ex[t][g].w));                                  \
-		_Pragma("unroll") for (int t = 0; t < QT; ++t)                                                                          \
-			_Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                                    \
-				const float x = ex[t][e >> 2].get(e & 3);                                                                       \
-				const float d = acc[t][e] - x;                                                                                  \
-				se[t] = fmaf(d, d, se[t]);                                                                                      \
-				sn[t] = fmaf(x, x, sn[t]);                                                                                      \
-			}                                                                                                                   \
-		/* this wave's parts of the next item tile and of the next exact tile have landed; the barrier orders LDS only */        \
-		if (NAB == 3 && ahead) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA) : "memory");                                        \
-		else __builtin_amdgcn_s_waitcnt(0x0F70);                                                                                \
-		asm volatile("" ::: "memory");                                                                                          \
-		__builtin_amdgcn_s_barrier();                                                                                           \
-		asm volatile("" ::: "memory");                                                                                          \
-	} while (0)
-	for (int j = j_begin; j < j_end; j += 2) {
-		ERRL_STEP(0, 0, j);
-		if (j + 1 < j_end) ERRL_STEP(1, 1, j + 1);
-	}
-#undef ERRL_STEP
-#pragma unroll
-	for (int t = 0; t < QT; ++t)
-		if (qv[t] < p.Q) {
-			atomicAdd(&err_sq[qv[t]], se[t]);
-			atomicAdd(&norm_sq[qv[t]], sn[t]);
-		}
-}
-
-// Full 32-item tiles only (p.n_tiles = I / 32): the host adds the last I % 32 columns with the strided kernel of gemm.hip.
-template <int KP, typename TA>
-__global__ __launch_bounds__(256, 2) void error_kernel(const FusedParams p, const TA *__restrict__ Aex, int64_t lda,
-														float *__restrict__ err_sq, float *__restrict__ norm_sq) {
-	using Cfg = FusedCfg<KP>;
-	constexpr int KSTEPS = Cfg::KSTEPS, QT = Cfg::QT, CPR = Cfg::CPR;
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int r = lane & 31, h = lane >> 5;
-	const int wid = xcd_remap(blockIdx.x, p.n_wg);
-	const int n_rb = (int)((p.Q + Cfg::BQ - 1) / Cfg::BQ);
-	const int split = wid / n_rb, rb = wid - split * n_rb;
-
-	bf16x8 xb[QT][KSTEPS];
-	int64_t qv[QT];
-	const TA *rowp[QT];  // this lane's row of the exact matrix, at its half's first item of a tile
-#pragma unroll
-	for (int t = 0; t < QT; ++t) {
-		qv[t] = (int64_t)rb * Cfg::BQ + wave * 32 * QT + 32 * t + r;
-		const bool ok = qv[t] < p.Q;
-		rowp[t] = Aex + (ok ? qv[t] : 0) * lda + 4 * h;  // rows past Q read row 0 (their sums are dropped)
-		const u32x4 *src = reinterpret_cast<const u32x4 *>(p.X + (ok ? qv[t] : 0) * p.ldx) + h;
-#pragma unroll
-		for (int s = 0; s < KSTEPS; ++s) {
-			const u32x4 zero = {0u, 0u, 0u, 0u};
-			const u32x4 w = ok ? src[2 * s] : zero;
-			xb[t][s] = __builtin_bit_cast(bf16x8, w);
-		}
-	}
-	__builtin_amdgcn_s_waitcnt(0x0F70);  // see score_sweep_kernel: keeps vmcnt(0) out of the tile loop
-
-	const int j_begin = split * p.tiles_per_split, j_end = min(j_begin + p.tiles_per_split, p.n_tiles);
-	float se[QT], sn[QT];
-	ExactQuad<TA> ex[QT][4];  // exact values of the tile whose MFMAs run next: items 32 j + 8 g + 4 h + {0..3}, g = 0..3
-#pragma unroll
-	for (int t = 0; t < QT; ++t) { se[t] = 0.f; sn[t] = 0.f; }
-	if (j_begin < j_end) {
-		tile_dma<KP>(p.Et, j_begin, smem, wave, lane);
-#pragma unroll
-		for (int t = 0; t < QT; ++t)
-#pragma unroll
-			for (int g = 0; g < 4; ++g) ex[t][g].load(rowp[t] + (int64_t)j_begin * TILE_I + 8 * g);
-	}
-	__builtin_amdgcn_s_waitcnt(0x0F70);
-	__syncthreads();
-	uint32_t aoff[Cfg::NAOFF];   // LDS byte address of this lane's A fragment of k-step s (< NAOFF) in tile buffer 0 (see stagger_tile)
-#pragma unroll
-	for (int s = 0; s < Cfg::NAOFF; ++s) aoff[s] = lds_addr(smem) + (uint32_t)(r * CPR + swz<CPR>(r, 2 * s + h)) * 16u;
-	__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): error_mfma_tile() counts LDS reads
-#define ERR_STEP(CUR, J)                                                                                                        \
-	do {                                                                                                                        \
-		const bool more = (J) + 1 < j_end;                                                                                      \
-		if (more) tile_dma<KP>(p.Et, (J) + 1, smem + ((CUR) ^ 1) * Cfg::TILE_BYTES, wave, lane);                                \
-		f32x16 acc[QT];                                                                                                         \
-		error_mfma_tile<KP, CUR>(aoff, xb, acc);                                                                                \
-		/* the exact values are consumed HERE, behind the MFMA chain: hipcc otherwise hoists their unpacking to the top of the */ \
-		/* iteration and waits vmcnt(0) there -- for them and for the tile DMA it has just issued */                            \
-		_Pragma("unroll") for (int t = 0; t < QT; ++t)                                                                          \
-			_Pragma("unroll") for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(ex[t][g].w));                                  \
-		_Pragma("unroll") for (int t = 0; t < QT; ++t)                                                                          \
-			_Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                                    \
-				const float x = ex[t][e >> 2].get(e & 3);                                                                       \
-				const float d = acc[t][e] - x;                                                                                  \
-				se[t] = fmaf(d, d, se[t]);                                                                                      \
-				sn[t] = fmaf(x, x, sn[t]);                                                                                      \
-			}                                                                                                                   \
-		/* the next tile's exact values are requested now and consumed after the next MFMA chain; the wait below covers the */  \
-		/* tile DMA only (loads return in order: the QT*4 quads issued after it may still be in flight) */                      \
-		if (more) {                                                                                                             \
-			/* the quads must be issued AFTER the tile DMA (the counted wait relies on it) and after the sums above have */      \
-			/* consumed the previous ones: otherwise hipcc sinks the sums below the loads and renames the destinations */       \
-			if (QT == 2) asm volatile("" : "+v"(se[0]), "+v"(sn[0]), "+v"(se[QT - 1]), "+v"(sn[QT - 1])::"memory");             \
-			else asm volatile("" : "+v"(se[0]), "+v"(sn[0])::"memory");                                                         \
-			_Pragma("unroll") for (int t = 0; t < QT; ++t)                                                                      \
-				_Pragma("unroll") for (int g = 0; g < 4; ++g) ex[t][g].load(rowp[t] + (int64_t)((J) + 1) * TILE_I + 8 * g);     \
-			__builtin_amdgcn_s_waitcnt(QT == 2 ? 0x0F78 : 0x0F74);  /* vmcnt(8) / vmcnt(4) */                                   \
-		}                                                                                                                       \
-		/* raw barrier: __syncthreads() carries a release fence for which hipcc waits vmcnt(0), i.e. for the quads just issued. */ \
-		/* What the barrier orders here is LDS only: this wave's fragment reads are complete, its part of the DMA has landed. */ \
-		asm volatile("" ::: "memory");                                                                                          \
-		__builtin_amdgcn_s_barrier();                                                                                           \
-		asm volatile("" ::: "memory");                                                                                          \
-	} while (0)
-	for (int j = j_begin; j < j_end; j += 2) {
-		ERR_STEP(0, j);
-		if (j + 1 < j_end) ERR_STEP(1, j + 1);
-	}
-#undef ERR_STEP
-#pragma unroll
-	for (int t = 0; t < QT; ++t)
-		if (qv[t] < p.Q) {
-			atomicAdd(&err_sq[qv[t]], se[t]);
-			atomicAdd(&norm_sq[qv[t]], sn[t]);
-		}
-}
-
-#include "score_evalf.hpp"
-
-// ------------------------------------------------------------------ select
-// Item-tile ranges of the sweep stages (which tiles item split s swept in stage g): [begin[g] + s*tps[g], + tps[g]) below end[g].
-// stride > 1: interleaved instead (split s swept begin[g] + s, + stride, ... below end[g]).
-// chunk > 0: dynamic schedule -- stage g's tiles were swept in chunks of `chunk` tiles, chunk c of query row block rb by the item
-// split owner[g][rb * n_chunks[g] + c] (row block = q / bq); chunk id c covers the tiles of position chunk_pos(c, rot, n_chunks[g]) (rot > 0:
-// score16_kernel met the sampled tiles last; one stage).
-struct SweepStages {
-	int n, begin[3], end[3], tps[3], stride;
-	int chunk, bq, n_chunks[3], rot;
-	const uint8_t *owner[3];
-};
-
-// One workgroup per query: exact top-k of the query's candidate segments.  A segment that overflowed (or whose LDS ring
-// wrapped: poisoned count) is repaired locally: the scores of the item tiles its split swept are recomputed here (fp32 dot
-// products of the same bf16 operands) and offered unfiltered, the stored candidates of that split are ignored.  Only a query
-// that still ends with fewer than k candidates is recomputed in full.
-template <int KMAX>
-__global__ __launch_bounds__(SEL_THREADS) void select_candidates_kernel(
-	const uint2 *__restrict__ cand, const uint32_t *__restrict__ seg_cnt, int nseg, int S, SweepStages stg, int capg,
-	const uint16_t *__restrict__ X, int64_t ldx, const uint16_t *__restrict__ Et, int64_t I, int KP, uint32_t k,
-	float *__restrict__ out_val, int32_t *__restrict__ out_idx, uint32_t *__restrict__ n_fallback,
-	const int32_t *__restrict__ hard_list, const uint32_t *__restrict__ hard_cnt, const float *__restrict__ tau_in, int tau_stride,
-	const int32_t *__restrict__ remap) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const SelState s = sel_carve<KMAX>(smem);
-	float *xq = reinterpret_cast<float *>(smem + SelCfg<KMAX>::LDS_BYTES);  // [KP], repair / fallback only
-	uint32_t *bad = reinterpret_cast<uint32_t *>(xq + KP);                  // [8]: bitmap of splits to repair (S <= 256)
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	auto score_of = [&](int64_t i) {
-		float v = 0.f;
-		const uint4 *er = reinterpret_cast<const uint4 *>(Et + i * KP);
-		for (int c = 0; c < KP / 8; ++c) {
-			const uint4 w = er[c];
-			const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-			for (int d = 0; d < 4; ++d) {
-				v = fmaf(__uint_as_float(ww[d] << 16), xq[8 * c + 2 * d], v);
-				v = fmaf(__uint_as_float(ww[d] & 0xffff0000u), xq[8 * c + 2 * d + 1], v);
-			}
-		}
-		return v;
-	};
-	// either one query per workgroup (hard_list == nullptr) or a grid-stride walk over the queries the wave kernel deferred
-	const uint32_t n_work = hard_list ? *hard_cnt : gridDim.x;
-	for (uint32_t wi = blockIdx.x; wi < n_work; wi += gridDim.x) {
-	__syncthreads();
-	sel_init(s);
-	if (tid < 8) bad[tid] = 0u;
-	__syncthreads();
-	const int64_t q = hard_list ? (int64_t)hard_list[wi] : (int64_t)wi;
-	const uint32_t *cnts = seg_cnt + q * nseg;
-	for (int sg = tid; sg < nseg; sg += SEL_THREADS) {
-		const uint32_t c = cnts[sg];
-		if (c > (uint32_t)capg) { const int sp = sg % S; atomicOr(&bad[sp >> 5], 1u << (sp & 31)); }
-	}
-	__syncthreads();
-	const bool repair = (bad[0] | bad[1] | bad[2] | bad[3] | bad[4] | bad[5] | bad[6] | bad[7]) != 0u;
-	for (int sg = tid; sg < nseg; sg += SEL_THREADS) {
-		const int sp = sg % S;
-		const uint32_t cc = ((bad[sp >> 5] >> (sp & 31)) & 1u) ? 0u : cnts[sg];
-		atomicAdd(&s.scal[9], cc);
-		atomicMax(&s.scal[10], cc);
-	}
-	__syncthreads();
-	const uint32_t total = s.scal[9], maxc = s.scal[10];
-	// (the threshold the last sweep stage ran with: earlier stages' candidates below it are dropped at the load)
-	float tau = tau_in ? tau_in[q * tau_stride] : -INFINITY;
-	uint64_t tau_key = 0;
-	bool full = !repair && total < k;  // the sweep ran without a usable threshold -- a NaN query row, fewer than k non-NaN group maxima, or a k-th
-	                                    // maximum of -inf (a NaN out of the coarse threshold kernel): nothing was offered, the whole row is rescanned (nfb counts it)
-	if (!full) {
-		for (int sb = 0; sb < nseg; sb += 4) {
-			const int sg = sb + wave;
-			const int sp = sg % S;
-			const bool use = sg < nseg && !((bad[sp >> 5] >> (sp & 31)) & 1u);
-			const uint32_t c = use ? cnts[sg] : 0u;
-			const uint2 *sp_ptr = cand + (q * nseg + (sg < nseg ? sg : 0)) * (int64_t)capg;
-			for (uint32_t e0 = 0; e0 < maxc; e0 += WAVE) {
-				const uint32_t e = e0 + lane;
-				const bool in = e < c;
-				const uint2 ce = in ? sp_ptr[e] : make_uint2(0, 0);
-				sel_offer(s, in, __uint_as_float(ce.x), ce.y, tau, tau_key);
-				sel_maybe_compact<KMAX>(s, k, tau, tau_key);
-			}
-		}
-	}
-	if (repair || full) {
-		if (tid == 0) atomicAdd(n_fallback, 1u);
-		for (int c = tid; c < KP; c += SEL_THREADS) xq[c] = bf16_bits_to_f32(X[q * ldx + c]);
-		__syncthreads();
-	}
-	if (repair) {
-		for (int sp = 0; sp < S; ++sp) {
-			if (!((bad[sp >> 5] >> (sp & 31)) & 1u)) continue;  // uniform
-			for (int g = 0; g < stg.n; ++g) {
-				if (stg.chunk > 0) {  // (uniform) dynamic schedule: the chunks of this query's row block that split sp drew
-					const uint8_t *own = stg.owner[g] + (q / stg.bq) * (int64_t)stg.n_chunks[g];
-					int it = 0;
-					for (int c = 0; c < stg.n_chunks[g]; ++c) {
-						if (own[c] != (uint8_t)sp) continue;  // (uniform: every thread reads the same byte)
-						const int cp = chunk_pos(c, stg.rot, stg.n_chunks[g]);
-						const int64_t i_beg = (int64_t)(stg.begin[g] + cp * stg.chunk) * TILE_I;
-						const int64_t i_end = (int64_t)min(stg.begin[g] + (cp + 1) * stg.chunk, stg.end[g]) * TILE_I;
-						for (int64_t i0 = i_beg; i0 < i_end; i0 += SEL_THREADS, ++it) {
-							const int64_t i = i0 + tid;
-							const bool in = i < i_end && i < I;
-							const float v = in ? score_of(i) : 0.f;
-							sel_offer(s, in, v, (uint32_t)i, tau, tau_key);
-							if ((it & 15) == 15) sel_maybe_compact<KMAX>(s, k, tau, tau_key);
-						}
-					}
-					sel_maybe_compact<KMAX>(s, k, tau, tau_key);
-					continue;
-				}
-				if (stg.stride > 1) {  // (uniform) interleaved splits: tiles begin + sp, + stride, ...; 8 tiles (256 items) per pass
-					int it = 0;
-					for (int tb = stg.begin[g] + sp; tb < stg.end[g]; tb += 8 * stg.stride, ++it) {
-						const int tile = tb + (tid >> 5) * stg.stride;
-						const int64_t i = (int64_t)tile * TILE_I + (tid & 31);
-						const bool in = tile < stg.end[g] && i < I;
-						const float v = in ? score_of(i) : 0.f;
-						sel_offer(s, in, v, (uint32_t)i, tau, tau_key);
-						if ((it & 15) == 15) sel_maybe_compact<KMAX>(s, k, tau, tau_key);
-					}
-					sel_maybe_compact<KMAX>(s, k, tau, tau_key);
-					continue;
-				}
-				const int t0 = stg.begin[g] + sp * stg.tps[g];
-				const int t1 = min(t0 + stg.tps[g], stg.end[g]);
-				int it = 0;
-				for (int64_t i0 = (int64_t)t0 * TILE_I; i0 < (int64_t)t1 * TILE_I; i0 += SEL_THREADS, ++it) {
-					const int64_t i = i0 + tid;
-					const bool in = i < (int64_t)t1 * TILE_I && i < I;
-					const float v = in ? score_of(i) : 0.f;
-					sel_offer(s, in, v, (uint32_t)i, tau, tau_key);
-					if ((it & 15) == 15) sel_maybe_compact<KMAX>(s, k, tau, tau_key);
-				}
-				sel_maybe_compact<KMAX>(s, k, tau, tau_key);
-			}
-		}
-		__syncthreads();
-		full = s.scal[0] < k && tau_key == 0;  // fewer than k even after the repair (and nothing was compacted away)
-	}
-	if (full) {
-		__syncthreads();
-		if (tid == 0) s.scal[0] = 0;
-		__syncthreads();
-		tau = -INFINITY; tau_key = 0;
-		int it = 0;
-		for (int64_t i0 = 0; i0 < I; i0 += SEL_THREADS, ++it) {
-			const int64_t i = i0 + tid;
-			const bool in = i < I;
-			const float v = in ? score_of(i) : 0.f;
-			sel_offer(s, in, v, (uint32_t)i, tau, tau_key);
-			if ((it & 15) == 15) sel_maybe_compact<KMAX>(s, k, tau, tau_key);
-		}
-	}
-	sel_finish<KMAX>(s, k, out_val + q * (int64_t)k, out_idx + q * (int64_t)k, remap);
-	}
-}
-
-// Threshold refinement between sweep stages for k > 128 (workgroup-level selector): tau[q] = max(tau[q], k-th best candidate so far).
-// A query with an overflowed segment, or with fewer than k candidates yet, keeps its (still valid) threshold.
-template <int KMAX>
-__global__ __launch_bounds__(SEL_THREADS) void tau_block_kernel(const uint2 *__restrict__ cand, const uint32_t *__restrict__ seg_cnt, int nseg,
-																 int capg, uint32_t k, float *__restrict__ tau_out, int tau_stride, int prefilter) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const SelState s = sel_carve<KMAX>(smem);
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int64_t q = blockIdx.x;
-	sel_init(s);
-	const uint32_t *cnts = seg_cnt + q * nseg;
-	for (int sg = tid; sg < nseg; sg += SEL_THREADS) {
-		const uint32_t c = cnts[sg];
-		if (c > (uint32_t)capg) atomicOr(&s.scal[8], 1u);
-		atomicAdd(&s.scal[9], c > (uint32_t)capg ? 0u : c);
-		atomicMax(&s.scal[10], c > (uint32_t)capg ? 0u : c);
-	}
-	__syncthreads();
-	if (s.scal[8] != 0u || s.scal[9] <= k) return;  // (uniform)
-	const uint32_t maxc = s.scal[10];
-	float tau = prefilter ? tau_out[q * tau_stride] : -INFINITY;  // earlier candidates below the running threshold cannot be the k-th best
-	uint64_t tau_key = 0;
-	for (int sb = 0; sb < nseg; sb += 4) {
-		const int sg = sb + wave;
-		const uint32_t c = sg < nseg ? cnts[sg] : 0u;
-		const uint2 *sp = cand + (q * nseg + (sg < nseg ? sg : 0)) * (int64_t)capg;
-		for (uint32_t e0 = 0; e0 < maxc; e0 += WAVE) {
-			const uint32_t e = e0 + lane;
-			const bool in = e < c;
-			const uint2 ce = in ? sp[e] : make_uint2(0, 0);
-			sel_offer(s, in, __uint_as_float(ce.x), ce.y, tau, tau_key);
-			sel_maybe_compact<KMAX>(s, k, tau, tau_key);
-		}
-	}
-	__syncthreads();
-	if (s.scal[0] > k) {  // (uniform) cut to k: the k-th best key is the new threshold
-		tau_key = sel_compact<KMAX>(s, k);
-		tau = key_val(tau_key);
-	}
-	if (tid == 0 && tau_key != 0 && s.scal[0] >= k) tau_out[q * tau_stride] = fmaxf(tau_out[q * tau_stride], tau);
-}
-
-// One WAVE per query (k <= 128, <= 64 segments): the query's candidate segments are streamed through the wave-level
-// selector of wave_select.hpp (wave-private LDS buffer, ballot/popcount radix select, in-register bitonic sort).
-// No workgroup barrier.  Queries whose segments overflowed or that collected fewer than k candidates are appended to
-// hard_list for the workgroup-level kernel (which recomputes them exactly).
-constexpr int WQ_CAP = 1024;
-constexpr int WQ_K2 = 1024;  // largest k of the wave-level candidate select (select_stream.hpp: 16 keys per lane in the final sort)
-template <int KW> struct WqCfg { static constexpr int CAP = KW <= 128 ? WQ_CAP : 2048, TRIGGER = CAP - WAVE, E = KW / 64; };
-
-// TAU_ONLY (between sweep stages): no output, the query's threshold is raised to the k-th best candidate collected so far.
-// KW = 128 or 512: capacity class of k.
-template <bool TAU_ONLY, int KW = 128>
-__global__ __launch_bounds__(256) void select_wave_kernel(const uint2 *__restrict__ cand, const uint32_t *__restrict__ seg_cnt, int nseg,
-														   int capg, int64_t Q, uint32_t k, float *__restrict__ out_val,
-														   int32_t *__restrict__ out_idx, uint32_t *__restrict__ hard_cnt,
-														   int32_t *__restrict__ hard_list, float *__restrict__ tau, int tau_stride, int prefilter,
-														   const int32_t *__restrict__ remap) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const int lane = lane_id(), wave = threadIdx.x >> 6;
-	const int64_t q = (int64_t)blockIdx.x * 4 + wave;
-	if (q >= Q) return;
-	const uint32_t c = (lane < nseg) ? seg_cnt[q * nseg + lane] : 0u;
-	const uint32_t inc = wave_scan_incl<DppAdd>(c);
-	const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, WAVE - 1), pre = inc - c;
-	if (__ballot(c > (uint32_t)capg) != 0ull || total < k) {
-		if (!TAU_ONLY && lane == 0) hard_list[atomicAdd(hard_cnt, 1u)] = (int32_t)q;
-		return;  // TAU_ONLY: keep the old (still valid) threshold
-	}
-	constexpr int CAP = WqCfg<KW>::CAP, TRIGGER = WqCfg<KW>::TRIGGER;
-	WaveSel w = wsel_init<CAP>(smem + wave * WaveSelLayout<CAP>::BYTES);
-	// the threshold the last sweep stage ran with is a valid lower bound on the k-th best: candidates of earlier stages below it
-	// are dropped at the load (at least k candidates are >= it by construction)
-	if (tau && prefilter) w.tau = tau[q * tau_stride];
-	const uint2 *qc = cand + q * nseg * (int64_t)capg;
-	// The candidates are fetched LOAD_U chunks of 64 at a time: the batch's flat-index -> (segment, entry) searches advance in
-	// LOCKSTEP (one round = LOAD_U independent ds_bpermute, one wait), the loads are unconditional (clamped address) and issued back
-	// to back.  Written chunk by chunk hipcc emitted LOAD_U serial chains of seven LDS round trips and one exposed HBM latency per chunk.
-	// (A search without LDS -- the segment ends read into scalars with v_readlane, every lane counting the ends at or below its index --
-	//  was slower: 9.5 k instead of 5 k cycles per wave for the 23 ends x 8 chunks.)
-	constexpr int LOAD_U = 8;
-	for (uint32_t j0 = 0; j0 < total; j0 += LOAD_U * WAVE) {
-		int sg[LOAD_U];  // last segment whose exclusive prefix is <= j (skips empty segments)
-#pragma unroll
-		for (int u = 0; u < LOAD_U; ++u) sg[u] = 0;
-#pragma unroll
-		for (int step = 32; step >= 1; step >>= 1) {
-			if (step < nseg) {  // (uniform: segments >= nseg do not exist)
-				uint32_t pv[LOAD_U];
-#pragma unroll
-				for (int u = 0; u < LOAD_U; ++u) pv[u] = __shfl(pre, (sg[u] + step) & 63);
-#pragma unroll
-				for (int u = 0; u < LOAD_U; ++u)
-					if (sg[u] + step < nseg && pv[u] <= j0 + (uint32_t)(u * WAVE + lane)) sg[u] += step;
-			}
-		}
-		uint32_t ps[LOAD_U];
-#pragma unroll
-		for (int u = 0; u < LOAD_U; ++u) ps[u] = __shfl(pre, sg[u]);
-		uint2 e[LOAD_U];
-#pragma unroll
-		for (int u = 0; u < LOAD_U; ++u) {
-			const uint32_t j = j0 + (uint32_t)(u * WAVE + lane);
-			e[u] = qc[j < total ? (int64_t)sg[u] * capg + (j - ps[u]) : 0];
-		}
-#pragma unroll
-		for (int u = 0; u < LOAD_U; ++u) {
-			if (j0 + (uint32_t)(u * WAVE) < total) {  // (uniform)
-				wsel_offer(w, j0 + (uint32_t)(u * WAVE + lane) < total, __uint_as_float(e[u].x), e[u].y);
-				if (w.cnt > (uint32_t)TRIGGER) wsel_compact<4, false, true>(w, k);
-			}
-		}
-	}
-	if (TAU_ONLY) {
-		if (w.cnt > k) wsel_compact<4, false, true>(w, k);
-		if (lane == 0 && w.cnt >= k) tau[q * tau_stride] = fmaxf(tau[q * tau_stride], w.tau);
-		return;
-	}
-	wsel_finish<0, 4, WqCfg<KW>::E, true>(w, k, out_val + q * (int64_t)k, out_idx + q * (int64_t)k, remap);
-}
+// The kernels, one header per body, in the order their definitions have always had in this translation unit.  This file keeps the plan,
+// the launchers and the C entry points.
+#include "sweep_common.hpp"    // types, FusedCfg, FusedParams, tile DMA, LDS accessors, fragment ring, query operand load
+#include "tile_schedule.hpp"   // the dynamic tile schedule (tickets, XCD slices), once for the three sweep kernels
+#include "score32.hpp"         // 32x32x16 bodies: per-lane rings, score_prepass_kernel, score_sweep_kernel
+#include "score16.hpp"         // 16x16x32 sweep (Kp <= 256): WaveQueue, threshold ladder, score16_kernel
+#include "prepass16.hpp"       // prepass on that body
+#include "score_q16.hpp"       // 16x16x32 sweep at Kp = 512
+#include "score_error.hpp"     // approximation-error kernels
+#include "score_evalf.hpp"     // error sums and candidates in one sweep
+#include "fused_select.hpp"    // select and threshold refinement
 
 }  // namespace
 namespace {

@@ -60,7 +60,7 @@ __device__ __forceinline__ void staggerq16_tile(const uint32_t (&aoff8)[8], cons
 		acc[ih][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, xb[1][ks], acc[ih][1], 0, 0, 0);
 		if (g & 1) {  // element e = g >> 1 of the previous tile: item half e >> 3, sub-tile (e >> 2) & 1, register e & 3
 			const int e = g >> 1;
-			filter16_one(accP[e >> 3][(e >> 2) & 1][e & 3], (uint32_t)(((e >> 3) * 16 + (e & 3)) | ((uint32_t)((e >> 2) & 1) << (WQ_ITEM_BITS + 4))),
+			filter16_one(accP[e >> 3][(e >> 2) & 1][e & 3], wq_elem_code(e, 0),
 						 ((e >> 2) & 1) ? tau1 : tau0, item0_prev, w, fill);
 		}
 	}
@@ -85,14 +85,7 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 #pragma unroll
 	for (int t = 0; t < 2; ++t) {
 		qv[t] = (int64_t)rb * C::BQ + wave * 32 + 16 * t + c16;
-		const bool ok = qv[t] < p.Q;
-		const u32x4 *src = reinterpret_cast<const u32x4 *>(p.X + (ok ? qv[t] : 0) * p.ldx) + g4;
-#pragma unroll
-		for (int s = 0; s < KS32; ++s) {
-			const u32x4 zero = {0u, 0u, 0u, 0u};
-			const u32x4 wv = ok ? src[4 * s] : zero;
-			xb[t][s] = __builtin_bit_cast(bf16x8, wv);
-		}
+		LOAD_QUERIES16(qv[t], g4, xb[t]);
 	}
 	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see score_sweep_kernel
 
@@ -103,50 +96,12 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 	const uint32_t lds_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(smem));
 	const int64_t q_wave0 = (int64_t)rb * C::BQ + wave_u * 32;  // (uniform) the wave's first query
 	WaveQueue w;
-	w.base = lds_base + (uint32_t)(C::QUEUE_OFF + wave_u * C::QCAP * 8);
-	w.limit = w.base + (uint32_t)(C::QCAP - 64 * (C::CHECK_PUSHES + 1)) * 8u;
-	w.cnt = lds_base + (uint32_t)(C::CNT_OFF + wave_u * 128);
-	w.q_stride8 = (uint32_t)p.nseg * (uint32_t)p.capg * 8u;
-	w.seg = p.cand + (q_wave0 * p.nseg + split) * (int64_t)p.capg;
-	w.capg = (uint32_t)p.capg; w.n_items = (uint32_t)p.I; w.lane = lane;
-	uint32_t fill = w.base;
-	if (lane < 32) {
-		const int64_t q = q_wave0 + lane;
-		lds_write_u32(w.cnt + (uint32_t)lane * 4u, q < p.Q ? (p.carry ? p.seg_cnt[q * p.nseg + split] : 0u) : PAD_ROW_COUNT);
-	}
+	uint32_t fill;
+	wq_init<C, 32, C::CHECK_PUSHES + 1>(w, fill, p, lds_base, wave_u, lane, split, q_wave0);
 
-	// ---- tile schedule: tickets (see score_sweep_kernel), or a static contiguous share
+	// ---- tile schedule (tile_schedule.hpp): tickets, or a static contiguous share
 	const int j_begin = p.tile_begin + split * p.tiles_per_split, j_end = min(j_begin + p.tiles_per_split, p.tile_end);
-	int t_cur = j_begin < j_end ? j_begin : -1, t_cend = j_end, t_next_chunk = -1;
-	bool ticket_pending = false;
-	const bool dyn = p.chunk_tiles > 0;
-	uint32_t ticket_slot = lds_addr(smem + C::TICKET_OFF);
-	// XCD-sliced tickets (score_fused.hip 'XCD-sliced tickets'): thread 0's slice state; unsliced = one counter per row block as in round 3
-	uint32_t *const ctr_rb = p.chunk_ctr + (p.sliced ? (size_t)rb * N_SLICES : (size_t)rb);
-	int slice = p.sliced ? xcc_id() : 0, tried = 0;
-	if (dyn) {
-		if (tid == 0) {
-			uint32_t c0, c1;
-			if (p.sliced) {
-				c0 = slice_resolve(atomicAdd(ctr_rb + slice, 1u), ctr_rb, p.n_chunks, p.chunks_per_slice, slice, tried);
-				c1 = c0 < (uint32_t)p.n_chunks ? slice_resolve(atomicAdd(ctr_rb + slice, 1u), ctr_rb, p.n_chunks, p.chunks_per_slice, slice, tried) : (uint32_t)p.n_chunks;
-			} else {
-				c0 = atomicAdd(ctr_rb, 2u); c1 = c0 + 1u;
-			}
-			if (p.chunk_owner) {
-				if (c0 < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c0] = (uint8_t)split;
-				if (c1 < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + c1] = (uint8_t)split;
-			}
-			lds_write_u32(ticket_slot + 8u, c0);   // (the prologue's pair sits in the third and fourth ticket word)
-			lds_write_u32(ticket_slot + 12u, c1);
-			__builtin_amdgcn_s_waitcnt(0xC07F);
-		}
-		__syncthreads();
-		const uint32_t c = lds_load_u32_uniform(ticket_slot + 8u), c1 = lds_load_u32_uniform(ticket_slot + 12u);
-		t_cur = c < (uint32_t)p.n_chunks ? p.tile_begin + (int)c * p.chunk_tiles : -1;
-		t_cend = min(t_cur + p.chunk_tiles, p.tile_end);
-		t_next_chunk = c1 < (uint32_t)p.n_chunks ? p.tile_begin + (int)c1 * p.chunk_tiles : -1;
-	}
+	TILE_SCHEDULE_BEGIN(p.chunk_tiles > 0, p.sliced, lds_addr(smem + C::TICKET_OFF), TILE_OF_CHUNK)
 	uint32_t dma_off[C::TILE_BYTES / 4096];
 	tile_dma_offsets<KP>(dma_off, wave_u, lane);
 	if (t_cur >= 0) tile_dma_s<KP>(p.Et, t_cur, lds_base, wave_u, dma_off);
@@ -170,35 +125,11 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 	__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): staggerq16_tile() counts LDS reads
 #define Q16_STEP(CUR, ACC, ACCP)                                                                                                \
 	do {                                                                                                                        \
-		const int J = t_cur;                                                                                                    \
-		if (ticket_pending) {                                                                                                   \
-			const uint32_t c = lds_load_u32_uniform(ticket_slot);                                                               \
-			t_next_chunk = c < (uint32_t)p.n_chunks ? p.tile_begin + (int)c * p.chunk_tiles : -1;                               \
-			ticket_pending = false;                                                                                             \
-			ticket_slot ^= 4u;                                                                                                  \
-		}                                                                                                                       \
-		int nx = J + 1;                                                                                                         \
-		bool crossed = false;                                                                                                   \
-		if (nx >= t_cend) { nx = t_next_chunk; crossed = dyn && nx >= 0; }                                                      \
-		if (nx >= 0) tile_dma_s<KP>(p.Et, nx, lds_base + ((CUR) ^ 1) * C::TILE_BYTES, wave_u, dma_off);                         \
-		uint32_t ticket = 0;                                                                                                    \
-		if (crossed && tid == 0) ticket_draw(ticket, ctr_rb + slice);                                                           \
+		TILE_STEP_HEAD(KP, CUR, TILE_OF_CHUNK, 1)                                                                               \
 		if (fill >= w.base + C::DRAIN_AT * 8u) wq_drain(w, fill);                                                               \
 		staggerq16_tile<KP, CUR>(aoff8, xb, ACC, ACCP, tp0, tp1, item0_prev, w, fill);                                          \
 		tp0 = tau0; tp1 = tau1; item0_prev = ((uint32_t)J * TILE_I + 4 * g4) | lane_code;                                       \
-		ticket_wait(ticket);                                                                                                    \
-		if (crossed) {                                                                                                          \
-			if (tid == 0) {                                                                                                     \
-				if (p.sliced) ticket = slice_resolve(ticket, ctr_rb, p.n_chunks, p.chunks_per_slice, slice, tried);             \
-				lds_write_u32(ticket_slot, ticket);                                                                             \
-				if (p.chunk_owner && ticket < (uint32_t)p.n_chunks) p.chunk_owner[(int64_t)rb * p.n_chunks + ticket] = (uint8_t)split; \
-				__builtin_amdgcn_s_waitcnt(0xC07F);                                                                             \
-			}                                                                                                                   \
-			ticket_pending = true;                                                                                              \
-			t_cend = min(nx + p.chunk_tiles, p.tile_end);                                                                       \
-		}                                                                                                                       \
-		__syncthreads();                                                                                                        \
-		t_cur = nx;                                                                                                             \
+		TILE_STEP_TAIL(p.sliced, )                                                                                              \
 	} while (0)
 	ANNCUR_PAD_HERE();
 	bool last_in_a = false;  // (uniform) which accumulator set holds the last tile
@@ -214,19 +145,12 @@ __global__ __launch_bounds__(256, 2) void scoreq16_kernel(const FusedParams p) {
 	wq_drain(w, fill);
 #define Q16_LAST(ACC)                                                                                                           \
 	_Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                                            \
-		filter16_one(ACC[e >> 3][(e >> 2) & 1][e & 3], (uint32_t)(((e >> 3) * 16 + (e & 3)) | ((uint32_t)((e >> 2) & 1) << (WQ_ITEM_BITS + 4))), \
+		filter16_one(ACC[e >> 3][(e >> 2) & 1][e & 3], wq_elem_code(e, 0), \
 					 ((e >> 2) & 1) ? tp1 : tp0, item0_prev, w, fill);                                                          \
 		if ((e % C::CHECK_PUSHES) == C::CHECK_PUSHES - 1 && fill > w.limit) wq_drain(w, fill);                                  \
 	}
 	if (last_in_a) { Q16_LAST(accA) } else { Q16_LAST(accB) }
 #undef Q16_LAST
 	wq_drain(w, fill);
-	if (lane < 32) {
-		const int64_t q = q_wave0 + lane;
-		uint32_t c = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-		asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(c) : "v"(w.cnt + (uint32_t)lane * 4u) : "memory");
-#endif
-		if (q < p.Q) p.seg_cnt[q * p.nseg + split] = c;
-	}
+	wq_store_counts<32>(w, p, split, q_wave0);
 }

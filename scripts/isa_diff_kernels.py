@@ -12,7 +12,8 @@ from check_kernel_resources import parse_kernel_notes
 RES = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size")
 # template parameters that went away: old spelling -> new spelling of the same kernel
 RENAMES = [(r"score_kernel<(\d+), 0, (\d+), false, false, (\d+)>", r"score_prepass_kernel<\1, \2, \3>"),
-		   (r"score_kernel<(\d+), 1, 16, (\w+), false, (\d+)>", r"score_sweep_kernel<\1, \2, \3>")]
+		   (r"score_kernel<(\d+), 1, 16, (\w+), false, (\d+)>", r"score_sweep_kernel<\1, \2, \3>"),
+		   (r"score16_kernel<(\d+), 4>", r"score16_kernel<\1>")]
 
 
 def demangle(names):
@@ -39,6 +40,8 @@ def load(lib):
 	kern = {}
 	for dis in disassemble(lib):
 		for name, body in functions(dis):
+			# (zero words behind the last instruction pad the gap to the next function: the disassembler prints them as v_cndmask_b32 v0, s0, v0, vcc)
+			while body and re.search(r":\s*00000000\s*$", body[-1][2]): body = body[:-1]
 			kern[name] = [regs(ins) for _, ins, _ in body]
 	notes = {k[".name"]: k for text in kernel_notes(lib) for k in parse_kernel_notes(text)}
 	dm = demangle(sorted(notes))

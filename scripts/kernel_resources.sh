@@ -1,5 +1,5 @@
 #!/bin/bash
-# Dev tool: VGPRs / SGPRs / scratch / occupancy of every kernel of one source file (hipcc -Rpass-analysis=kernel-resource-usage), one line each.
+# Dev tool: VGPRs / SGPRs / scratch / occupancy of every kernel of one source file and the headers it includes (hipcc -Rpass-analysis=kernel-resource-usage), one line each.
 # usage: bash scripts/kernel_resources.sh score_fused.hip [grep pattern] [extra hipcc flags]
 cd "$(dirname "$0")/../anncur_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I../../include $3 -Rpass-analysis=kernel-resource-usage -c "$1" -o /tmp/kres.o 2>&1 \

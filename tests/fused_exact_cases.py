@@ -3,7 +3,7 @@
 Everything is small-integer data: every bf16 operand and every fp32 partial sum of a score is exact, so a score matrix S [Q x I] built here
 on the host (integers, never read back from the device) is what the kernels must compute bit for bit.  The references below are written
 from the kernels' own definitions:
-  - the prepass' sample and group layout: score_prepass_kernel<KP, GROUP> in csrc/score_fused.hip (32-item tiles, tile_of) and
+  - the prepass' sample and group layout: score_prepass_kernel<KP, GROUP> in csrc/score32.hpp (32-item tiles, tile_of) and
     wide_kernel<0, GROUP> in csrc/score_wide.hpp (256-item block tiles, bt_of; a block tile is eight 32-item sub-tiles in the same layout);
   - the threshold the sweep runs with: the k-th largest group maximum, cut to its 16-bit key prefix by the coarse threshold kernel
     (kth_value_wave_kernel in csrc/topk.hip) while a query has at most 4096 group maxima, exact above."""

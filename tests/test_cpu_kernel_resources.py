@@ -72,18 +72,18 @@ def _kernel(name, vgpr, scratch=0, lds=0, **more):
 	return {".name": name, ".vgpr_count": vgpr, ".private_segment_fixed_size": scratch, ".group_segment_fixed_size": lds, **more}
 
 
-_SWEEP = "_ZN12_GLOBAL__N_114score16_kernelILi256ELi4EEEvNS_11FusedParamsE"
+_SWEEP = "_ZN12_GLOBAL__N_114score16_kernelILi256EEEvNS_11FusedParamsE"
 _GATHER = "_ZN12_GLOBAL__N_118gather_cols_kernelIttEEvPKT_lllPKiiPT0_l"
 _OVERLAP = "_ZN12_GLOBAL__N_119overlap_wave_kernelEPKiiS1_ilNS_8OvlPairsEiPi"
 
 
 def test_verdicts():
 	from check_kernel_resources import check_kernels
-	others = [_kernel("_ZN12_GLOBAL__N_114score16_kernelILi128ELi4EEEvNS_11FusedParamsE", 300, scratch=64),      # not held to a budget
+	others = [_kernel("_ZN12_GLOBAL__N_114score16_kernelILi128EEEvNS_11FusedParamsE", 300, scratch=64),      # not held to a budget
 			  _kernel("_ZN12_GLOBAL__N_118gather_cols_kernelIffEEvPKT_lllPKiiPT0_l", 64, lds=4096)]
 	good = [_kernel(_SWEEP, 240), _kernel(_GATHER, 18), _kernel(_OVERLAP, 14)] + others
 	f, rows = check_kernels(good)
-	assert f == [] and [w for w, _ in rows] == ["score16_kernel<256, 4>", "gather_cols_kernel<uint16_t, uint16_t>", "overlap_wave_kernel"]
+	assert f == [] and [w for w, _ in rows] == ["score16_kernel<256>", "gather_cols_kernel<uint16_t, uint16_t>", "overlap_wave_kernel"]
 	assert check_kernels([_kernel(_SWEEP, 233), _kernel(_GATHER, 24, scratch=8), _kernel(_OVERLAP, 24)])[0] == []    # scratch is the sweep's limit only
 
 	def one(ks, word):
@@ -101,7 +101,7 @@ def test_verdicts():
 	one([_kernel(_SWEEP, 240), _kernel(_GATHER, 18), _kernel(_OVERLAP, 14, lds=64)], "overlap_wave_kernel: 64 bytes of LDS")
 	# a kernel that was renamed or dropped does not pass silently
 	one([_kernel(_SWEEP, 240), _kernel(_GATHER, 18)], "overlap_wave_kernel: 0 kernels match")
-	one([_kernel(_GATHER, 18), _kernel(_OVERLAP, 14)], "score16_kernel<256, 4>: 0 kernels match")
+	one([_kernel(_GATHER, 18), _kernel(_OVERLAP, 14)], "score16_kernel<256>: 0 kernels match")
 	bad = _kernel(_SWEEP, 240)
 	del bad[".private_segment_fixed_size"]
 	one([bad, _kernel(_GATHER, 18), _kernel(_OVERLAP, 14)], "no .private_segment_fixed_size")
@@ -125,13 +125,13 @@ def test_parser_on_the_built_library(built):
 		assert 1 <= k[".vgpr_count"] <= 512 and k[".private_segment_fixed_size"] >= 0 and 0 <= k[".group_segment_fixed_size"] <= 163840, k
 		assert k[".wavefront_size"] == 64 and isinstance(k[".uses_dynamic_stack"], bool), k
 		assert k[".symbol"] == k[".name"] + ".kd"
-	for frag in ("14score16_kernelILi64ELi4EE", "14score16_kernelILi128ELi4EE", "14score16_kernelILi256ELi4EE", "16prepass16_kernelILi256EE",
+	for frag in ("14score16_kernelILi64EE", "14score16_kernelILi128EE", "14score16_kernelILi256EE", "16prepass16_kernelILi256EE",
 				 "18gather_cols_kernelIttEE", "18gather_cols_kernelIffEE", "19overlap_wave_kernelE"):
 		assert sum(frag in n for n in names) == 1, frag
 
 
 def test_built_library_keeps_the_room_beside_the_sweep(built):
-	"""What `make verify` enforces: score16_kernel<256, 4> at 240 VGPRs or fewer without scratch, the column gather and the overlap counts
+	"""What `make verify` enforces: score16_kernel<256> at 240 VGPRs or fewer without scratch, the column gather and the overlap counts
 	at 24 or fewer without LDS -- two sweep waves and one of theirs fit a SIMD's 512 registers."""
 	from check_kernel_resources import allocated_vgprs, check, check_kernels
 	f, rows = check_kernels(built)

@@ -1,6 +1,6 @@
 """Exact-data tests of the fused score + top-k at Kp = 512 and on the wide kernel (Kp > 512): the three sweep bodies that had none --
   "q16"  scoreq16_kernel (csrc/score_q16.hpp): Kp = 512, the default; wave-level queue, XCD-sliced tickets, owner-map repair;
-  "ring" score_sweep_kernel<512> (csrc/score_fused.hip, the per-lane-ring body, mfma32=True): static interleaved tile shares;
+  "ring" score_sweep_kernel<512> (csrc/score32.hpp, the per-lane-ring body, mfma32=True): static interleaved tile shares;
   "wide" wide_kernel (csrc/score_wide.hpp): Kp = 640 and 1152, 256-item block tiles, static contiguous shares.
 Every operand is a small integer, so every score is exact in fp32 in any order and the result must be THE top-k (values descending,
 ties by ascending row) bit for bit.  Every call runs on a private workspace filled with 0xff (the q16 / ring chains rely on

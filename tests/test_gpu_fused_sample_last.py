@@ -1,5 +1,5 @@
 """The fused score + top-k when its sweep meets the prepass' sampled tiles LAST and starts the threshold ladder from the prepass
-(csrc/score16.hpp 'SAMPLED TILES LAST'; the pre-credit: kth_value_wave_kernel in csrc/topk.hip; the chunk map: chunk_pos in csrc/score_fused.hip).
+(csrc/score16.hpp 'SAMPLED TILES LAST'; the pre-credit: kth_value_wave_kernel in csrc/topk.hip; the chunk map: chunk_pos in csrc/sweep_common.hpp).
 
 The route is taken by the ladder plans with the leading sample whose prepass runs on the sweep's own body (groups of 16: I >= 65 536 at
 k <= 128); below that the plan keeps item order and counters from zero, and the same assertions hold for it.  All data is small-integer

@@ -1,5 +1,5 @@
 """The prepass of the fused score + top-k on the sweep's 16x16x32 body (csrc/prepass16.hpp) and the workspace header the prepass kernels
-clear themselves (zero_ws_header in csrc/score_fused.hip; there is no memset launch in front of the chain any more).
+clear themselves (zero_ws_header in csrc/sweep_common.hpp; there is no memset launch in front of the chain any more).
 
 Every workspace here is filled with 0xff before its first call: the header words, the ticket counters and the ladder's counter words start
 poisoned, so a chain that still relied on a memset returns garbage (tickets past the last chunk: nothing is swept; ladder fields at
