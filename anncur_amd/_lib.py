@@ -65,6 +65,12 @@ SIGNATURES = {
 								  c_void_p, c_size_t, c_void_p]),
 	"anncur_score_topk_ex": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p,
 									 c_void_p, c_size_t, c_int32, c_void_p, c_void_p]),
+	"anncur_score_topk_few_supported": (c_int, [c_int64, c_int64, c_int32, c_int32]),
+	"anncur_score_topk_few_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+	"anncur_score_topk_few": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+									  c_void_p, c_size_t, c_void_p]),
+	"anncur_score_rows_few": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+	"anncur_score_topk_few_plan": (c_int, [c_int64, c_int64, c_int32, c_int32, _p32, c_int32]),
 	"anncur_pack_split_bf16": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p]),
 	"anncur_rescore_topk": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int64, c_int64, c_int32,
 									c_void_p, c_void_p, c_void_p, c_void_p]),

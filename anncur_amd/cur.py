@@ -140,8 +140,9 @@ def _is_full_range(idx, n):
 
 class CURApprox(object):
 
-	def __init__(self, rows, cols, row_idxs, col_idxs, approx_preference, A=None, compute_dtype=None, device=None, pinv_backend="auto", rcond=None):
-		"""rcond: the cutoff of U = pinv(W) relative to W's largest singular value, for pinv_backend "svd" and "numpy" (None = the reference's
+	def __init__(self, rows, cols, row_idxs, col_idxs, approx_preference, A=None, compute_dtype=None, device=None, pinv_backend="auto", rcond=None, small_batch=False):
+		"""small_batch: compute_dtype "bf16" only -- calls of up to 64 queries take the small-batch route (topk_route names it).
+		rcond: the cutoff of U = pinv(W) relative to W's largest singular value, for pinv_backend "svd" and "numpy" (None = the reference's
 		1e-15; with any other backend a given rcond is a ValueError).  With "svd" and no A=, singular_values (fp64, descending) and rank (those
 		above the cutoff) describe the anchor block W; they are None otherwise, and where the block went to the host."""
 		super(CURApprox, self).__init__()
@@ -168,6 +169,7 @@ class CURApprox(object):
 		if compute_dtype not in COMPUTE_DTYPES:
 			raise ValueError(f"compute_dtype = {compute_dtype} not supported")
 		self.compute_dtype = compute_dtype
+		self.small_batch = bool(small_batch)
 
 		assert _is_sorted(self.row_idxs), "row_idxs should be sorted"
 		assert _is_sorted(self.col_idxs), "col_idxs should be sorted"
@@ -296,12 +298,19 @@ class CURApprox(object):
 		excl, kc = _exclusion_arg(exclude, Q, self.m, k, self.device)
 		if self._split is not None and self._split.takes(Q, self.m, k, excl):
 			return self._split.topk(X, self._Et, k, excl)
+		if _few_takes(self, Q, kc):
+			return _filtered(ops.score_topk_few(ops.pack_bf16(X, self._Etp.shape[1]), self._Etp, self.m, kc), excl, k)
 		if self._Etp is not None and ops.fused_supported(Q, self.m, self._Etp.shape[1], kc):
 			return _filtered(ops.score_topk_fused(ops.pack_bf16(X, self._Etp.shape[1]), self._Etp_sorted, self.m, kc, leading_sample=True, item_ids=self._item_ids), excl, k)
 		Et = self._Et if self.compute_dtype != "bf16" else (self._Etp[:self.m, :X.shape[1]] if self._Etp is not None else self._Et)
 		if self.compute_dtype == "bf16" and X.dtype != torch.bfloat16:
 			X = ops.convert(X, torch.bfloat16)
 		return _filtered(ops.score_topk_dense(X, Et, kc), excl, k)
+
+	def topk_route(self, Q, k, exclude=None):
+		"""The route topk_in_row takes for Q queries and k results: "bf16x3", "bf16-few", "bf16" or "dense" (_route_name)."""
+		excl, _ = _exclusion_arg(exclude, Q, self.m, k, self.device)
+		return _route_name(self, Q, k, excl)
 
 	def topk_in_row(self, sparse_rows, k, exclude=None):
 		v, i = self.topk_in_row_device(sparse_rows, k, exclude=exclude)
@@ -401,12 +410,22 @@ class _SplitOperands(object):
 		return ops.approx_error_packed(ops.pack_split_bf16(X, 0, self.kp), self._item_order, A, Et.shape[0])
 
 
+def _few_takes(op, Q, kc):
+	"""The small-batch route: only where the index was built with small_batch=True on the "bf16" operands, for up to 64
+	queries; "fp32" and "bf16x3" indices ignore the flag."""
+	return (getattr(op, "small_batch", False) and op.compute_dtype == "bf16" and op._Etp is not None and kc <= min(op.m, ops._lib.MAX_TOPK)
+			and ops.score_topk_few_ok(Q, op.m, op._Etp.shape[1], kc))
+
+
 def _route_name(op, Q, k, excl=None):
-	"""Which of the three top-k routes `op` (a CURRowIndex or an _ItemOperand) takes for Q queries and k results: "bf16x3" (split
-	operands + fp32 rescore), "bf16" (fused sweep) or "dense" (fp32 / bf16 GEMM + exact scan)."""
+	"""Which of the top-k routes `op` (a CURRowIndex, a CURApprox or an _ItemOperand) takes for Q queries and k results: "bf16x3" (split
+	operands + fp32 rescore), "bf16-few" (small_batch=True and Q <= 64: the streamed score + group-sparse select), "bf16" (fused sweep) or
+	"dense" (fp32 / bf16 GEMM + exact scan)."""
 	kc = k + (excl.e_max if excl is not None else 0)
 	if op._split is not None and op._split.takes(Q, op.m, k, excl):
 		return "bf16x3"
+	if _few_takes(op, Q, kc):
+		return "bf16-few"
 	if op._Etp is not None and kc <= min(op.m, ops._lib.MAX_TOPK) and ops.fused_supported(Q, op.m, op._Etp.shape[1], kc):
 		return "bf16"
 	return "dense"
@@ -419,6 +438,8 @@ def _route_topk(op, X, k, exclude=None):
 	excl, kc = _exclusion_arg(exclude, Q, op.m, k, X.device)
 	if op._split is not None and op._split.takes(Q, op.m, k, excl):
 		return op._split.topk(X, op._Et, k, excl)
+	if _few_takes(op, Q, kc):
+		return _filtered(ops.score_topk_few(ops.pack_bf16(X, op._Etp.shape[1]), op._Etp, op.m, kc), excl, k)
 	if op._Etp is not None and ops.fused_supported(Q, op.m, op._Etp.shape[1], kc):
 		return _filtered(ops.score_topk_fused(ops.pack_bf16(X, op._Etp.shape[1]), op._Etp_sorted, op.m, kc, leading_sample=True, item_ids=op._item_ids), excl, k)
 	Et = op._Et if op.compute_dtype != "bf16" or op._Etp is None else op._Etp[:op.m, :X.shape[1]]
@@ -490,8 +511,8 @@ class _ItemOperand(object):
 	"""An item-major fp32 matrix Et [m x K] prepared for _route_topk the way CURRowIndex prepares E^T: "bf16" packs it (item order and
 	descending-norm order with the id map), "bf16x3" builds the split operands, "fp32" keeps it as it is."""
 
-	def __init__(self, Et, compute_dtype):
-		self._Et, self.m, self.compute_dtype = Et, Et.shape[0], compute_dtype
+	def __init__(self, Et, compute_dtype, small_batch=False):
+		self._Et, self.m, self.compute_dtype, self.small_batch = Et, Et.shape[0], compute_dtype, bool(small_batch)
 		kp = ops.padded_k(Et.shape[1])
 		self._Etp = self._Etp_sorted = self._item_ids = None
 		if compute_dtype == "bf16" and kp is not None:
@@ -561,8 +582,9 @@ class CURRowIndex(object):
 	all-gather, U = pinv(R[:, col_idxs]) and E = U.R replicated, its own queries' anchor scores gathered locally.
 	Same arithmetic as CURApprox(rows=R, cols=A[:, col_idxs], ...) (eval/matrix_approx_zeshel.py:42-65)."""
 
-	def __init__(self, rows, col_idxs, compute_dtype=None, pinv_backend="auto", rcond=None):
-		"""rcond, and the attributes singular_values / rank that pinv_backend "svd" fills: as for CURApprox."""
+	def __init__(self, rows, col_idxs, compute_dtype=None, pinv_backend="auto", rcond=None, small_batch=False):
+		"""small_batch: compute_dtype "bf16" only -- calls of up to 64 queries (topk, and the adaptive search's rounds) take the small-batch
+		route (topk_route names the route of a call).  rcond, and the attributes singular_values / rank that pinv_backend "svd" fills: as for CURApprox."""
 		self.rcond = check_pinv_args(pinv_backend, rcond)
 		self.R = rows
 		self.m = rows.shape[1]
@@ -572,6 +594,7 @@ class CURRowIndex(object):
 		if compute_dtype not in COMPUTE_DTYPES:
 			raise ValueError(f"compute_dtype = {compute_dtype} not supported")
 		self.compute_dtype = compute_dtype
+		self.small_batch = bool(small_batch)
 		W = ops.gather_cols(rows, col_idxs)                      # kr x kc
 		info = {}
 		self.U = _pinv(W, rows.device, pinv_backend, self.rcond, info)   # kc x kr
@@ -590,6 +613,11 @@ class CURRowIndex(object):
 		exclude: items left out of the result, as for CURApprox.topk_in_row_device (e.g. ops.exclusion(self.col_idxs, ...), built once:
 		the anchor items, whose exact scores the caller holds already)."""
 		return _route_topk(self, X, k, exclude)
+
+	def topk_route(self, Q, k, exclude=None):
+		"""The route topk() takes for Q queries and k results: "bf16x3", "bf16-few", "bf16" or "dense" (_route_name)."""
+		excl, _ = _exclusion_arg(exclude, Q, self.m, k, self._Et.device)
+		return _route_name(self, Q, k, excl)
 
 	def rank_route(self, t):
 		"""The route rank_of() takes for t targets per query: "bf16" (fused, S_hat never written) or "dense"."""
@@ -614,7 +642,7 @@ class CURRowIndex(object):
 		embeddings -- Rt fp32 [m x kq], row i = item i's scores under the kq anchor queries -- behind the same three routes as E^T."""
 		if self._adaptive is None:
 			R = self.R if self.R.dtype == torch.float32 else ops.convert(self.R, torch.float32)
-			self._adaptive = _ItemOperand(R.t().contiguous(), self.compute_dtype)   # (a copy, no arithmetic)
+			self._adaptive = _ItemOperand(R.t().contiguous(), self.compute_dtype, self.small_batch)   # (a copy, no arithmetic)
 		return self._adaptive
 
 	def eval_topk(self, X, exact_rows, k, k_retvr):

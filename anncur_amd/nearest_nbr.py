@@ -42,9 +42,13 @@ class FlatIPIndex:
 	Score ties: the fp32 route orders them by the smaller id; the bf16 route on the fused kernel by the smaller ROW of its descending-norm copy
 	(256 norm buckets, id order inside a bucket), so by the smaller id only among vectors of one norm bucket (tests/test_gpu_ivf_index_exact.py)."""
 
-	def __init__(self, d, dtype="fp32", device=None):
+	def __init__(self, d, dtype="fp32", device=None, small_batch=False):
+		"""small_batch: dtype "bf16" only -- searches of up to 64 queries take the small-batch route on an item-order packed copy (DESIGN 4.4h;
+		search_route names the route of a call; ties by the smaller id there)."""
 		self.d = d
 		self.dtype = dtype
+		self.small_batch = bool(small_batch)
+		self._Xp_items = None        # small_batch: packed bf16 copy in item order (built at the first such search)
 		self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
 		self.ntotal = 0
 		self._X = None
@@ -58,7 +62,7 @@ class FlatIPIndex:
 		assert x.dim() == 2 and x.shape[1] == self.d, f"expected [n, {self.d}] embeddings"
 		self._X = x if self._X is None else torch.cat([self._X, x], dim=0)
 		self.ntotal = self._X.shape[0]
-		self._Xp = self._split = self._rank_operand = None
+		self._Xp = self._Xp_items = self._split = self._rank_operand = None
 
 	def train(self, embeds):  # FAISS API compatibility (flat index needs no training)
 		return None
@@ -78,7 +82,11 @@ class FlatIPIndex:
 				self._split = _SplitOperands.build(self._X)
 			if self._split.takes(q.shape[0], self.ntotal, k_eff, excl):
 				return _faiss_pad(*self._split.topk(q, self._X, k_eff, excl), q.shape[0], k, k_eff)
-		if self.dtype == "bf16" and kp is not None and ops.fused_supported(q.shape[0], self.ntotal, kp, kc):
+		if self._few_takes(q.shape[0], kp, kc):
+			if self._Xp_items is None:
+				self._Xp_items = ops.pack_bf16(self._X, kp, row_multiple=32)
+			v, i = ops.score_topk_few(ops.pack_bf16(q, kp), self._Xp_items, self.ntotal, kc)
+		elif self.dtype == "bf16" and kp is not None and ops.fused_supported(q.shape[0], self.ntotal, kp, kc):
 			if self._Xp is None:
 				from .cur import _norm_sorted_pack
 				self._Xp, self._ids = _norm_sorted_pack(self._X, kp)   # largest-norm vectors first: the likeliest maximum inner products
@@ -87,6 +95,27 @@ class FlatIPIndex:
 			v, i = ops.score_topk_dense(q, self._X, kc)
 		v, i = _filtered(ops.TopK(v, i), excl, k_eff)
 		return _faiss_pad(v, i, q.shape[0], k, k_eff)
+
+	def _few_takes(self, nq, kp, kc):
+		return (self.small_batch and self.dtype == "bf16" and kp is not None and kc <= min(self.ntotal, ops._lib.MAX_TOPK)
+				and ops.score_topk_few_ok(nq, self.ntotal, kp, kc))
+
+	def search_route(self, nq, k, exclude=None):
+		"""The route search() takes for nq queries: "bf16x3", "bf16-few" (small_batch=True, nq <= 64), "bf16" (fused sweep) or "dense"."""
+		from .cur import _exclusion_arg
+		k_eff, kp = min(k, self.ntotal), ops.padded_k(self.d)
+		excl, kc = _exclusion_arg(exclude, nq, self.ntotal, k_eff, self.device)
+		if self.dtype == "bf16x3":
+			if self._split is None:
+				from .cur import _SplitOperands
+				self._split = _SplitOperands.build(self._X)
+			if self._split.takes(nq, self.ntotal, k_eff, excl):
+				return "bf16x3"
+		if self._few_takes(nq, kp, kc):
+			return "bf16-few"
+		if self.dtype == "bf16" and kp is not None and ops.fused_supported(nq, self.ntotal, kp, kc):
+			return "bf16"
+		return "dense"
 
 	def _rank_op(self):
 		if self._rank_operand is None:

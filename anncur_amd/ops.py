@@ -756,6 +756,117 @@ def score_topk_fused(Xp, Etp, I, k, return_fallbacks=False, workspace=None, lead
 	return TopK(val, idx)
 
 
+# ------------------------------------------------------------------ small-batch route (csrc/few.hip)
+FEW_MAX_Q = 64              # ANNCUR_FEW_MAX_Q
+FEW_STAGE_BYTES = 65536     # ANNCUR_FEW_STAGE_BYTES
+_FEW_PLAN = ("tiles", "workgroups", "waves_per_workgroup", "tiles_per_wave_min", "tiles_per_wave_max", "query_subtiles", "groups", "cand_cap",
+			 "pitch", "groups_per_wave", "gmax_offset", "scores_offset")
+FewStats = namedtuple("FewStats", ["groups_read", "n_cand", "fallback"])
+
+
+def _few_check(what, Q, I, Kp, k=None):
+	"""Host-side limits of the small-batch route; a ValueError names the one that is broken."""
+	if not 1 <= Q <= FEW_MAX_Q:
+		raise ValueError(f"{what}: Q = {Q} queries, the small-batch route takes 1..{FEW_MAX_Q} per call")
+	if not _kp_ok(Kp):
+		raise ValueError(f"{what}: Kp = {Kp} is not a padded inner dimension (64, 128, 256, 512 or a multiple of 128 up to {_KP_WIDE_MAX}: padded_k)")
+	stage = 16 * -(-Q // 16) * Kp * 2
+	if stage > FEW_STAGE_BYTES:
+		raise ValueError(f"{what}: {-(-Q // 16) * 16} staged query rows of Kp = {Kp} take {stage} bytes, above the LDS stage of {FEW_STAGE_BYTES}")
+	if not 1 <= I < (1 << 31) - 1:
+		raise ValueError(f"{what}: I = {I} items is outside 1..2^31 - 2")
+	if k is not None:
+		limit = min(I, _lib.MAX_TOPK)
+		if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= limit:
+			raise ValueError(f"{what}: k = {k} outside 1..min(I, ANNCUR_MAX_TOPK) = min({I}, {_lib.MAX_TOPK}) = {limit}")
+
+
+def _few_operands(what, Xp, Etp, I):
+	"""Shape, dtype and pitch checks of the packed operands, before either has to be on the GPU -> (Q, Kp, ldx)."""
+	if not (torch.is_tensor(Xp) and torch.is_tensor(Etp)) or Xp.dim() != 2 or Etp.dim() != 2:
+		raise ValueError(f"{what}: Xp and Etp must be 2-D tensors")
+	if Xp.dtype != torch.bfloat16 or Etp.dtype != torch.bfloat16:
+		raise TypeError(f"{what} takes bf16 operands")
+	Q, Kp = Xp.shape
+	if Etp.shape[1] != Kp or not Etp.is_contiguous() or Etp.shape[0] < -(-I // 32) * 32:
+		raise ValueError(f"{what}: Et must be packed [ceil(I/32)*32 x Kp]")
+	if Kp > 1 and Xp.stride(1) != 1:
+		raise ValueError(f"{what}: the rows of Xp must be contiguous")
+	ldx = Xp.stride(0) if Q > 1 else max(Kp, 1)
+	if ldx < Kp or ldx % 8 != 0:
+		raise ValueError(f"{what}: ldx = {ldx}, the pitch of Xp must be >= Kp = {Kp} and a multiple of 8 (ldx % 8 == 0)")
+	return Q, Kp, ldx
+
+
+def score_topk_few_ok(Q, I, Kp, k):
+	"""Does the small-batch route take the shape?  (host query, no GPU needed)"""
+	return _kp_ok(Kp) and bool(_lib.load().anncur_score_topk_few_supported(Q, I, Kp, k))
+
+
+def few_plan(Q, I, Kp, k):
+	"""The plan of score_topk_few (host query): tiles of 16 items, workgroups, waves per workgroup, fewest / most tiles of a wave, 16-query
+	sub-tiles, groups of 64 items per query, cand_cap (candidates the select buffers before it falls back to a full scan), the pitch of the
+	score scratch in floats, groups per wave, byte offsets of the group maxima and the scores in the workspace."""
+	_few_check("few_plan", Q, I, Kp, k)
+	out = (ctypes.c_int32 * len(_FEW_PLAN))()
+	check(_lib.load().anncur_score_topk_few_plan(Q, I, Kp, k, out, len(_FEW_PLAN)), "score_topk_few_plan")
+	w = dict(zip(_FEW_PLAN, (int(x) for x in out)))
+	w["pitch"] *= 32
+	w["gmax_offset"] *= 256
+	w["scores_offset"] *= 256
+	return w
+
+
+def few_workspace(Q, I, Kp, k, device):
+	"""A private workspace for score_topk_few (256-byte aligned uint8 tensor), as fused_workspace."""
+	_few_check("few_workspace", Q, I, Kp, k)
+	nbytes = _lib.load().anncur_score_topk_few_workspace_bytes(Q, I, Kp, k)
+	buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+	off = (-buf.data_ptr()) % 256
+	return buf[off:off + nbytes]
+
+
+@_on_device
+def score_topk_few(Xp, Etp, I, k, workspace=None, return_stats=False):
+	"""Exact top-k of S_hat = X . E for 1..64 queries in two launches (csrc/few.hip): Xp [Q x Kp] bf16 (rows may be pitched, pitch a
+	multiple of 8), Etp [ceil32(I) x Kp] bf16 packed in ITEM order (pack_bf16(..., row_multiple=32)).  Same result as score_topk_fused on the
+	same operands, value bits included at Kp <= 256.  workspace: from few_workspace(); default = the grow-only buffer of the fused route.
+	return_stats: also FewStats of int32 [Q] device tensors -- groups of 64 items the select read, candidates at or above its threshold,
+	1 where it fell back to scanning the whole row.  Limits are checked on the host first (ValueError names the one that is broken)."""
+	Q, Kp, ldx = _few_operands("score_topk_few", Xp, Etp, I)
+	_few_check("score_topk_few", Q, I, Kp, k)
+	_dev(Xp, Etp)
+	lib = _lib.load()
+	nbytes = lib.anncur_score_topk_few_workspace_bytes(Q, I, Kp, k)
+	if workspace is None:
+		ws = _Workspace.get(nbytes, Xp.device)
+	else:
+		ws = workspace
+		if ws.numel() < nbytes or ws.data_ptr() % 256 != 0 or ws.device != Xp.device:
+			raise ValueError("score_topk_few: workspace too small, misaligned or on another device (use few_workspace())")
+	val = torch.empty((Q, k), dtype=torch.float32, device=Xp.device)
+	idx = torch.empty((Q, k), dtype=torch.int32, device=Xp.device)
+	check(lib.anncur_score_topk_few(_p(Xp), ldx, _p(Etp), Kp, Q, I, Kp, int(k), _p(val), _p(idx), _p(ws), nbytes, _stream()), "score_topk_few")
+	if return_stats:
+		h = ws[:16 * Q].view(torch.int32).view(Q, 4)
+		return TopK(val, idx), FewStats(h[:, 0], h[:, 1], h[:, 2])
+	return TopK(val, idx)
+
+
+@_on_device
+def score_rows_few(Xp, Etp, I):
+	"""Launch 1 of score_topk_few alone ("get_complete_row for a few queries on the bf16 operands") -> (S [Q x I] fp32, a view of rows
+	ceil32(I) apart, GM [Q x ceil(I / 64)] fp32: the maximum of every 64 consecutive items, NaN skipped, NaN for an all-NaN group)."""
+	Q, Kp, ldx = _few_operands("score_rows_few", Xp, Etp, I)
+	_few_check("score_rows_few", Q, I, Kp)
+	_dev(Xp, Etp)
+	pitch, G = -(-I // 32) * 32, -(-I // 64)
+	S = torch.empty((Q, pitch), dtype=torch.float32, device=Xp.device)
+	GM = torch.empty((Q, G), dtype=torch.float32, device=Xp.device)
+	check(_lib.load().anncur_score_rows_few(_p(Xp), ldx, _p(Etp), Kp, Q, I, Kp, _p(S), pitch, _p(GM), G, _stream()), "score_rows_few")
+	return S[:, :I], GM
+
+
 _aux_streams = {}
 
 

@@ -249,6 +249,43 @@ int anncur_score_topk_ex(const void *X, int64_t ldx, const void *Et, int64_t lde
                          void *workspace, size_t workspace_bytes,
                          int32_t flags, const int32_t *item_ids, void *stream);
 
+/* a6+a7 for a FEW queries (1 <= Q <= 64): the small-batch route (csrc/few.hip) ---------------------------------------
+ * Same operands and the same result as anncur_score_topk -- the exact top-k of S_hat = X . E, score descending, ties by ascending row,
+ * NaN never selected, +-inf ordinary candidates, (-inf, -1) pads -- in TWO launches: few_score_kernel streams Et once (item fragments
+ * straight from global memory into v_mfma_f32_16x16x32_bf16, k ascending into one accumulator: at Kp <= 256 a score has the bits of
+ * anncur_score_topk's) and writes S_hat [Q x ceil32(I)] fp32 plus one maximum per 64 consecutive items into the workspace;
+ * few_select_kernel takes the k-th largest group maximum as threshold, reads only the groups that reach it, and selects.  A query with
+ * more than cand_cap candidates at or above its threshold (heavy ties) is scanned in full by the same workgroup: always exact.
+ * Et is in ITEM order (no leading-sample hint, no id map).  Rows >= Q of X are never read. */
+#define ANNCUR_FEW_MAX_Q 64             /* queries per call */
+#define ANNCUR_FEW_STAGE_BYTES 65536    /* LDS stage of the queries: 16 ceil(Q / 16) x Kp x 2 bytes must fit (Q <= 16: Kp <= 2048; Q > 48: Kp <= 512) */
+#define ANNCUR_FEW_PLAN_WORDS 12
+/*   CURApprox.topk_in_row, few queries          eval/matrix_approx_zeshel.py:121-126 ; models/nearest_nbr.py:36-38
+ * 1 when 1 <= Q <= ANNCUR_FEW_MAX_Q, Kp in {64,128,256,512} or a multiple of 128 up to 4096, the queries fit the LDS stage,
+ * 1 <= k <= min(I, ANNCUR_MAX_TOPK) and I < 2^31 - 1; 0 otherwise. */
+int anncur_score_topk_few_supported(int64_t Q, int64_t I, int32_t Kp, int32_t k);
+/*   eval/matrix_approx_zeshel.py:121-126 ; models/nearest_nbr.py:36-38
+ * Header (1 KiB: per query {groups_read, n_cand, fallback, 0} as uint32), the group maxima and the score scratch; 0 = unsupported. */
+size_t anncur_score_topk_few_workspace_bytes(int64_t Q, int64_t I, int32_t Kp, int32_t k);
+/*   eval/matrix_approx_zeshel.py:121-126 ; models/nearest_nbr.py:36-38
+ * X [Q x Kp] bf16 (pitch ldx >= Kp, a multiple of 8), Et [ceil32(I) x Kp] bf16 packed (lde == Kp), both 16-byte aligned; out_val float[Q x k],
+ * out_idx int32[Q x k]; workspace 256-byte aligned, nothing in it pre-filled by the caller (the kernels write the header themselves).
+ * A shape outside anncur_score_topk_few_supported is ANNCUR_E_UNSUPPORTED (k outside its range: ANNCUR_E_INVALID), a missing, short or
+ * misaligned workspace ANNCUR_E_WORKSPACE; nothing is written then. */
+int anncur_score_topk_few(const void *X, int64_t ldx, const void *Et, int64_t lde, int64_t Q, int64_t I, int32_t Kp, int32_t k,
+                          float *out_val, int32_t *out_idx, void *workspace, size_t workspace_bytes, void *stream);
+/*   CURApprox.get_complete_row, few queries     eval/matrix_approx_zeshel.py:118-126 ; models/nearest_nbr.py:36-38
+ * Launch 1 alone, on the bf16 operands: S[q, i] = <X[q], Et[i]> for q < Q, i < I (pitch lds >= I, a multiple of 4, S 16-byte aligned) and
+ * GM[q, g] = max of S[q, 64 g .. 64 g + 63] over the items < I (pitch ldg >= ceil(I / 64)); a NaN is skipped, an all-NaN group gives NaN.
+ * Nothing else of S or GM is written. */
+int anncur_score_rows_few(const void *X, int64_t ldx, const void *Et, int64_t lde, int64_t Q, int64_t I, int32_t Kp, float *S, int64_t lds,
+                          float *GM, int64_t ldg, void *stream);
+/*   eval/matrix_approx_zeshel.py:121-126 ; models/nearest_nbr.py:36-38
+ * The plan of a call (host only, no device): out[0..min(n_out, ANNCUR_FEW_PLAN_WORDS)) = {16-item tiles, workgroups, waves per workgroup,
+ * fewest / most tiles of a wave that has any, 16-query sub-tiles, groups per query, cand_cap, scratch pitch / 32, groups per wave,
+ * byte offsets / 256 of the group maxima and of the score scratch in the workspace}.  ANNCUR_E_UNSUPPORTED outside the route. */
+int anncur_score_topk_few_plan(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t *out, int32_t n_out);
+
 /* a6+a7 at fp32 parity on the bf16 matrix cores: the split-bf16 ("bf16x3") route -------------------------------------------------
  *   CURApprox.get_complete_row + topk_in_row on FloatTensors      eval/matrix_approx_zeshel.py:118,126
  *   faiss IndexFlatIP.add / .search on float32 vectors            models/nearest_nbr.py:36-38
