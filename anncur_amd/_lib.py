@@ -26,6 +26,8 @@ SVD_MAX_G = 2048      # ANNCUR_SVD_MAX_G
 SVD_MAX_L = 8192      # ANNCUR_SVD_MAX_L
 SUMSQ_PARTIALS = 1024 # ANNCUR_SUMSQ_PARTIALS
 RANK_MAX_T = 1024     # ANNCUR_RANK_MAX_T
+SPARSE_WINDOW = 2048  # ANNCUR_SPARSE_WINDOW
+SPARSE_MAX_QNNZ = 1024  # ANNCUR_SPARSE_MAX_QNNZ
 
 _p32 = POINTER(c_int32)
 
@@ -71,6 +73,11 @@ SIGNATURES = {
 									  c_void_p, c_size_t, c_void_p]),
 	"anncur_score_rows_few": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
 	"anncur_score_topk_few_plan": (c_int, [c_int64, c_int64, c_int32, c_int32, _p32, c_int32]),
+	"anncur_sparse_score_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+	"anncur_sparse_score_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p,
+										 c_void_p, c_size_t, c_void_p]),
+	"anncur_sparse_score_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+	"anncur_sparse_plan": (c_int, [c_int64, c_int64, _p32, c_int32]),
 	"anncur_pack_split_bf16": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p]),
 	"anncur_rescore_topk": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int64, c_int64, c_int32,
 									c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -32,6 +32,38 @@ def load_score_pickle(path):
 	return d
 
 
+def load_embeds(path):
+	"""Precomputed embeddings of bienc / tfidf: .npy -> a dense NumPy array; .npz in the layout of scipy.sparse.save_npz (keys indptr, indices,
+	data, shape, format = csr) -> ops.SparseCSR of host tensors, read with numpy.load alone and checked for canonical form."""
+	if not str(path).endswith(".npz"):
+		return np.load(path)
+	with np.load(path, allow_pickle=False) as z:
+		missing = [key for key in ("indptr", "indices", "data", "shape") if key not in z.files]
+		if missing:
+			raise KeyError(f"{path}: not a scipy.sparse.save_npz file (missing {', '.join(missing)})")
+		fmt = z["format"].item() if "format" in z.files else b"csr"
+		fmt = fmt.decode("ascii") if isinstance(fmt, bytes) else str(fmt)
+		if fmt != "csr":
+			raise ValueError(f"{path}: sparse format {fmt}, CSR is required (tocsr() before save_npz)")
+		indptr, indices, data, shape = z["indptr"], z["indices"], z["data"], tuple(int(s) for s in z["shape"])
+	if indptr.dtype.kind not in "iu" or indices.dtype.kind not in "iu" or data.dtype.kind != "f":
+		raise TypeError(f"{path}: indptr / indices must be integer arrays and data a floating-point array")
+	return ops.sparse_csr(ops.SparseCSR(torch.from_numpy(indptr.astype(np.int64)), torch.from_numpy(indices.astype(np.int32)),
+										torch.from_numpy(data.astype(np.float32)), shape[0], shape[1]), shape[1], str(path))
+
+
+def take_embed_rows(embeds, rows):
+	"""embeds[rows] for a dense array or an ops.SparseCSR on the host (tfidf: the test mentions of all mentions' embeddings, splits.py:378)."""
+	rows = np.asarray(rows, dtype=np.int64)
+	if not isinstance(embeds, ops.SparseCSR):
+		return embeds[rows]
+	indptr = embeds.indptr.cpu().numpy()
+	counts = (indptr[1:] - indptr[:-1])[rows]
+	new_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+	src = torch.from_numpy(np.repeat(indptr[rows] - new_ptr[:-1], counts) + np.arange(new_ptr[-1], dtype=np.int64))
+	return ops.SparseCSR(torch.from_numpy(new_ptr), embeds.indices.cpu()[src], embeds.data.cpu()[src], rows.size, embeds.n_cols)
+
+
 def to_device_matrix(scores, device, dtype="fp32"):
 	t = scores if torch.is_tensor(scores) else torch.as_tensor(np.asarray(scores))
 	t = t.to(device=device, dtype=torch.float32)
@@ -414,15 +446,27 @@ def run_eval_method_cur(A_test_dev, A_train_dev, seed, grids, compute_dtype=None
 
 def run_eval_method_embeds(A_test_dev, mention_embeds, label_embeds, n_train, grids):
 	"""bienc / tfidf / fixed_anc_ent given PRECOMPUTED embeddings: scores = mention_embeds @ label_embeds.T (splits.py:283,324,383);
-	one result is repeated for every anchor count, as the reference does (splits.py:412-418)."""
-	n_ent = label_embeds.shape[0]
+	one result is repeated for every anchor count, as the reference does (splits.py:412-418).
+	Sparse embeddings (tfidf: CSR objects or ops.SparseCSR, see ops.is_sparse_arg) are retrieved through the term-major index instead of
+	being densified; if only one side is sparse, the dense side is sparsified."""
+	sparse = ops.is_sparse_arg(mention_embeds) or ops.is_sparse_arg(label_embeds)
+	if sparse:
+		dims = [int(e.shape[1]) if hasattr(e, "shape") else getattr(e, "n_cols", None) for e in (label_embeds, mention_embeds)]
+		mention_embeds, label_embeds = (e if ops.is_sparse_arg(e) else ops.sparse_from_dense(e) for e in (mention_embeds, label_embeds))
+		label_embeds = ops.sparse_csr(label_embeds, dims[0] if dims[0] is not None else dims[1], "label_embeds")   # (a bare triple takes the other side's width)
+		n_ent = label_embeds.n_rows
+	else:
+		n_ent = label_embeds.shape[0]
 	top_k_vals, retr_vals, anc_vals = grids["top_k_vals"], grids["top_k_retr_vals"], grids["n_ent_anchors_vals"]
 	kr_max = max([kr for kr in retr_vals if kr <= min(n_ent, ops._lib.MAX_TOPK)] or [0])
 	k_max = max([k for k in top_k_vals if k <= kr_max] or [0])
 	if kr_max == 0:
 		return {}
 	exact = ops.rowwise_topk(A_test_dev, k_max)
-	approx = ops.score_topk_dense(mention_embeds, label_embeds, kr_max)
+	if sparse:
+		approx = ops.sparse_score_topk(mention_embeds, ops._postings_of(label_embeds, A_test_dev.device), kr_max)
+	else:
+		approx = ops.score_topk_dense(mention_embeds, label_embeds, kr_max)
 	res = defaultdict(lambda: defaultdict(dict))
 	for (k, kr), metrics in _sweep_cells(A_test_dev, approx.indices, exact, top_k_vals, retr_vals, n_ent).items():
 		for n_anc in anc_vals:

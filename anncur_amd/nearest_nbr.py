@@ -142,6 +142,62 @@ class FlatIPIndex:
 	rank_of = rank   # the name CURRowIndex gives the same question (its `rank` is the anchor block's numerical rank)
 
 
+class SparseIPIndex:
+	"""FlatIPIndex for SPARSE vectors (TF-IDF: the reference densifies them, utils/data_process.py:373-397): exact maximum-inner-product
+	search through a term-major index on the device (ops.sparse_postings / ops.sparse_score_topk).  add() takes CSR objects
+	(anything with .indptr / .indices / .data / .shape, scipy.sparse.csr_matrix among them) or (indptr, indices, data) triples in
+	canonical form; search() also takes a dense [nq x d] array, which is sparsified on the way in.  Scores are the ascending-term fp32
+	chain; ties go to the smaller id."""
+
+	def __init__(self, d, dtype="fp32", device=None):
+		if dtype != "fp32":
+			raise ValueError(f"dtype = {dtype} not supported")
+		self.d, self.dtype = int(d), dtype
+		self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+		self.ntotal = 0
+		self.nprobe = 1        # accepted for FAISS API compatibility
+		self._parts = []       # SparseCSR pieces in insertion order (where the caller's arrays live)
+		self._postings = None  # rebuilt at the first search after an add
+
+	def add(self, csr):
+		part = ops.sparse_csr(csr, self.d, "SparseIPIndex.add")
+		self._parts.append(part)
+		self.ntotal += part.n_rows
+		self._postings = None
+
+	def train(self, embeds):  # FAISS API compatibility
+		return None
+
+	def _index(self):
+		if self._postings is None:
+			assert self._parts, "index is empty"
+			parts = [ops.SparseCSR(*(a.to(self.device) for a in p[:3]), p.n_rows, p.n_cols) for p in self._parts]
+			if len(parts) > 1:
+				offs = np.cumsum([0] + [int(p.indices.numel()) for p in parts])
+				indptr = torch.cat([parts[0].indptr] + [p.indptr[1:] + int(o) for p, o in zip(parts[1:], offs[1:])])
+				merged = ops.SparseCSR(indptr, torch.cat([p.indices for p in parts]), torch.cat([p.data for p in parts]), self.ntotal, self.d)
+				self._parts = parts = [merged]
+			self._postings = ops.sparse_postings(*parts[0][:3], self.ntotal, self.d, device=self.device)
+		return self._postings
+
+	def _queries(self, x):
+		if ops.is_sparse_arg(x):
+			return x
+		q = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32))
+		assert q.dim() == 2 and q.shape[1] == self.d, f"expected [nq, {self.d}] queries"
+		return ops.sparse_from_dense(q.to(self.device))
+
+	def search(self, x, k, exclude=None):
+		"""exclude: as FlatIPIndex.search.  -> (D float32 [nq x k], I int64 [nq x k]) NumPy arrays, (-FLT_MAX, -1) where k > ntotal."""
+		post = self._index()
+		k_eff = min(k, self.ntotal)
+		v, i = ops.sparse_score_topk(self._queries(x), post, k_eff, exclude=exclude)
+		return _faiss_pad(v, i, v.shape[0], k, k_eff)
+
+	def search_route(self, nq, k, exclude=None):
+		return "sparse"
+
+
 class IVFFlatIPIndex:
 	"""faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT) on the GPU: train (k-means coarse quantiser) / add
 	(inverted lists) / search (exact inner products inside the nprobe best lists).  Restated from FAISS' published algorithm and
@@ -285,10 +341,34 @@ class IVFFlatIPIndex:
 		return _faiss_pad(v, i, q.shape[0], k, min(k, ops._lib.MAX_TOPK))
 
 
-def build_flat_or_ivff_index(embeds, force_exact_search, probe_mult_factor=1, dtype="fp32", device=None):
+def _build_sparse_index(embeds, force_exact_search, dtype, device, n_terms):
+	if hasattr(embeds, "shape"):
+		d = int(embeds.shape[1])
+	elif isinstance(embeds, ops.SparseCSR):
+		d = embeds.n_cols
+	elif n_terms is not None:
+		d = int(n_terms)
+	else:
+		ids = embeds[1]
+		d = int(ids.max()) + 1 if len(ids) else 0
+	index = SparseIPIndex(d, dtype=dtype, device=device)
+	LOGGER.info(f"Beginning indexing given {len(embeds.indptr if hasattr(embeds, 'indptr') else embeds[0]) - 1} sparse embeddings")
+	index.add(embeds)
+	if index.ntotal > 11000 and not force_exact_search:
+		LOGGER.info(f"{index.ntotal} sparse vectors: the sparse index has no IVF form, the search stays exact")
+	LOGGER.info("Finished indexing given embeddings")
+	return index
+
+
+def build_flat_or_ivff_index(embeds, force_exact_search, probe_mult_factor=1, dtype="fp32", device=None, n_terms=None):
 	"""models/nearest_nbr.py:24-55.  dtype: "fp32", "bf16", or "bf16x3" -- the flat index' fp32-parity route on the bf16 matrix cores.
 	The IVF lists stay fp32 / bf16: above 11 000 vectors without force_exact_search, dtype="bf16x3" raises the ValueError IVFFlatIPIndex
-	raises for a dtype it does not know."""
+	raises for a dtype it does not know.
+	A CSR object (.indptr / .indices / .data / .shape) or an (indptr, indices, data) triple -- ops.is_sparse_arg -- gives a SparseIPIndex:
+	always exact, whatever the number of vectors; a dtype other than "fp32" is that same ValueError.  n_terms: the dimension of a triple
+	(default: its largest term id + 1)."""
+	if ops.is_sparse_arg(embeds):
+		return _build_sparse_index(embeds, force_exact_search, dtype, device, n_terms)
 	LOGGER.info(f"Beginning indexing given {len(embeds)} embeddings")
 	if type(embeds) is not np.ndarray:
 		embeds = embeds.detach().cpu().numpy() if torch.is_tensor(embeds) else np.array(embeds)

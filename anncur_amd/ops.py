@@ -1080,6 +1080,255 @@ def score_topk_dense(X, Et, k, max_bytes=2 << 30):
 	return TopK(val, idx)
 
 
+# ------------------------------------------------------------------ sparse inner-product search
+SPARSE_WINDOW = _lib.SPARSE_WINDOW        # ANNCUR_SPARSE_WINDOW
+SPARSE_MAX_QNNZ = _lib.SPARSE_MAX_QNNZ    # ANNCUR_SPARSE_MAX_QNNZ
+SPARSE_MAX_Q_PER_CALL = 1 << 20           # queries per library call (the launch is one workgroup per query at least)
+_SPARSE_PLAN = ("windows", "windows_per_wave", "spans", "workgroups_per_query", "workgroups", "waves_per_workgroup", "lds_bytes", "pitch", "groups", "max_qnnz")
+SparsePostings = namedtuple("SparsePostings", ["term_ptr", "post_item", "post_val", "n_items", "n_terms"])
+SparseCSR = namedtuple("SparseCSR", ["indptr", "indices", "data", "n_rows", "n_cols"])
+
+
+def is_sparse_arg(x):
+	"""Is x a CSR operand: an object with .indptr / .indices / .data / .shape (scipy.sparse.csr_matrix is one; scipy is never imported),
+	a SparseCSR, or an (indptr, indices, data) triple of 1-D tensors / arrays?"""
+	if isinstance(x, SparseCSR) or all(hasattr(x, a) for a in ("indptr", "indices", "data", "shape")):
+		return True
+	if not (isinstance(x, (tuple, list)) and len(x) == 3 and all(torch.is_tensor(a) or isinstance(a, np.ndarray) for a in x) and all(a.ndim == 1 for a in x)):
+		return False
+	kinds = ["f" if (a.dtype.is_floating_point if torch.is_tensor(a) else a.dtype.kind == "f") else "i" for a in x]
+	return kinds == ["i", "i", "f"]   # (three float rows are a dense matrix)
+
+
+def _sparse_tensor(a, what, name):
+	if torch.is_tensor(a):
+		return a.detach()
+	a = np.asarray(a)
+	if a.dtype == object:
+		raise TypeError(f"{what}: {name} is not a numeric array")
+	return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def sparse_csr(x, n_cols=None, what="sparse", max_row_nnz=None):
+	"""A CSR operand, checked where it lives (host arrays on the host, before anything touches the device) -> SparseCSR of tensors on that
+	same device: indptr int64 [n + 1], indices int32, data fp32.
+	x: an (indptr, indices, data) triple -- dtypes must be exactly those, TypeError otherwise; n_cols must be given -- or an object with
+	.indptr / .indices / .data / .shape, whose arrays are converted (integer index arrays to int64 / int32, floating data to fp32).
+	ValueError: indptr not starting at 0, decreasing or not ending at nnz; a term id outside [0, n_cols) (one reduction); a row whose term
+	ids are not strictly ascending -- the first such row is named; the remedy is sort_indices() / sum_duplicates() --; n >= 2^31 - 1,
+	n_cols >= 2^31, nnz >= 2^31; max_row_nnz: a row with more stored terms (queries: ANNCUR_SPARSE_MAX_QNNZ)."""
+	if isinstance(x, SparseCSR):
+		indptr, indices, data, shape, strict = x.indptr, x.indices, x.data, (x.n_rows, x.n_cols), True
+	elif isinstance(x, (tuple, list)):
+		if len(x) != 3:
+			raise ValueError(f"{what}: a CSR operand is an (indptr, indices, data) triple or an object with .indptr / .indices / .data / .shape")
+		(indptr, indices, data), shape, strict = x, None, True
+	else:
+		try:
+			indptr, indices, data, shape, strict = x.indptr, x.indices, x.data, tuple(int(s) for s in x.shape), False
+		except AttributeError:
+			raise TypeError(f"{what}: expected a CSR operand (an (indptr, indices, data) triple or an object with .indptr / .indices / .data / .shape), "
+							f"got {type(x).__name__}") from None
+		fmt = getattr(x, "format", "csr")
+		if fmt != "csr":
+			raise TypeError(f"{what}: the sparse matrix is in {fmt} format, CSR is required (tocsr())")
+	indptr, indices, data = (_sparse_tensor(a, what, n) for a, n in ((indptr, "indptr"), (indices, "indices"), (data, "data")))
+	if not strict:
+		for a, n in ((indptr, "indptr"), (indices, "indices")):
+			if a.dtype not in (torch.int32, torch.int64):
+				raise TypeError(f"{what}: {n} must be an int32 or int64 array (got {a.dtype})")
+		if not data.dtype.is_floating_point:
+			raise TypeError(f"{what}: data must be a floating-point array (got {data.dtype})")
+		indptr, data = indptr.to(torch.int64), data.to(torch.float32)
+	if indptr.dtype != torch.int64 or indices.dtype not in (torch.int32, torch.int64) or (strict and indices.dtype != torch.int32) or data.dtype != torch.float32:
+		raise TypeError(f"{what}: a CSR triple is (indptr int64, indices int32, data float32), got ({indptr.dtype}, {indices.dtype}, {data.dtype})")
+	if indptr.dim() != 1 or indices.dim() != 1 or data.dim() != 1 or indptr.numel() < 1:
+		raise ValueError(f"{what}: indptr [n + 1], indices [nnz] and data [nnz] must be 1-D arrays")
+	n, nnz = indptr.numel() - 1, indices.numel()
+	if shape is not None:
+		if len(shape) != 2 or shape[0] != n:
+			raise ValueError(f"{what}: shape {tuple(shape)} does not go with an indptr of {n + 1} entries")
+		if n_cols is not None and shape[1] != n_cols:
+			raise ValueError(f"{what}: the matrix has {shape[1]} columns, expected {n_cols}")
+		n_cols = shape[1]
+	if n_cols is None:
+		raise ValueError(f"{what}: the number of columns (terms) of a CSR triple must be given")
+	n_cols = int(n_cols)
+	if data.numel() != nnz:
+		raise ValueError(f"{what}: indices holds {nnz} entries, data {data.numel()}")
+	if n >= (1 << 31) - 1:
+		raise ValueError(f"{what}: n = {n} rows, the limit is n < 2^31 - 1")
+	if not 0 <= n_cols < (1 << 31):
+		raise ValueError(f"{what}: V = {n_cols} terms, the limit is V < 2^31")
+	if nnz >= (1 << 31):
+		raise ValueError(f"{what}: nnz = {nnz} stored entries, the limit is nnz < 2^31")
+	first, last = int(indptr[0]), int(indptr[-1])
+	if first != 0 or last != nnz:
+		raise ValueError(f"{what}: indptr must start at 0 and end at nnz = {nnz} (got indptr[0] = {first}, indptr[-1] = {last})")
+	counts = indptr[1:] - indptr[:-1]
+	if n and int(counts.min()) < 0:
+		raise ValueError(f"{what}: indptr decreases at row {int(torch.nonzero(counts < 0)[0])}")
+	if nnz:
+		lo, hi = (int(v) for v in torch.aminmax(indices))
+		if lo < 0 or hi >= n_cols:
+			raise ValueError(f"{what}: term id {lo if lo < 0 else hi} is outside [0, {n_cols})")
+	if indices.dtype != torch.int32:
+		indices = indices.to(torch.int32)
+	if nnz > 1:
+		ok = indices[1:] > indices[:-1]
+		starts = indptr[1:-1]
+		ok[starts[(starts > 0) & (starts < nnz)] - 1] = True      # the first entry of a row has no predecessor in its row
+		if not bool(ok.all()):
+			p = int(torch.nonzero(~ok)[0]) + 1
+			row = int(torch.searchsorted(indptr, torch.tensor([p], dtype=torch.int64, device=indptr.device), right=True)[0]) - 1
+			a, b = int(indices[p - 1]), int(indices[p])
+			raise ValueError(f"{what}: row {row} is not in canonical form: " + (f"duplicate term {b}" if a == b else f"unsorted, term {b} follows term {a}")
+							 + "; the term ids of a row must be strictly ascending (scipy: sort_indices() / sum_duplicates())")
+	if max_row_nnz is not None and n and int(counts.max()) > max_row_nnz:
+		row = int(torch.nonzero(counts > max_row_nnz)[0])
+		raise ValueError(f"{what}: row {row} stores {int(counts[row])} terms, above ANNCUR_SPARSE_MAX_QNNZ = {max_row_nnz} stored terms per query")
+	return SparseCSR(indptr.contiguous(), indices.contiguous(), data.contiguous(), n, n_cols)
+
+
+def sparse_from_dense(M):
+	"""Dense [n x V] floating array / tensor -> SparseCSR of its non-zero entries (row-major order is canonical form), on M's device."""
+	M = torch.as_tensor(np.ascontiguousarray(M, dtype=np.float32)) if not torch.is_tensor(M) else M.detach().to(torch.float32)
+	if M.dim() != 2:
+		raise ValueError("sparse_from_dense: expected a 2-D array")
+	nz = M != 0
+	indptr = torch.zeros(M.shape[0] + 1, dtype=torch.int64, device=M.device)
+	indptr[1:] = torch.cumsum(nz.sum(dim=1), dim=0)
+	rc = torch.nonzero(nz)
+	return SparseCSR(indptr, rc[:, 1].to(torch.int32).contiguous(), M[nz].contiguous(), M.shape[0], M.shape[1])
+
+
+def _sparse_k_check(what, k, n):
+	limit = min(n, _lib.MAX_TOPK)
+	if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= limit:
+		raise ValueError(f"{what}: k = {k} outside 1..min(n, ANNCUR_MAX_TOPK) = min({n}, {_lib.MAX_TOPK}) = {limit}")
+
+
+def sparse_postings(indptr, indices, data, n_items, n_terms, device=None):
+	"""The term-major (inverted) index of a CSR item matrix [n_items x n_terms] on the device: term_ptr int64 [V + 1], post_item int32 [nnz]
+	(ascending inside a term), post_val fp32 [nnz].  Canonical form and the limits are checked first (sparse_csr), where the arrays live.
+	The transposition is torch's stable sort by term id + bincount + cumsum on the device."""
+	csr = sparse_csr((indptr, indices, data), n_terms, "sparse_postings")
+	if csr.n_rows != n_items:
+		raise ValueError(f"sparse_postings: indptr has {csr.n_rows + 1} entries, expected n_items + 1 = {n_items + 1}")
+	if n_items < 1:
+		raise ValueError("sparse_postings: the index needs at least one item")
+	return _postings_of(csr, device)
+
+
+def _postings_of(csr, device=None):
+	if device is None:
+		device = csr.indptr.device if csr.indptr.is_cuda else torch.device("cuda", torch.cuda.current_device())
+	device = torch.device(device)
+	indptr, indices, data = (a.to(device) for a in csr[:3])
+	with torch.cuda.device(device):
+		counts = indptr[1:] - indptr[:-1]
+		rows = torch.repeat_interleave(torch.arange(csr.n_rows, dtype=torch.int32, device=device), counts)
+		order = torch.sort(indices, stable=True).indices
+		term_ptr = torch.zeros(csr.n_cols + 1, dtype=torch.int64, device=device)
+		if indices.numel():
+			term_ptr[1:] = torch.cumsum(torch.bincount(indices, minlength=csr.n_cols), dim=0)
+		return SparsePostings(term_ptr, rows[order].contiguous(), data[order].contiguous(), csr.n_rows, csr.n_cols)
+
+
+def _sparse_queries(what, queries, postings):
+	if not isinstance(postings, SparsePostings):
+		raise TypeError(f"{what}: postings must come from sparse_postings()")
+	return sparse_csr(queries, postings.n_terms, what, max_row_nnz=SPARSE_MAX_QNNZ)   # (an object's own .shape[1] must equal the index' terms)
+
+
+def sparse_plan(Q, I):
+	"""The plan of a sparse scoring launch (host query): windows of SPARSE_WINDOW items per query, windows per wave, spans (waves with work)
+	and workgroups per query, workgroups, waves per workgroup, LDS bytes per workgroup, the pitch of the score scratch in floats, groups of
+	64 items, ANNCUR_SPARSE_MAX_QNNZ."""
+	if not 1 <= Q or not 1 <= I < (1 << 31) - 1:
+		raise ValueError(f"sparse_plan: (Q = {Q}, I = {I}) is outside Q >= 1, 1 <= I < 2^31 - 1")
+	out = (ctypes.c_int32 * len(_SPARSE_PLAN))()
+	check(_lib.load().anncur_sparse_plan(Q, I, out, len(_SPARSE_PLAN)), "sparse_plan")
+	w = dict(zip(_SPARSE_PLAN, (int(x) for x in out)))
+	w["pitch"] *= 32
+	return w
+
+
+def sparse_workspace(Q, I, k, device):
+	"""A private workspace for sparse_score_topk (256-byte aligned uint8 tensor) that holds the score rows of Q queries."""
+	nbytes = _lib.load().anncur_sparse_score_topk_workspace_bytes(Q, I, k)
+	buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+	off = (-buf.data_ptr()) % 256
+	return buf[off:off + nbytes]
+
+
+def _sparse_args(csr, postings, q0, q1):
+	ip = csr.indptr[q0:q1 + 1]
+	return (_p(ip), _p(csr.indices) if csr.indices.numel() else None, _p(csr.data) if csr.data.numel() else None, q1 - q0, _p(postings.term_ptr),
+			_p(postings.post_item) if postings.post_item.numel() else None, _p(postings.post_val) if postings.post_val.numel() else None,
+			postings.n_terms, postings.n_items)
+
+
+def sparse_score_rows(queries, postings):
+	"""The scoring launch alone, for audits on small shapes -> (S [Q x I] fp32, a view of rows ceil32(I) apart, GM [Q x ceil(I / 64)] fp32:
+	the maximum of every 64 consecutive items).  S[q, i] is the ascending-term fp32 chain of include/anncur_hip.h."""
+	csr = _sparse_queries("sparse_score_rows", queries, postings)
+	dev = postings.term_ptr.device
+	_dev(postings.term_ptr, postings.post_item, postings.post_val)
+	csr = SparseCSR(*(a.to(dev) for a in csr[:3]), csr.n_rows, csr.n_cols)
+	Q, I = csr.n_rows, postings.n_items
+	pitch, G = -(-I // 32) * 32, -(-I // 64)
+	with torch.cuda.device(dev):
+		S = torch.empty((Q, pitch), dtype=torch.float32, device=dev)
+		GM = torch.empty((Q, G), dtype=torch.float32, device=dev)
+		for q0 in range(0, Q, SPARSE_MAX_Q_PER_CALL):
+			q1 = min(Q, q0 + SPARSE_MAX_Q_PER_CALL)
+			check(_lib.load().anncur_sparse_score_rows(*_sparse_args(csr, postings, q0, q1), _p(S[q0:q1]), pitch, _p(GM[q0:q1]), G, _stream()), "sparse_score_rows")
+	return S[:, :I], GM
+
+
+def sparse_score_topk(queries, postings, k, exclude=None, max_bytes=2 << 30, workspace=None):
+	"""Exact top-k of the sparse inner products: queries (a CSR object or triple, on the host or the device) against sparse_postings() ->
+	TopK(values f32 [Q x k], indices int32 [Q x k]), score descending, equal scores to the smaller item id, (-inf, -1) pads.  The score rows
+	of a chunk of queries go into the workspace (at most max_bytes, at least one query), then the exact scan.  exclude: as every other
+	route, k + the longest list candidates per query, then filter_topk.  workspace: a 256-byte aligned uint8 tensor for one chunk
+	(sparse_workspace); default = the grow-only buffer of the fused route."""
+	csr = _sparse_queries("sparse_score_topk", queries, postings)
+	Q, I = csr.n_rows, postings.n_items
+	_sparse_k_check("sparse_score_topk", k, I)
+	dev = postings.term_ptr.device
+	excl, kc = None, int(k)
+	if exclude is not None:
+		excl = exclusion(exclude, Q, I, dev)
+		if excl.e_max == 0:
+			excl = None
+		else:
+			kc = filtered_k(int(k), excl.e_max, I)
+	_dev(postings.term_ptr, postings.post_item, postings.post_val)
+	csr = SparseCSR(*(a.to(dev) for a in csr[:3]), csr.n_rows, csr.n_cols)
+	lib = _lib.load()
+	pitch = -(-I // 32) * 32
+	rows = max(1, min(Q, max_bytes // (4 * pitch), SPARSE_MAX_Q_PER_CALL))
+	with torch.cuda.device(dev):
+		val = torch.empty((Q, kc), dtype=torch.float32, device=dev)
+		idx = torch.empty((Q, kc), dtype=torch.int32, device=dev)
+		if Q:
+			nbytes = lib.anncur_sparse_score_topk_workspace_bytes(rows, I, kc)
+			if workspace is None:
+				ws = _Workspace.get(nbytes, dev)
+			else:
+				ws = workspace
+				if ws.numel() < nbytes or ws.data_ptr() % 256 != 0 or ws.device != dev:
+					raise ValueError(f"sparse_score_topk: workspace too small ({ws.numel()} of {nbytes} bytes), misaligned or on another device (use sparse_workspace())")
+		for q0 in range(0, Q, rows):
+			q1 = min(Q, q0 + rows)
+			check(lib.anncur_sparse_score_topk(*_sparse_args(csr, postings, q0, q1), kc, _p(val[q0:q1]), _p(idx[q0:q1]), _p(ws), ws.numel(), _stream()),
+				  "sparse_score_topk")
+		if excl is not None:
+			return filter_topk(val, idx, excl, int(k))
+	return TopK(val, idx)
+
+
 # ------------------------------------------------------------------ ranks of given items (DESIGN 4.4g)
 RANK_MAX_T = _lib.RANK_MAX_T
 _RANK_KP = (64, 128, 256, 512)

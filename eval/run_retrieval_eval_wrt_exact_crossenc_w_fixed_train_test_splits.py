@@ -101,13 +101,14 @@ def run_eval_method(curr_method, test_data_file, train_data_file, args, seed, de
 										  progress=lambda j, n: LOGGER.info(f"anchor count {j + 1}/{n}"), pinv_backend=args.pinv, **pool_kw)
 	elif curr_method in ("bienc", "tfidf"):
 		if not (args.mention_embeds_file and args.entity_embeds_file):
-			raise SystemExit(f"eval_method={curr_method}: pass --mention_embeds_file and --entity_embeds_file (.npy); "
-							 "computing them needs the reference's encoders, which are out of scope of this build")
-		ment = np.load(args.mention_embeds_file)
-		if curr_method == "tfidf" and ment.shape[0] != n_test:
-			ment = ment[np.asarray(test_ment_idxs)]        # splits.py:378
-		res = harness.run_eval_method_embeds(A_test_dev, torch.as_tensor(ment, dtype=torch.float32).to(device),
-											 torch.as_tensor(np.load(args.entity_embeds_file), dtype=torch.float32).to(device), n_train, grids)
+			raise SystemExit(f"eval_method={curr_method}: pass --mention_embeds_file and --entity_embeds_file (.npy, or .npz as scipy.sparse.save_npz "
+							 "writes a CSR matrix); computing them needs the reference's encoders, which are out of scope of this build")
+		ment, ent = harness.load_embeds(args.mention_embeds_file), harness.load_embeds(args.entity_embeds_file)
+		if curr_method == "tfidf" and (ment.n_rows if isinstance(ment, ops.SparseCSR) else ment.shape[0]) != n_test:
+			ment = harness.take_embed_rows(ment, test_ment_idxs)        # splits.py:378
+		# a sparse side stays sparse (harness.run_eval_method_embeds retrieves through the term-major index; a dense other side is sparsified there)
+		ment, ent = (e if isinstance(e, ops.SparseCSR) else torch.as_tensor(e, dtype=torch.float32).to(device) for e in (ment, ent))
+		res = harness.run_eval_method_embeds(A_test_dev, ment, ent, n_train, grids)
 	elif curr_method in ("fixed_anc_ent", "fixed_anc_ent_cur"):
 		if not os.path.isfile(args.e2e_fname):
 			raise SystemExit(f"File {args.e2e_fname} not found")

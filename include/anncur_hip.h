@@ -286,6 +286,53 @@ int anncur_score_rows_few(const void *X, int64_t ldx, const void *Et, int64_t ld
  * byte offsets / 256 of the group maxima and of the score scratch in the workspace}.  ANNCUR_E_UNSUPPORTED outside the route. */
 int anncur_score_topk_few_plan(int64_t Q, int64_t I, int32_t Kp, int32_t k, int32_t *out, int32_t n_out);
 
+/* a6+a7 on SPARSE operands: inner-product search through a term-major (inverted) index (csrc/sparse.hip) ------------------
+ *   tfidf evaluation method           eval/run_retrieval_eval_wrt_exact_crossenc_w_fixed_train_test_splits.py:360-385
+ *   TF-IDF hard-negative mining       utils/data_process.py:373-397 ; utils/compute_tfidf_hard_negs.py
+ * Queries: CSR [Q x V], q_ptr int64[Q + 1], q_term int32 (strictly ascending inside a row), q_val fp32.  Items: the TRANSPOSE of a CSR
+ * matrix [I x V], term_ptr int64[V + 1], post_item int32[nnz] (ascending inside a term), post_val fp32[nnz].  All on the device.
+ * Score: S[q, i] = the fp32 chain over the terms t that q and i share, in ascending t, from +0.0f, each step two separately rounded
+ * operations acc = fadd_rn(acc, fmul_rn(w_qt, v_it)); an item that shares no term with q scores +0.0 (bit pattern 0).  No atomics and no
+ * split sums: a score does not depend on the launch shape, on Q or on the position of q in the call, and equals a float32 loop on the host.
+ * One launch: a four-wave workgroup per (query, run of item windows); a wave owns a span of consecutive windows of ANNCUR_SPARSE_WINDOW
+ * items with private accumulators in LDS and one cursor per query term into that term's posting list (found once per span by a lower
+ * bound, carried from window to window).  LDS per workgroup: 8 bytes per staged query term (8 KB) + 4 waves x (8 KB accumulators + 8 bytes
+ * per term of cursors) = 72 KB at ANNCUR_SPARSE_MAX_QNNZ = 1024, so two workgroups share a CU's 160 KB; 2048 terms would take 136 KB and
+ * leave one.  A query with more stored terms than that is the CALLER's error (q_ptr lives on the device: ops checks it on the host); the
+ * kernel reads its first ANNCUR_SPARSE_MAX_QNNZ terms.  Equally defensive: a term id outside [0, V) contributes nothing and term_ptr is
+ * not read for it, a posting list is read for at most I entries, an item outside the window is skipped.
+ * Top-k: anncur_rowwise_topk on the score rows -- score descending, equal scores to the smaller item id, NaN never, -inf ordinary,
+ * (-inf, -1) pads; this route has no selector of its own.  On a row where thousands of items tie at +0.0 the scan's threshold is a composite
+ * (score, id) key: once a compaction has left it at the k-th zero, every later zero has a larger id, a smaller key, and is dropped
+ * without being buffered (the one-wave form for k <= 128 does the same in its wave's buffer): exact, and one read of the row as on any
+ * other data.  (few_select_kernel on (S, GM) would find nearly every group maximum equal to the
+ * threshold, overflow its candidate buffer and fall back to the same full scan, so GM buys nothing there; it is written for callers that
+ * audit the scores.) */
+#define ANNCUR_SPARSE_WINDOW 2048       /* items per window of LDS accumulators */
+#define ANNCUR_SPARSE_MAX_QNNZ 1024     /* stored terms per query (a 128-token mention has at most 128, an entity description a few hundred) */
+#define ANNCUR_SPARSE_PLAN_WORDS 10
+/*   ..._splits.py:383 (mention x entity TF-IDF scores)
+ * S[q, i] for q < Q, i < I at pitch lds >= I (16-byte stores when S is 16-byte aligned and lds a multiple of 4, scalar stores otherwise)
+ * and, if GM is not NULL, GM[q, g] = max of S[q, 64 g .. 64 g + 63] over the items < I at pitch ldg >= ceil(I / 64), an fmaxf chain from
+ * NaN as anncur_score_rows_few's.  Nothing else of S or GM is written.  Q >= 0 (Q == 0 returns OK), 1 <= I < 2^31 - 1, 0 <= V < 2^31;
+ * Q x workgroups per query must stay below 2^31 (ANNCUR_E_UNSUPPORTED: call in chunks).  post_item / post_val may be NULL when nnz == 0. */
+int anncur_sparse_score_rows(const int64_t *q_ptr, const int32_t *q_term, const float *q_val, int64_t Q, const int64_t *term_ptr,
+                             const int32_t *post_item, const float *post_val, int64_t V, int64_t I, float *S, int64_t lds, float *GM,
+                             int64_t ldg, void *stream);
+/*   ..._splits.py:383-385 ; utils/data_process.py:397 (index.search(ment_embeds, k))
+ * The scores into the workspace [Q x ceil32(I)] fp32 (256-byte aligned, nothing pre-filled), then anncur_rowwise_topk: out_val float[Q x k],
+ * out_idx int32[Q x k], 1 <= k <= min(I, ANNCUR_MAX_TOPK).  A short or misaligned workspace is ANNCUR_E_WORKSPACE, nothing is written. */
+int anncur_sparse_score_topk(const int64_t *q_ptr, const int32_t *q_term, const float *q_val, int64_t Q, const int64_t *term_ptr,
+                             const int32_t *post_item, const float *post_val, int64_t V, int64_t I, int32_t k, float *out_val,
+                             int32_t *out_idx, void *workspace, size_t workspace_bytes, void *stream);
+/* Q x ceil32(I) x 4 bytes; 0 outside the limits. */
+size_t anncur_sparse_score_topk_workspace_bytes(int64_t Q, int64_t I, int32_t k);
+/* The plan of a call (host only, no device): out[0..min(n_out, ANNCUR_SPARSE_PLAN_WORDS)) = {windows per query, windows per wave, spans
+ * (waves with work) per query, workgroups per query, workgroups, waves per workgroup, LDS bytes per workgroup, score pitch / 32, groups of
+ * 64 items per query, ANNCUR_SPARSE_MAX_QNNZ}.  Windows per wave = ceil(Q x windows / 2048 waves), at most a query's windows: one query
+ * spreads over its windows, many queries give each wave a long span and few searches. */
+int anncur_sparse_plan(int64_t Q, int64_t I, int32_t *out, int32_t n_out);
+
 /* a6+a7 at fp32 parity on the bf16 matrix cores: the split-bf16 ("bf16x3") route -------------------------------------------------
  *   CURApprox.get_complete_row + topk_in_row on FloatTensors      eval/matrix_approx_zeshel.py:118,126
  *   faiss IndexFlatIP.add / .search on float32 vectors            models/nearest_nbr.py:36-38
