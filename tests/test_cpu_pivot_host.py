@@ -103,6 +103,36 @@ def test_restatement_equals_the_closed_form_on_hadamard_data():
 	assert n_sel == want[2] == 40 and np.array_equal(ids, want[0]) and np.array_equal(gains, want[1])
 
 
+@pytest.mark.parametrize("n, kq, m, k", [(16, 16, 1300, 24), (256, 256, 1500, 40), (256, 600, 1777, 32), (1024, 1027, 2100, 24)])
+def test_restatement_equals_the_closed_form_at_other_hadamard_orders(n, kq, m, k):
+	"""The closed form with the Hadamard order as a parameter (the data of tests/test_gpu_select_pivoted_large.py), against the restatement:
+	ids, gains and n_sel are equal.  kq > n appends zero rows; with n = 16 the rank stops the k = 24 picks at 16."""
+	rng = np.random.default_rng(n + kq)
+	scales = rng.integers(1, 10, m)
+	scales[rng.choice(m, m // 8, replace=False)] *= -1
+	want = pn.hadamard_closed_form(scales, k, n=n)
+	ids, gains, n_sel, _ = pn.select(pn.hadamard_items(scales, kq, n=n), k)
+	assert n_sel == want[2] == min(k, n) and np.array_equal(ids, want[0]) and np.array_equal(gains, want[1])
+	assert np.array_equal(gains[:n_sel], float(n) * scales[ids[:n_sel]].astype(np.float64) ** 2) and (ids[n_sel:] == -1).all()
+	# NaN columns among the would-be winners are passed over, here as there
+	never = tuple(int(i) for i in want[0][:3])
+	R = pn.hadamard_items(scales, kq, n=n).astype(np.float64)
+	R[:, list(never)] = np.nan
+	want = pn.hadamard_closed_form(scales, k, never=never, n=n)
+	ids, gains, n_sel, _ = pn.select(R, k)
+	assert n_sel == want[2] and np.array_equal(ids, want[0]) and np.array_equal(gains, want[1]) and not np.isin(never, ids).any()
+
+
+def test_hadamard_order_must_be_a_power_of_4():
+	for n in (2, 8, 32, 48, 128, 512):
+		with pytest.raises(AssertionError):
+			pn.hadamard_items(np.ones(10, dtype=np.int64), 1024, n=n)
+		with pytest.raises(AssertionError):
+			pn.hadamard_closed_form(np.ones(10, dtype=np.int64), 4, n=n)
+	for n in (1, 4, 16, 64, 256, 1024, 4096):
+		assert pn._power_of_4(n)
+
+
 def test_anchor_selection_sorted_and_its_errors():
 	from anncur_amd.cur import ANCHOR_SELECTIONS, AnchorSelection, select_anchor_items
 	assert ANCHOR_SELECTIONS == ("random", "pivoted")

@@ -4,11 +4,15 @@
 of the identity with a power of two as square root, every intermediate is exact in fp64 and W must equal the rational result
 (sum_j c_j col_j) / d rounded to fp32 -- here exactly representable.  Layout of every case: Rt is a view into a NaN-filled buffer (pitch pad
 and the rows no id names are NaN), ids in random order, holes in the first, middle and last position, workspace and W filled with 0xff,
-Q in {1, 5}, the chunked path forced by a byte cap of three queries (chunks of 3 and 2).
+Q in {1, 5}, the chunked path forced by a byte cap of three queries (chunks of 3 and 2).  Sizes: g = 16, 64, 256 throughout, and each closed
+form once more at the call's limits -- g = 512 on the item side (kq = 1024) and on the query side (kq = 512, with and without holes, and with
+a ridge at n = 2048), kq = 4096.
 (b) Against fp64 numpy on Gaussian data, with the bound derived in the issue: normal equations in fp64 err by at most
 cond(G) g 2^-53 <= 2^10 2^9 2^-53 = 2^-34 relative to ||w||_2 where cond_2(R_S) <= 32 (asserted here on the host, from the reference alone; a
 draw that fails is replaced), plus one fp32 rounding:  |W - w| <= 2^-24 |w| + 2^-30 ||w||_2  elementwise (16x margin on the 2^-34).
 Needs an MI355X."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -24,11 +28,14 @@ def ops():
 	return _ops
 
 
+@functools.lru_cache(maxsize=None)
 def hadamard(g):
+	"""(shared between the cases and never written to)"""
 	H = np.array([[1]], dtype=np.int64)
 	while H.shape[0] < g:
 		H = np.block([[H, H], [H, -H]])
 	assert H.shape[0] == g
+	H.setflags(write=False)
 	return H
 
 
@@ -141,6 +148,55 @@ def test_item_side_ridge_hadamard_bit_exact(ops, g, Q):
 	Rt, ids, C, S = hadamard_case(g, cols, Q, seed=13 * g + Q, hole_pos=pos)
 	W, status = run_poisoned(ops, Rt, ids, C, 3.0 * g, Q == 5)
 	assert not status.any() and np.array_equal(W.view(np.uint32), exact_f32(S, 4 * g).view(np.uint32))
+
+
+# The same closed forms at the limits of the call: g = ANNCUR_LSTSQ_MAX_G = 512 on either side (the ninth row block of the factorisation's
+# MAXBLK), kq = ANNCUR_LSTSQ_MAX_KQ = 4096 and n = ANNCUR_MAX_TOPK = 2048.  Q = 5 runs chunked (3 + 2).
+@pytest.mark.parametrize("Q", [1, 5])
+def test_item_side_g512_hadamard_bit_exact(ops, Q):
+	# n = 512 positions on kq = 1024: 509 signed columns of H_1024 and holes first / middle / last; G = 1024 I
+	from anncur_amd import _lib
+	assert _lib.LSTSQ_MAX_G == 512
+	cols = list(np.random.default_rng(512).permutation(1024)[:509])
+	Rt, ids, C, S = hadamard_case(1024, cols, Q, seed=5120 + Q, hole_pos=(0, 256, 511))
+	assert ids.shape[1] == 512
+	W, status = run_poisoned(ops, Rt, ids, C, 0.0, Q == 5)
+	assert not status.any() and np.array_equal(W.view(np.uint32), exact_f32(S, 1024).view(np.uint32))
+
+
+@pytest.mark.parametrize("Q", [1, 5])
+def test_item_side_kq4096_hadamard_bit_exact(ops, Q):
+	# n = 64 positions on kq = 4096 = ANNCUR_LSTSQ_MAX_KQ: 61 signed columns of H_4096 and three holes; G = 4096 I
+	from anncur_amd import _lib
+	assert _lib.LSTSQ_MAX_KQ == 4096
+	cols = list(np.random.default_rng(4096).permutation(4096)[:61])
+	Rt, ids, C, S = hadamard_case(4096, cols, Q, seed=4096 + Q, hole_pos=(0, 32, 63))
+	assert ids.shape[1] == 64
+	W, status = run_poisoned(ops, Rt, ids, C, 0.0, Q == 5)
+	assert not status.any() and np.array_equal(W.view(np.uint32), exact_f32(S, 4096).view(np.uint32))
+
+
+@pytest.mark.parametrize("with_holes", [False, True])
+@pytest.mark.parametrize("Q", [1, 5])
+def test_query_side_kq512_hadamard_bit_exact(ops, Q, with_holes):
+	# R_S = [H_512 | H_512] under signs: g = kq = 512, G = 1024 I; the three holes are extra positions (n = 1027)
+	cols = list(range(512)) * 2
+	Rt, ids, C, S = hadamard_case(512, cols, Q, seed=7 * 512 + Q, hole_pos=holes3(1024) if with_holes else ())
+	assert ids.shape[1] == 1024 + (3 if with_holes else 0)
+	W, status = run_poisoned(ops, Rt, ids, C, 0.0, Q == 5)
+	assert not status.any() and np.array_equal(W.view(np.uint32), exact_f32(S, 1024).view(np.uint32))
+
+
+@pytest.mark.parametrize("Q", [1, 5])
+def test_query_side_ridge_at_the_longest_list_bit_exact(ops, Q):
+	# four copies of H_512: n = 2048 = ANNCUR_MAX_TOPK, G = 2048 I, lambda = 2048: G + lambda I = 4096 I
+	from anncur_amd import _lib
+	assert _lib.MAX_TOPK == 2048
+	cols = list(range(512)) * 4
+	Rt, ids, C, S = hadamard_case(512, cols, Q, seed=9 * 512 + Q)
+	assert ids.shape[1] == 2048
+	W, status = run_poisoned(ops, Rt, ids, C, 2048.0, Q == 5)
+	assert not status.any() and np.array_equal(W.view(np.uint32), exact_f32(S, 4096).view(np.uint32))
 
 
 @pytest.mark.parametrize("g", [16, 64, 256])

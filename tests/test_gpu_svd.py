@@ -8,6 +8,16 @@ Generic data against numpy.linalg.svd in fp64 on the same fp32 values: the four 
 chosen in advance: the largest ratio error / (g 2^-53 sigma_max) over the ten shapes was measured on an MI355X (the figures are in DESIGN
 4.5a and printed by every run of the test) and C is 8 times that, rounded up to a power of two -- the margin covers other seeds and LAPACK's
 own error.  The issue's condition C <= 1024 (above it the iteration would not reach fp64 accuracy) holds.
+The same two kinds of data above 256 vectors, where every loop over g takes more than one pass: the exact block at g = 600 (H_1024) and at the
+limit g = 2048 (H_4096, S = 64 d), generic 300 x 320, 700 x 513 and 300 x 2100, a truncation among 300 singular values, and the fixed matrix
+[[2, 1], [1, 2]] whose first rotation has zeta == 0.
+
+Mutations tried on scratch builds when the tests above 256 vectors were written (each only drops work; every test this file had before PASSES on
+both -- the largest g was 130):
+  * svd_pair_kernel rotates only the first 256 entries of Vt's rows: generic 300 x 320, 700 x 513 and 300 x 2100 fail (V^T V - I or U^T U - I)
+    and so do both truncations among 300 singular values (5 tests).  The exact blocks pass: nothing rotates on them.
+  * svd_scale_cols_kernel counts the rank over its first pass only: the exact blocks at g = 600 (4 tests) and g = 2048 (2) fail, and the
+    truncation at rank 271; the one at rank 152 passes, as it must (every kept value lies in the first pass).
 Needs an MI355X."""
 import functools
 import logging
@@ -20,7 +30,7 @@ pytestmark = pytest.mark.gpu
 
 C = 32.0            # 8 x the largest measured ratio (2.604, V^T V - I of the 96 x 96 block: DESIGN 4.5a) = 20.8, rounded up to a power of two
 EPS = 2.0 ** -53
-SHAPES = [(1, 1), (1, 40), (2, 2), (5, 3), (33, 17), (64, 64), (96, 96), (96, 192), (192, 96), (257, 130)]
+SHAPES = [(1, 1), (1, 40), (2, 2), (5, 3), (33, 17), (64, 64), (96, 96), (96, 192), (192, 96), (257, 130), (300, 320), (700, 513)]
 
 
 @pytest.fixture(scope="module")
@@ -32,13 +42,11 @@ def ops():
 
 
 def hadamard(n):
-	H = np.ones((1, 1))
+	"""Sylvester's H_n as int8 (H_4096 is 16 MB this way); a product with a float64 array widens it."""
+	H = np.ones((1, 1), dtype=np.int8)
 	while H.shape[0] < n:
 		H = np.block([[H, H], [H, -H]])
 	return H
-
-
-D48 = 2.0 ** -(np.arange(48) % 7)
 
 
 @functools.lru_cache(maxsize=None)
@@ -72,12 +80,16 @@ def _guarded(shape, pitch, device, fill):
 	return view, buf
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
-@pytest.mark.parametrize("transposed", [False, True], ids=["W", "Wt"])
-def test_exact_hadamard_block_bit_for_bit(ops, dtype, transposed):
+def _exact_hadamard_block(ops, n, g, dtype, transposed):
+	"""W = H_n[:, :g] diag(d), d_j = 2^-(j mod 7), n a power of 4 (sqrt(n) a power of two): sweeps == 1 with zero rotations, S = sqrt(n) d sorted,
+	the pseudo-inverse diag(1/d) H^T / n bit for bit, and the cutoff 2^-3.5 between two singular values."""
 	dev = torch.device("cuda")
-	W = hadamard(64)[:, :48] * D48                                       # 64 x 48, every entry +-2^-k
-	X_want = (hadamard(64)[:, :48] / D48).T / 64.0                        # 48 x 64 = diag(1/d) H^T / 64
+	root = int(round(n ** 0.5))
+	assert root * root == n and root & (root - 1) == 0
+	D = 2.0 ** -(np.arange(g) % 7)
+	Hg = hadamard(n)[:, :g]
+	W = Hg * D                                                           # n x g, every entry +-2^-k
+	X_want = (Hg / D).T / float(n)                                        # g x n = diag(1/d) H^T / n
 	if transposed:
 		W, X_want = W.T, X_want.T
 	rows, cols = W.shape
@@ -85,7 +97,6 @@ def test_exact_hadamard_block_bit_for_bit(ops, dtype, transposed):
 	big[:, :cols] = torch.from_numpy(W.astype(np.float32)).to(dev).to(dtype)
 	Wd = big[:, :cols]
 	assert np.array_equal(Wd.float().cpu().numpy().astype(np.float64), W)         # (exact in bf16 too)
-	g = 48
 	need = ops._lib.load().anncur_svd_workspace_bytes(rows, cols)
 	wsbuf = torch.full((need + 512,), 0xff, dtype=torch.uint8, device=dev)       # every double of the workspace starts as a NaN
 	off = (-wsbuf.data_ptr()) % 256
@@ -103,12 +114,12 @@ def test_exact_hadamard_block_bit_for_bit(ops, dtype, transposed):
 	assert bool((wsbuf[:off] == 0xff).all()) and bool((wsbuf[off + need:] == 0xff).all())
 	# guards: behind each output and in the row pitch pads
 	assert bool((sbuf[g:] == SENT).all())
-	for view, buf, pitch, n in ((U, ubuf, g + 3, rows), (V, vbuf, g + 7, cols)):
+	for view, buf, pitch, nr in ((U, ubuf, g + 3, rows), (V, vbuf, g + 7, cols)):
 		flat = buf.clone()
-		torch.as_strided(flat, (n, g), (pitch, 1)).fill_(SENT)
+		torch.as_strided(flat, (nr, g), (pitch, 1)).fill_(SENT)
 		assert bool((flat == SENT).all()), "an element outside the [n x g] output was written"
 	S, order = torch.sort(sigma, descending=True, stable=True)
-	assert np.array_equal(S.cpu().numpy(), np.sort(8.0 * D48)[::-1])
+	assert np.array_equal(S.cpu().numpy(), np.sort(float(root) * D)[::-1])
 	svd = ops.SVD(U.index_select(1, order), S, V.index_select(1, order), sweeps, converged)
 	# the same through the public call (its own scratch and outputs): equal bits
 	pub = ops.svd_jacobi(Wd)
@@ -116,18 +127,40 @@ def test_exact_hadamard_block_bit_for_bit(ops, dtype, transposed):
 	for a, b in ((pub.U, svd.U), (pub.S, svd.S), (pub.V, svd.V)):
 		assert torch.equal(a.view(torch.int64), b.contiguous().view(torch.int64))
 	X, rank = ops.pinv_from_svd(svd)
-	assert rank == 48 and X.dtype == torch.float32 and tuple(X.shape) == (cols, rows)
+	assert rank == g and X.dtype == torch.float32 and tuple(X.shape) == (cols, rows)
 	assert np.array_equal(X.cpu().numpy().view(np.uint32), X_want.astype(np.float32).view(np.uint32))
 	# a cutoff between two singular values: d_j < 2^-3.5 goes
 	Xt, rank_t = ops.pinv_from_svd(svd, rcond=2.0 ** -3.5)
-	keep = D48 > 2.0 ** -3.5
-	assert rank_t == int(keep.sum()) == 28
+	keep = D > 2.0 ** -3.5
+	assert rank_t == int(keep.sum()) == 4 * (g // 7) + min(g % 7, 4)
 	want_t = X_want.copy()
 	if transposed:
 		want_t[:, ~keep] = 0.0
 	else:
 		want_t[~keep, :] = 0.0
 	assert np.array_equal(Xt.cpu().numpy().view(np.uint32), want_t.astype(np.float32).view(np.uint32))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("transposed", [False, True], ids=["W", "Wt"])
+def test_exact_hadamard_block_bit_for_bit(ops, dtype, transposed):
+	_exact_hadamard_block(ops, 64, 48, dtype, transposed)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("transposed", [False, True], ids=["W", "Wt"])
+def test_exact_hadamard_block_above_256_vectors(ops, dtype, transposed):
+	"""g = 600: three passes of every loop over g (the copy of Vt, the maximum, the scaling and the rank count, the identity's grid), the third
+	one ragged (600 = 2 * 256 + 88).  No rotation happens on this data, so the rotation of Vt is the generic cases' to test."""
+	_exact_hadamard_block(ops, 1024, 600, dtype, transposed)
+
+
+@pytest.mark.parametrize("transposed", [False, True], ids=["W", "Wt"])
+def test_exact_hadamard_block_at_the_limit(ops, transposed):
+	"""g = 2048 = ANNCUR_SVD_MAX_G with L = 4096: eight full passes over g, rows read twice (L above the register path), S = 64 d."""
+	from anncur_amd import _lib
+	assert _lib.SVD_MAX_G == 2048
+	_exact_hadamard_block(ops, 4096, 2048, torch.float32, transposed)
 
 
 # ------------------------------------------------------------------ 2. generic data
@@ -146,13 +179,25 @@ def test_generic_against_numpy_fp64(ops, shape):
 		assert v <= C, (k, v)
 
 
-LONG_SHAPES = [(5, 2048), (3, 2049), (2049, 3), (2, 8192)]
+def test_two_columns_of_equal_norm_take_the_45_degree_rotation(ops):
+	"""[[2, 1], [1, 2]]: alpha == beta, so zeta == 0 and the rotation is t = 1 (the branch no random matrix takes); singular values 3 and 1."""
+	W = np.array([[2.0, 1.0], [1.0, 2.0]], dtype=np.float32)
+	svd = ops.svd_jacobi(torch.tensor(W).cuda())
+	assert svd.converged and svd.sweeps == 2                             # one rotation, then a sweep that finds nothing to do
+	r = ratios(W, np.array([3.0, 1.0]), svd)
+	print("svd [[2, 1], [1, 2]]: error / (g 2^-53 sigma_max): " + ", ".join(f"{k} {v:.3f}" for k, v in r.items()))
+	for k, v in r.items():
+		assert v <= C, (k, v)
+
+
+LONG_SHAPES = [(5, 2048), (3, 2049), (2049, 3), (2, 8192), (300, 2100)]
 
 
 @pytest.mark.parametrize("shape", LONG_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_long_rows_on_both_sides_of_the_register_path(ops, shape):
 	"""L = 2048 is the longest row a thread keeps in registers between the dot pass and the update, 2049 the first that is read twice, 8192
-	the limit.  Few vectors, so a sweep is a handful of launches.  With g this small the term that counts is not g but sqrt(L): the rotation
+	the limit.  Few vectors, so a sweep is a handful of launches -- but for 300 x 2100: rows read twice TOGETHER with g > 256 (there the scale
+	below is 1).  With g this small the term that counts is not g but sqrt(L): the rotation
 	rule leaves |u_i . u_j| up to sqrt(L) 2^-53 by construction, and a sum of L products carries rounding of that order, so the figures are
 	held to C max(g, sqrt(L)) 2^-53 sigma_max: the constant of the generic test on the larger of the two scales."""
 	W, _, S_ref, _ = generic(*shape)
@@ -174,14 +219,12 @@ def _pinv_bound(X_ref, S_ref, rank, g):
 	return C * g * EPS * (S_ref[0] / S_ref[rank - 1]) * xm + 2.0 ** -24 * xm
 
 
-def test_truncation_between_two_singular_values(ops):
+def _truncation_between_two_singular_values(rows, g, rcond, seed):
 	from anncur_amd import pinv
-	rng = np.random.default_rng(7)
-	rows, g = 96, 64
+	rng = np.random.default_rng(seed)
 	U0, _ = np.linalg.qr(rng.standard_normal((rows, g)))
 	V0, _ = np.linalg.qr(rng.standard_normal((g, g)))
 	W = ((U0 * np.logspace(0, -6, g)) @ V0.T).astype(np.float32)
-	rcond = 10.0 ** -3.05
 	W64 = W.astype(np.float64)
 	S_ref = np.linalg.svd(W64, compute_uv=False)
 	rank_ref = int((S_ref > rcond * S_ref[0]).sum())
@@ -190,9 +233,22 @@ def test_truncation_between_two_singular_values(ops):
 	X, info = pinv.pinv_svd(torch.from_numpy(W).cuda(), rcond=rcond, return_info=True)
 	assert info["converged"] and info["rank"] == rank_ref
 	err, bound = np.abs(X.cpu().numpy().astype(np.float64) - X_ref).max(), _pinv_bound(X_ref, S_ref, rank_ref, g)
-	print(f"truncated pinv 96 x 64: rank {info['rank']}, sweeps {info['sweeps']}, max|X - X_ref| = {err:.3e}, bound {bound:.3e}")
+	print(f"truncated pinv {rows} x {g}: rank {info['rank']}, sweeps {info['sweeps']}, max|X - X_ref| = {err:.3e}, bound {bound:.3e}")
 	assert err <= bound
 	assert np.abs(info["singular_values"].cpu().numpy() - S_ref).max() <= C * g * EPS * S_ref[0]
+	return info["rank"]
+
+
+def test_truncation_between_two_singular_values(ops):
+	_truncation_between_two_singular_values(96, 64, 10.0 ** -3.05, 7)
+
+
+@pytest.mark.parametrize("rank", [152, 271])
+def test_truncation_between_two_of_300_singular_values(ops, rank):
+	"""g = 300: svd_scale_cols_kernel scales and counts over two passes.  The values are sorted descending, so with rank 152 the second pass
+	(256 .. 299) must zero everything and count nothing, with rank 271 both passes keep and count.  The cutoff is the geometric mean of two
+	neighbours of logspace(0, -6, 300); the fp32 rounding of W moves no singular value to within 2 % of it."""
+	assert _truncation_between_two_singular_values(400, 300, 10.0 ** (-6.0 * (rank - 0.5) / 299.0), 8) == rank
 
 
 def test_rank_deficient_block(ops):
