@@ -667,7 +667,9 @@ __global__ __launch_bounds__(SEL_THREADS) void rerank_kernel(const T *__restrict
 }
 
 // ------------------------------------------------------------------ a10: overlap counts
-// common[p*Q + q] = |set(a[q,:ka[p]]) & set(b[q,:kb[p]])|.  pos[j] = first position of a[q,j] in b[q,:] (or lb).
+// common[p*Q + q] = |set(a[q,:ka[p]]) & set(b[q,:kb[p]])|, negative ids (the selectors' -1 pads) in no set.  Either list may
+// repeat an id.  pos[j] = first position of a[q,j] in b[q,:] if j is the FIRST position of that id in a[q,:], else "nowhere": an id of the
+// intersection is then counted once, at its first position in a, for exactly the pairs with ka > that position and kb > pos[j].
 constexpr int OVL_MAX_PAIRS = 64;
 struct OvlPairs { int32_t ka[OVL_MAX_PAIRS]; int32_t kb[OVL_MAX_PAIRS]; };
 
@@ -678,21 +680,27 @@ __global__ __launch_bounds__(256) void overlap_kernel(const int32_t *__restrict_
 	int32_t *sb = reinterpret_cast<int32_t *>(smem);  // [lb]
 	int32_t *spos = sb + lb;                          // [la]
 	int32_t *scnt = spos + la;                        // [n_pairs]
+	int32_t *sown = scnt + n_pairs;                   // [lb]: the first j with pos[j] == t
 	const int tid = threadIdx.x;
 	const int64_t q = blockIdx.x;
-	for (int j = tid; j < lb; j += 256) sb[j] = b[q * lb + j];
+	for (int j = tid; j < lb; j += 256) { sb[j] = b[q * lb + j]; sown[j] = 0x7fffffff; }
 	for (int p = tid; p < n_pairs; p += 256) scnt[p] = 0;
 	__syncthreads();
 	for (int j = tid; j < la; j += 256) {
 		const int32_t x = a[q * la + j];
 		int32_t pos = lb;
-		// also require that x did not already appear earlier in a[q,:j] (set semantics); inputs are
-		// distinct per row on this path, so this is a no-op scan kept cheap by the early exit below
 		if (x >= 0) {
 			for (int t = 0; t < lb; ++t)
 				if (sb[t] == x) { pos = t; break; }
 		}
 		spos[j] = pos;
+		// two positions of a share a first position in b exactly when they hold the same id: the smallest j owns it
+		if (pos < lb) atomicMin(&sown[pos], j);
+	}
+	__syncthreads();
+	for (int j = tid; j < la; j += 256) {   // (the thread that wrote spos[j])
+		const int32_t pos = spos[j];
+		if (pos < lb && sown[pos] != j) spos[j] = lb;
 	}
 	__syncthreads();
 	for (int p = 0; p < n_pairs; ++p) {
@@ -732,8 +740,8 @@ __global__ __launch_bounds__(256) void overlap_wave_kernel(const int32_t *__rest
 			const int p = e * WAVE + t;
 			const unsigned long long m0 = __ballot(av[0] == x), m1 = __ballot(av[1] == x);
 #if defined(__HIP_DEVICE_COMPILE__)
-			if (m0 != 0ull) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %1, m0" : "+v"(pos[0]) : "s"(p), "s"((int)__builtin_ctzll(m0)) : "m0");   // (more than one lane: a's -1 padding, never counted)
-			if (m1 != 0ull) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %1, m0" : "+v"(pos[1]) : "s"(p), "s"((int)__builtin_ctzll(m1)) : "m0");
+			if (m0 != 0ull) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %1, m0" : "+v"(pos[0]) : "s"(p), "s"((int)__builtin_ctzll(m0)) : "m0");   // (more than one lane: a's -1 padding, never counted, or a repeated id: its first lane only)
+			else if (m1 != 0ull) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %1, m0" : "+v"(pos[1]) : "s"(p), "s"((int)__builtin_ctzll(m1)) : "m0");
 #endif
 		}
 	}
@@ -1012,7 +1020,7 @@ extern "C" int anncur_rerank(const void *A, int dtype, int64_t Q, int64_t I, int
 
 extern "C" int anncur_overlap_counts(const int32_t *a, int32_t la, const int32_t *b, int32_t lb, int64_t Q,
 									 const int32_t *ka, const int32_t *kb, int32_t n_pairs, int32_t *common, void *stream) {
-	ANNCUR_REQUIRE(a && b && ka && kb && common, ANNCUR_E_INVALID, "overlap_counts: null pointer");
+	ANNCUR_REQUIRE(ka && kb, ANNCUR_E_INVALID, "overlap_counts: null pointer");
 	ANNCUR_REQUIRE(la >= 1 && lb >= 1 && la <= 4096 && lb <= 4096, ANNCUR_E_INVALID, "overlap_counts: list lengths must be in 1..4096");
 	ANNCUR_REQUIRE(n_pairs >= 1 && n_pairs <= OVL_MAX_PAIRS, ANNCUR_E_INVALID, "overlap_counts: n_pairs must be in 1..%d", OVL_MAX_PAIRS);
 	ANNCUR_REQUIRE(Q >= 0 && Q < (int64_t)0x7fffffff, ANNCUR_E_INVALID, "overlap_counts: bad Q");
@@ -1023,14 +1031,15 @@ extern "C" int anncur_overlap_counts(const int32_t *a, int32_t la, const int32_t
 		pairs.ka[p] = ka[p];
 		pairs.kb[p] = kb[p];
 	}
-	if (Q == 0) return ANNCUR_OK;
+	if (Q == 0) return ANNCUR_OK;  // (empty tensors have null data pointers: nothing to do comes first)
+	ANNCUR_REQUIRE(a && b && common, ANNCUR_E_INVALID, "overlap_counts: null pointer");
 	if (la <= 2 * WAVE && lb <= 2 * WAVE) {
 		hipLaunchKernelGGL(overlap_wave_kernel, dim3((unsigned)ceil_div64(Q, 4)), dim3(256), 0, (hipStream_t)stream, a, la, b, lb, Q, pairs,
 						   n_pairs, common);
 		ANNCUR_LAUNCH_OK();
 		return ANNCUR_OK;
 	}
-	const size_t lds = (size_t)(la + lb + n_pairs) * 4;
+	const size_t lds = (size_t)(la + 2 * lb + n_pairs) * 4;  // (<= 49 408 bytes)
 	hipLaunchKernelGGL(overlap_kernel, dim3((unsigned)Q), dim3(256), lds, (hipStream_t)stream, a, la, b, lb, Q, pairs, n_pairs, common);
 	ANNCUR_LAUNCH_OK();
 	return ANNCUR_OK;

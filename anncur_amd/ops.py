@@ -2097,18 +2097,22 @@ def gather_pairs(A, idx):
 
 @_on_device
 def overlap_counts(a, b, pairs, mapped_host_out=None):
-	"""common[p, q] = |set(a[q, :ka_p]) & set(b[q, :kb_p])| for pairs = [(ka, kb), ...] -> int32 [n_pairs, Q].
+	"""common[p, q] = |set(a[q, :ka_p]) & set(b[q, :kb_p])| for pairs = [(ka, kb), ...] -> int32 [n_pairs, Q] (DESIGN 4.3a).
+	Ids below zero (the -1 pads of a short top-k row) belong to no set; either list may repeat an id, which counts once, at its first position
+	in each list.  Lists hold 1..4096 ids; any number of pairs (64 per launch, each launch writing its own rows of the result); pairs = [] or
+	Q = 0 give the empty result without a launch.
 	mapped_host_out: a contiguous PINNED host tensor int32 [n_pairs, Q] (mapped into the device address space by the HIP runtime): the kernel writes
-	the counts there itself -- no device buffer, no copy launch (graph-capturable; the caller synchronises before reading it)."""
-	_dev(a, b)
-	a = a.to(torch.int32).contiguous()
-	b = b.to(torch.int32).contiguous()
+	the counts there itself -- no device buffer, no copy launch (graph-capturable; the caller synchronises before reading it).  Every element is
+	written; it is also what the call returns."""
 	Q = a.shape[0]
 	if mapped_host_out is not None:
 		out = mapped_host_out
 		if out.is_cuda or not out.is_pinned() or not out.is_contiguous() or out.dtype != torch.int32 or tuple(out.shape) != (len(pairs), Q):
 			raise ValueError("overlap_counts: mapped_host_out must be a contiguous pinned int32 host tensor [n_pairs, Q]")
-	else:
+	_dev(a, b)
+	a = a.to(torch.int32).contiguous()
+	b = b.to(torch.int32).contiguous()
+	if mapped_host_out is None:
 		out = torch.empty((len(pairs), Q), dtype=torch.int32, device=a.device)
 	lib = _lib.load()
 	for s in range(0, len(pairs), 64):
@@ -2315,10 +2319,12 @@ def ivf_search_grouped(lists, offsets, ids, sizes_host, Q, probe, k, max_bytes=8
 @_on_device
 def copy_to_mapped_host(src, pinned_host):
 	"""Device kernel copy of `src` (CUDA tensor) into a PINNED host tensor (mapped into the device address space by the HIP
-	runtime): graph-capturable, no copy engine.  The caller synchronises (event) before reading `pinned_host`."""
-	_dev(src)
+	runtime): graph-capturable, no copy engine.  The caller synchronises (event) before reading `pinned_host`.
+	A copy of bytes: the two tensors need the same byte count, not the same dtype or shape; exactly those bytes of `pinned_host` are written
+	(it may be a 16-byte-aligned contiguous view of a larger pinned tensor), `src` is not; zero bytes launch nothing."""
 	if pinned_host.is_cuda or not pinned_host.is_pinned() or not pinned_host.is_contiguous():
 		raise ValueError("copy_to_mapped_host needs a contiguous pinned host tensor")
+	_dev(src)
 	src = src.contiguous()
 	nbytes = src.numel() * src.element_size()
 	if nbytes != pinned_host.numel() * pinned_host.element_size():

@@ -448,7 +448,11 @@ int anncur_rerank(const void *A, int dtype, int64_t Q, int64_t I, int64_t lda,
                   const int32_t *approx_idx, int64_t ld_idx, int32_t k_retvr, int32_t k_out,
                   float *rerank_val, int32_t *rerank_idx, void *stream);
 /* common[p*Q + q] = | a[q, :ka[p]] (set) intersect b[q, :kb[p]] | for each of n_pairs
- * (ka,kb) prefix-length pairs (host int32 arrays), a int32[Q x la], b int32[Q x lb]. */
+ * (ka,kb) prefix-length pairs (host int32 arrays), a int32[Q x la], b int32[Q x lb].
+ * Set semantics on both sides: an id that a prefix repeats is one member, and ids below zero (the -1 pads
+ * of a top-k row with fewer than k items) are members of no set.  1 <= la, lb <= 4096, 0 <= ka[p] <= la,
+ * 0 <= kb[p] <= lb, 1 <= n_pairs <= 64; every one of the n_pairs x Q counts is written (common may be
+ * mapped host memory).  Q == 0 is valid and launches nothing; all other arguments are still checked. */
 int anncur_overlap_counts(const int32_t *a, int32_t la, const int32_t *b, int32_t lb, int64_t Q,
                           const int32_t *ka, const int32_t *kb, int32_t n_pairs,
                           int32_t *common, void *stream);
