@@ -126,8 +126,6 @@ SIGNATURES = {
 	"anncur_ivf_list_means": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
 	"anncur_renorm_rows": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p]),
 	"anncur_ivf_scan": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
-	"anncur_ivf_group_scores": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
-	"anncur_ivf_group_scores_bf16": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
 	"anncur_ivf_group_scores_dev": (c_int, [c_void_p, c_int, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
 	"anncur_rowwise_topk_ragged": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
 	"anncur_ivf_search_tile": (c_int32, [c_int, c_int32, c_int64, c_int64, c_int64]),

@@ -25,30 +25,45 @@ __global__ __launch_bounds__(256) void ivf_count_kernel(const int32_t *__restric
 	if (threadIdx.x == 0) counts[l] = (int32_t)(part[0] + part[1] + part[2] + part[3]);
 }
 
-// offsets[0..nlist] = exclusive prefix sum of counts (single workgroup; nlist is ~sqrt(n))
-__global__ __launch_bounds__(256) void ivf_scan_counts_kernel(const int32_t *__restrict__ counts, int32_t nlist, int32_t *__restrict__ offsets) {
-	__shared__ int32_t carry;
-	__shared__ int32_t wsum[4];
-	if (threadIdx.x == 0) carry = 0;
-	__syncthreads();
+// Exclusive prefix sums of N series over 0 .. nlist - 1 in one pass, by ONE workgroup of 256 threads (nlist is ~sqrt(n)): value(i, c) gives
+// the series' values at i, store(i, x) takes their prefixes at i < nlist and their totals at i = nlist.  256 values per step: a wave scan +
+// the earlier waves' sums + the earlier steps' carry.
+template <int N, typename F, typename G>
+__device__ __forceinline__ void ivf_prefix256(int32_t nlist, F value, G store) {
+	__shared__ int32_t wsum[N][4];
+	const int wave = threadIdx.x >> 6;
+	int32_t carry[N] = {};   // (the same in every thread)
 	for (int32_t b = 0; b < nlist; b += 256) {
 		const int32_t i = b + threadIdx.x;
-		const int32_t c = i < nlist ? counts[i] : 0;
-		int32_t inc = c;
-		for (int d = 1; d < WAVE; d <<= 1) {
-			const int32_t t = __shfl_up(inc, d);
-			if (lane_id() >= d) inc += t;
+		int32_t c[N] = {}, inc[N], x[N];
+		if (i < nlist) value(i, c);
+#pragma unroll
+		for (int j = 0; j < N; ++j) inc[j] = c[j];
+		for (int d = 1; d < WAVE; d <<= 1)
+#pragma unroll
+			for (int j = 0; j < N; ++j) {
+				const int32_t t = __shfl_up(inc[j], d);
+				if (lane_id() >= d) inc[j] += t;
+			}
+#pragma unroll
+		for (int j = 0; j < N; ++j)
+			if (lane_id() == WAVE - 1) wsum[j][wave] = inc[j];
+		__syncthreads();
+#pragma unroll
+		for (int j = 0; j < N; ++j) {
+			x[j] = carry[j] + inc[j] - c[j];
+			for (int w = 0; w < wave; ++w) x[j] += wsum[j][w];
+			carry[j] += wsum[j][0] + wsum[j][1] + wsum[j][2] + wsum[j][3];
 		}
-		if (lane_id() == WAVE - 1) wsum[threadIdx.x >> 6] = inc;
-		__syncthreads();
-		int32_t base = carry;
-		for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) base += wsum[w];
-		if (i < nlist) offsets[i] = base + inc - c;
-		__syncthreads();
-		if (threadIdx.x == 255) carry = base + inc;
-		__syncthreads();
+		if (i < nlist) store(i, x);
+		__syncthreads();   // (wsum is rewritten by the next step)
 	}
-	if (threadIdx.x == 0) offsets[nlist] = carry;
+	if (threadIdx.x == 0) store(nlist, carry);
+}
+
+// offsets[0..nlist] = exclusive prefix sum of counts
+__global__ __launch_bounds__(256) void ivf_scan_counts_kernel(const int32_t *__restrict__ counts, int32_t nlist, int32_t *__restrict__ offsets) {
+	ivf_prefix256<1>(nlist, [&](int32_t l, int32_t (&c)[1]) { c[0] = counts[l]; }, [&](int32_t i, const int32_t (&x)[1]) { offsets[i] = x[0]; });
 }
 
 // ids[offsets[l] ..] = the points of list l in ascending id order (stable).  One workgroup per list; each of its four waves owns a
@@ -154,78 +169,25 @@ __global__ __launch_bounds__(SEL_THREADS) void ivf_scan_kernel(const float *__re
 	sel_finish<KMAX>(s, k, out_val + qi * (int64_t)k, out_idx + qi * (int64_t)k);
 }
 
-// ---- batched search: queries grouped by probed list, scored on the fp32 matrix cores --------------------------------------------
+// ---- batched search: queries grouped by probed list, scored on the matrix cores ---------------------------------------------------
 // The per-query kernel above reads every probed list once PER QUERY (nq x nprobe x list bytes through L2: 167 GB for 10^4 queries on
 // 10^5 x 768 vectors, 28 ms -- slower than the exact flat search of the same queries).  Batched, the (query, probe slot) pairs are sorted
 // by list (anncur_ivf_build_lists on the flattened probe array) and each list is one small GEMM: [pairs of the list x d] . [d x vectors
-// of the list], 64 x 64 output tiles from a host-built worklist, products and sums exact fp32 (v_mfma_f32_32x32x2_f32).  Scores go to
+// of the list] in 64 x 64 output tiles.  Two score layouts share the tile GEMM (ivf_tile64 below): SLOTTED here -- scores go to
 // S[pair][position in its list] (row pitch lmax, the caller pre-fills -inf), i.e. query q's row of S holds its nprobe lists side by
-// side: anncur_rowwise_topk over [nq x nprobe * lmax] + ivf_map_ids_kernel finish the search.
-constexpr int GT = 64, GK = 16, GP = GT + 1;   // tile edge, k-tile depth, LDS pitch (k-major tiles as in gemm.hip)
-
-// Device-built tile worklist (round 4).  Round 3 copied the pairs-per-list counts to the host, enumerated the (list, query tile, vector tile)
-// triples there and copied them back: a device synchronisation in the middle of every search.  Now tile_start[l] = number of tiles of the
-// lists before l (ivf_tile_starts_kernel: one workgroup, nlist is ~sqrt(n)); the GEMM is launched with an upper bound on the tile count
-// that the host knows without looking at the counts, and workgroup b finds its triple by a binary search (b >= tile_start[nlist]: exit).
-__global__ __launch_bounds__(256) void ivf_tile_starts_kernel(const int32_t *__restrict__ pair_off, const int32_t *__restrict__ offsets, int32_t nlist,
-															   int32_t *__restrict__ tile_start) {
-	__shared__ int32_t carry;
-	__shared__ int32_t wsum[4];
-	if (threadIdx.x == 0) carry = 0;
-	__syncthreads();
-	for (int32_t b = 0; b < nlist; b += 256) {
-		const int32_t l = b + threadIdx.x;
-		int32_t c = 0;
-		if (l < nlist) {
-			const int32_t qt = (pair_off[l + 1] - pair_off[l] + GT - 1) / GT, vt = (offsets[l + 1] - offsets[l] + GT - 1) / GT;
-			c = qt * vt;
-		}
-		int32_t inc = c;
-		for (int d = 1; d < WAVE; d <<= 1) {
-			const int32_t t = __shfl_up(inc, d);
-			if (lane_id() >= d) inc += t;
-		}
-		if (lane_id() == WAVE - 1) wsum[threadIdx.x >> 6] = inc;
-		__syncthreads();
-		int32_t base = carry;
-		for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) base += wsum[w];
-		if (l < nlist) tile_start[l] = base + inc - c;
-		__syncthreads();
-		if (threadIdx.x == 255) carry = base + inc;
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) tile_start[nlist] = carry;
-}
-// workgroup b -> (list, query tile, vector tile) from the host-built triples (nlist = 0) or the device-built starts; false: nothing to do
-__device__ __forceinline__ bool ivf_tile_of(const int32_t *__restrict__ tiles, int32_t nlist, const int32_t *__restrict__ offsets, int32_t &l, int32_t &qt, int32_t &vt) {
-	const int32_t b = blockIdx.x;
-	if (nlist <= 0) { l = tiles[3 * b]; qt = tiles[3 * b + 1]; vt = tiles[3 * b + 2]; return true; }
-	if (b >= tiles[nlist]) return false;
-	int32_t lo = 0, hi = nlist;   // largest l with tiles[l] <= b (empty lists repeat their start: the search lands past them)
-	while (hi - lo > 1) {
-		const int32_t mid = (lo + hi) >> 1;
-		if (tiles[mid] <= b) lo = mid; else hi = mid;
-	}
-	l = lo;
-	const int32_t vcnt = (offsets[l + 1] - offsets[l] + GT - 1) / GT, within = b - tiles[l];
-	qt = within / vcnt; vt = within - qt * vcnt;
-	return true;
-}
+// side: anncur_rowwise_topk over [nq x nprobe * lmax] + ivf_map_ids_kernel finish the search -- and PACKED further down.
+constexpr int GT = 64, GK = 16, GP = GT + 1;   // tile edge, fp32 k-tile depth, fp32 LDS pitch (k-major tiles as in gemm.hip)
 typedef __attribute__((ext_vector_type(16))) float f32x16g;
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8g;
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4g;
 
-__global__ __launch_bounds__(256) void ivf_group_scores_kernel(const float *__restrict__ Xs, int64_t ldx, int32_t dp, const int32_t *__restrict__ offsets,
-																const float *__restrict__ Q, int64_t ldq, int32_t nprobe, const int32_t *__restrict__ pair_ids,
-																const int32_t *__restrict__ pair_off, const int32_t *__restrict__ tiles, int32_t nlist, int64_t lmax,
-																float *__restrict__ S) {
+// The k loop of one 64 x 64 tile: tile row m = query row arow[m] of Q (-1: none, a zero row), tile column n = vector v0 + n of Xs (zero
+// from v_end on); wave (wm, wn) = (wave >> 1, wave & 1) accumulates its 32 x 32 block.  arow is in LDS and published by the caller's barrier.
+// fp32: products and sums exact fp32 (v_mfma_f32_32x32x2_f32), k-tiles of 16, k-major LDS tiles of pitch 65.
+__device__ __forceinline__ f32x16g ivf_tile64_mma(const float *__restrict__ Xs, int64_t ldx, int32_t dp, const float *__restrict__ Q, int64_t ldq,
+												   const int32_t *arow, int32_t v0, int32_t v_end) {
 	__shared__ float As[GK * GP], Bs[GK * GP];
-	__shared__ int32_t arow[GT];   // query row of each pair of the tile (-1 past the list's pairs)
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, r = lane & 31, h = lane >> 5;
-	int32_t l, qt, vt;
-	if (!ivf_tile_of(tiles, nlist, offsets, l, qt, vt)) return;   // (uniform: before any barrier)
-	const int32_t p0 = pair_off[l] + qt * GT, p_end = pair_off[l + 1];
-	const int32_t v0 = offsets[l] + vt * GT, v_end = offsets[l + 1];
-	if (tid < GT) arow[tid] = p0 + tid < p_end ? pair_ids[p0 + tid] / nprobe : -1;
-	__syncthreads();
 	// thread -> (row m, k) of the operand tiles: k fastest (16 consecutive floats of a row per 16 lanes)
 	const int kk = tid & 15, mm = tid >> 4;
 	f32x16g acc;
@@ -252,34 +214,17 @@ __global__ __launch_bounds__(256) void ivf_group_scores_kernel(const float *__re
 			acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(2 * ks + h) * GP + wm * 32 + r], Bs[(2 * ks + h) * GP + wn * 32 + r], acc, 0, 0, 0);
 		__syncthreads();
 	}
-	// C/D layout: col = lane & 31 (vector), row = (e & 3) + 8 (e >> 2) + 4 h (pair)
-#pragma unroll
-	for (int e = 0; e < 16; ++e) {
-		const int m = wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h, n = wn * 32 + r;
-		if (p0 + m < p_end && v0 + n < v_end) S[(int64_t)pair_ids[p0 + m] * lmax + (vt * GT + n)] = acc[e];
-	}
+	return acc;
 }
-
-// The same GEMM per list on the bf16 matrix cores (round 4: the index built with dtype = "bf16" keeps a bf16 copy of the list-ordered
-// vectors; the queries are rounded to bf16 per call): 64 x 64 output tiles as above, k-tiles of 32, v_mfma_f32_32x32x16_bf16 with fp32
-// accumulation.  Staging: every thread moves ONE 16-byte chunk (8 bf16) of a pair's query row and one of a vector per k-tile -- 64 rows
-// x 4 chunks -- into a [64 rows][4 chunks] LDS image whose chunk index is XOR-ed with (row >> 2) & 3 (rows are 64 bytes apart: a
-// ds_read_b128 of 16 rows x one chunk column then touches every bank group once); the next k-tile's chunks are in flight during the MFMAs.
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8g;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4g;
-__global__ __launch_bounds__(256) void ivf_group_scores_bf16_kernel(const uint16_t *__restrict__ Xs, int64_t ldx, int32_t dp, const int32_t *__restrict__ offsets,
-																	 const uint16_t *__restrict__ Q, int64_t ldq, int32_t nprobe, const int32_t *__restrict__ pair_ids,
-																	 const int32_t *__restrict__ pair_off, const int32_t *__restrict__ tiles, int32_t nlist, int64_t lmax,
-																	 float *__restrict__ S) {
+// bf16 (round 4: the index built with dtype = "bf16" keeps a bf16 copy of the list-ordered vectors; the queries are rounded to bf16 per
+// call): k-tiles of 32, v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  Staging: every thread moves ONE 16-byte chunk (8 bf16) of a
+// pair's query row and one of a vector per k-tile -- 64 rows x 4 chunks -- into a [64 rows][4 chunks] LDS image whose chunk index is
+// XOR-ed with (row >> 2) & 3 (rows are 64 bytes apart: a ds_read_b128 of 16 rows x one chunk column then touches every bank group
+// once); the next k-tile's chunks are in flight during the MFMAs.
+__device__ __forceinline__ f32x16g ivf_tile64_mma(const uint16_t *__restrict__ Xs, int64_t ldx, int32_t dp, const uint16_t *__restrict__ Q, int64_t ldq,
+												   const int32_t *arow, int32_t v0, int32_t v_end) {
 	__shared__ __attribute__((aligned(16))) u32x4g As[GT * 4], Bs[GT * 4];
-	__shared__ int32_t arow[GT];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, r = lane & 31, h = lane >> 5;
-	int32_t l, qt, vt;
-	if (!ivf_tile_of(tiles, nlist, offsets, l, qt, vt)) return;   // (uniform: before any barrier)
-	const int32_t p0 = pair_off[l] + qt * GT, p_end = pair_off[l + 1];
-	const int32_t v0 = offsets[l] + vt * GT, v_end = offsets[l + 1];
-	if (tid < GT) arow[tid] = p0 + tid < p_end ? pair_ids[p0 + tid] / nprobe : -1;
-	__syncthreads();
 	const int row = tid >> 2, ch = tid & 3;                 // this thread's chunk of the operand tiles
 	const int slot = row * 4 + (ch ^ ((row >> 2) & 3));
 	const int32_t qr = arow[row];
@@ -309,12 +254,81 @@ __global__ __launch_bounds__(256) void ivf_group_scores_bf16_kernel(const uint16
 		}
 		__syncthreads();
 	}
-	// C/D layout: col = lane & 31 (vector), row = (e & 3) + 8 (e >> 2) + 4 h (pair)
+	return acc;
+}
+// One 64 x 64 tile for either layout: tile row m < p_rows is query row arow[m] and writes its scores at S[obase[m] * ostride + c0 + n] (a
+// 64-bit product), n = the tile's vectors [v0, min(v0 + 64, v_end)).  arow (-1 from p_rows on) and obase are LDS arrays that the caller has
+// filled; the barrier is here.  ostride: the slotted route's row pitch, which it does not multiply in front of the barrier (a kernel
+// argument load and a 64-bit product on every tile's critical path); the packed route's bases are element offsets, ostride = 1.
+template <typename T>
+__device__ __forceinline__ void ivf_tile64(const T *__restrict__ Xs, int64_t ldx, int32_t dp, const T *__restrict__ Q, int64_t ldq, const int32_t *arow,
+											const uint32_t *obase, int64_t ostride, int32_t p_rows, int32_t v0, int32_t v_end, int32_t c0, float *__restrict__ S) {
+	__syncthreads();
+	const f32x16g acc = ivf_tile64_mma(Xs, ldx, dp, Q, ldq, arow, v0, v_end);
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1, r = lane & 31, h = lane >> 5;
+	// C/D layout: col = lane & 31 (vector), row = (e & 3) + 8 (e >> 2) + 4 h (pair).  The rows' bases first, all 16 (one LDS round trip, not one
+	// in front of every store).
+	const int m0 = wm * 32 + 4 * h, n = wn * 32 + r;
+	uint32_t ob[16];
 #pragma unroll
-	for (int e = 0; e < 16; ++e) {
-		const int m = wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h, n = wn * 32 + r;
-		if (p0 + m < p_end && v0 + n < v_end) S[(int64_t)pair_ids[p0 + m] * lmax + (vt * GT + n)] = acc[e];
+	for (int e = 0; e < 16; ++e) ob[e] = obase[m0 + (e & 3) + 8 * (e >> 2)];
+#pragma unroll
+	for (int e = 0; e < 16; ++e)
+		if (m0 + (e & 3) + 8 * (e >> 2) < p_rows && v0 + n < v_end) S[(int64_t)ob[e] * ostride + (c0 + n)] = acc[e];
+}
+
+// Device-built tile worklist (round 4).  Round 3 copied the pairs-per-list counts to the host, enumerated the (list, query tile, vector tile)
+// triples there and copied them back: a device synchronisation in the middle of every search.  Now tile_start[l] = number of tiles of the
+// lists before l (one workgroup, nlist is ~sqrt(n)); the GEMM is launched with an upper bound on the tile count that the host knows
+// without looking at the counts, and workgroup b finds its triple by a binary search (b >= tile_start[nlist]: exit).
+__global__ __launch_bounds__(256) void ivf_tile_starts_kernel(const int32_t *__restrict__ pair_off, const int32_t *__restrict__ offsets, int32_t nlist,
+															   int32_t *__restrict__ tile_start) {
+	ivf_prefix256<1>(nlist, [&](int32_t l, int32_t (&c)[1]) { c[0] = ((pair_off[l + 1] - pair_off[l] + GT - 1) / GT) * ((offsets[l + 1] - offsets[l] + GT - 1) / GT); },
+					 [&](int32_t i, const int32_t (&x)[1]) { tile_start[i] = x[0]; });
+}
+// workgroup b -> (list, query tile, vector tile); false: past the last tile, nothing to do
+__device__ __forceinline__ bool ivf_tile_of(const int32_t *__restrict__ tile_start, int32_t nlist, const int32_t *__restrict__ offsets, int32_t &l, int32_t &qt, int32_t &vt) {
+	const int32_t b = blockIdx.x;
+	if (b >= tile_start[nlist]) return false;
+	int32_t lo = 0, hi = nlist;   // largest l with tile_start[l] <= b (empty lists repeat their start: the search lands past them)
+	while (hi - lo > 1) {
+		const int32_t mid = (lo + hi) >> 1;
+		if (tile_start[mid] <= b) lo = mid; else hi = mid;
 	}
+	l = lo;
+	const int32_t vcnt = (offsets[l + 1] - offsets[l] + GT - 1) / GT, within = b - tile_start[l];
+	qt = within / vcnt; vt = within - qt * vcnt;
+	return true;
+}
+// The slotted tile: pair = q * nprobe + slot is row `pair` of S, pitch lmax.  pair * lmax stays 64-bit (nq * nprobe * lmax is not bounded here).
+template <typename T>
+__device__ __forceinline__ void ivf_group_scores_tile(const T *__restrict__ Xs, int64_t ldx, int32_t dp, const int32_t *__restrict__ offsets,
+													   const T *__restrict__ Q, int64_t ldq, int32_t nprobe, const int32_t *__restrict__ pair_ids,
+													   const int32_t *__restrict__ pair_off, const int32_t *__restrict__ tile_start, int32_t nlist, int64_t lmax,
+													   float *__restrict__ S) {
+	__shared__ int32_t arow[GT];
+	__shared__ uint32_t obase[GT];
+	int32_t l, qt, vt;
+	if (!ivf_tile_of(tile_start, nlist, offsets, l, qt, vt)) return;   // (uniform: before any barrier)
+	const int32_t p0 = pair_off[l] + qt * GT, p_rows = pair_off[l + 1] - p0;
+	if (threadIdx.x < GT) {
+		const int32_t pair = (int32_t)threadIdx.x < p_rows ? pair_ids[p0 + threadIdx.x] : -1;
+		arow[threadIdx.x] = pair >= 0 ? pair / nprobe : -1;
+		obase[threadIdx.x] = (uint32_t)pair;
+	}
+	ivf_tile64(Xs, ldx, dp, Q, ldq, arow, obase, lmax, p_rows, offsets[l] + vt * GT, offsets[l + 1], vt * GT, S);
+}
+__global__ __launch_bounds__(256) void ivf_group_scores_kernel(const float *__restrict__ Xs, int64_t ldx, int32_t dp, const int32_t *__restrict__ offsets,
+																const float *__restrict__ Q, int64_t ldq, int32_t nprobe, const int32_t *__restrict__ pair_ids,
+																const int32_t *__restrict__ pair_off, const int32_t *__restrict__ tiles, int32_t nlist, int64_t lmax,
+																float *__restrict__ S) {
+	ivf_group_scores_tile(Xs, ldx, dp, offsets, Q, ldq, nprobe, pair_ids, pair_off, tiles, nlist, lmax, S);
+}
+__global__ __launch_bounds__(256) void ivf_group_scores_bf16_kernel(const uint16_t *__restrict__ Xs, int64_t ldx, int32_t dp, const int32_t *__restrict__ offsets,
+																	 const uint16_t *__restrict__ Q, int64_t ldq, int32_t nprobe, const int32_t *__restrict__ pair_ids,
+																	 const int32_t *__restrict__ pair_off, const int32_t *__restrict__ tiles, int32_t nlist, int64_t lmax,
+																	 float *__restrict__ S) {
+	ivf_group_scores_tile(Xs, ldx, dp, offsets, Q, ldq, nprobe, pair_ids, pair_off, tiles, nlist, lmax, S);
 }
 
 // column of the [nq x nprobe * lmax] score matrix -> id of the vector: slot = col / lmax, position = col % lmax in list probe[q, slot]
@@ -398,32 +412,8 @@ __global__ __launch_bounds__(256) void ivf_layout_kernel(const int32_t *__restri
 // counts, tile = T pairs x T vectors.  One workgroup.
 __global__ __launch_bounds__(256) void ivf_pair_offsets_kernel(const int32_t *__restrict__ counts, const int32_t *__restrict__ offsets, int32_t nlist, int32_t T,
 																int32_t *__restrict__ pair_off, int32_t *__restrict__ cursor, int32_t *__restrict__ tile_start) {
-	__shared__ int32_t carry[2];
-	__shared__ int32_t wsum[2][4];
-	if (threadIdx.x < 2) carry[threadIdx.x] = 0;
-	__syncthreads();
-	for (int32_t b = 0; b < nlist; b += 256) {
-		const int32_t l = b + threadIdx.x;
-		int32_t c0 = 0, c1 = 0;
-		if (l < nlist) {
-			c0 = counts[l];
-			c1 = ((c0 + T - 1) / T) * ((offsets[l + 1] - offsets[l] + T - 1) / T);
-		}
-		int32_t i0 = c0, i1 = c1;
-		for (int d = 1; d < WAVE; d <<= 1) {
-			const int32_t t0 = __shfl_up(i0, d), t1 = __shfl_up(i1, d);
-			if (lane_id() >= d) { i0 += t0; i1 += t1; }
-		}
-		if (lane_id() == WAVE - 1) { wsum[0][threadIdx.x >> 6] = i0; wsum[1][threadIdx.x >> 6] = i1; }
-		__syncthreads();
-		int32_t b0 = carry[0], b1 = carry[1];
-		for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) { b0 += wsum[0][w]; b1 += wsum[1][w]; }
-		if (l < nlist) { pair_off[l] = b0 + i0 - c0; cursor[l] = b0 + i0 - c0; tile_start[l] = b1 + i1 - c1; }
-		__syncthreads();
-		if (threadIdx.x == 255) { carry[0] = b0 + i0; carry[1] = b1 + i1; }
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) { pair_off[nlist] = carry[0]; tile_start[nlist] = carry[1]; }
+	ivf_prefix256<2>(nlist, [&](int32_t l, int32_t (&c)[2]) { c[0] = counts[l]; c[1] = ((c[0] + T - 1) / T) * ((offsets[l + 1] - offsets[l] + T - 1) / T); },
+					 [&](int32_t i, const int32_t (&x)[2]) { pair_off[i] = x[0]; tile_start[i] = x[1]; if (i < nlist) cursor[i] = x[0]; });
 }
 
 // pairs -> their lists' ranges: pair_q[pos] = query row, pair_out[pos] = element offset of the pair's scores in S (q * pitch + coff).
@@ -470,92 +460,26 @@ __device__ __forceinline__ void ivf_find_tile(const int32_t *__restrict__ tile_s
 	qt = within / vcnt; vt = within - qt * vcnt;
 }
 
-// The round-3/4 tile kernels (64 x 64; fp32 lists, and bf16 rows whose length is not a multiple of 128) on the packed layout.
+// The 64 x 64 tile GEMM (fp32 lists, and bf16 rows whose length is not a multiple of 128) on the packed layout.
 template <typename T>
 __global__ __launch_bounds__(256) void ivf_tile64_packed_kernel(const T *__restrict__ Xs, int64_t ldx, int32_t dp, const int32_t *__restrict__ offsets,
 																 const T *__restrict__ Q, int64_t ldq, const int32_t *__restrict__ pair_q,
 																 const uint32_t *__restrict__ pair_out, const int32_t *__restrict__ pair_off,
 																 const int32_t *__restrict__ tile_start, int32_t nlist, float *__restrict__ S) {
-	constexpr bool F32 = sizeof(T) == 4;
-	__shared__ __attribute__((aligned(16))) unsigned char tiles_lds[F32 ? 2 * GK * GP * 4 : 2 * GT * 64];
 	__shared__ int32_t arow[GT];
-	__shared__ uint32_t orow[GT];
+	__shared__ uint32_t obase[GT];
 	__shared__ int32_t meta[2];
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, r = lane & 31, h = lane >> 5;
 	const int32_t n_tiles = min(tile_start[nlist], (int32_t)gridDim.x);   // (the grid is the caller's bound on the tile count)
 	if ((int32_t)blockIdx.x >= n_tiles) return;   // (uniform: before any barrier)
 	int32_t l, qt, vt;
 	ivf_find_tile(tile_start, nlist, offsets, GT, ivf_xcd_remap((int)blockIdx.x, n_tiles), meta, l, qt, vt);
-	const int32_t p0 = pair_off[l] + qt * GT, p_end = pair_off[l + 1];
-	const int32_t v0 = offsets[l] + vt * GT, v_end = offsets[l + 1];
-	if (tid < GT) {
-		const bool in = p0 + tid < p_end;
-		arow[tid] = in ? pair_q[p0 + tid] : -1;
-		orow[tid] = in ? pair_out[p0 + tid] : 0u;
+	const int32_t p0 = pair_off[l] + qt * GT, p_rows = pair_off[l + 1] - p0;
+	if (threadIdx.x < GT) {
+		const bool in = (int32_t)threadIdx.x < p_rows;
+		arow[threadIdx.x] = in ? pair_q[p0 + threadIdx.x] : -1;
+		obase[threadIdx.x] = in ? pair_out[p0 + threadIdx.x] : 0u;
 	}
-	__syncthreads();
-	f32x16g acc;
-#pragma unroll
-	for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-	if constexpr (F32) {
-		float *As = reinterpret_cast<float *>(tiles_lds), *Bs = As + GK * GP;
-		const int kk = tid & 15, mm = tid >> 4;
-		float ra[4], rb[4];
-		auto load = [&](int k0) {
-#pragma unroll
-			for (int p = 0; p < 4; ++p) {
-				const int m = mm + 16 * p;
-				const int32_t qr = arow[m];
-				ra[p] = (qr >= 0 && k0 + kk < dp) ? Q[(int64_t)qr * ldq + k0 + kk] : 0.f;
-				rb[p] = (v0 + m < v_end && k0 + kk < dp) ? Xs[(int64_t)(v0 + m) * ldx + k0 + kk] : 0.f;
-			}
-		};
-		load(0);
-		for (int k0 = 0; k0 < dp; k0 += GK) {
-#pragma unroll
-			for (int p = 0; p < 4; ++p) { As[kk * GP + mm + 16 * p] = ra[p]; Bs[kk * GP + mm + 16 * p] = rb[p]; }
-			__syncthreads();
-			if (k0 + GK < dp) load(k0 + GK);
-#pragma unroll
-			for (int ks = 0; ks < GK / 2; ++ks)
-				acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(2 * ks + h) * GP + wm * 32 + r], Bs[(2 * ks + h) * GP + wn * 32 + r], acc, 0, 0, 0);
-			__syncthreads();
-		}
-	} else {
-		u32x4g *As = reinterpret_cast<u32x4g *>(tiles_lds), *Bs = As + GT * 4;
-		const int row = tid >> 2, ch = tid & 3;
-		const int slot = row * 4 + (ch ^ ((row >> 2) & 3));
-		const int32_t qr = arow[row];
-		const uint16_t *ap = qr >= 0 ? reinterpret_cast<const uint16_t *>(Q) + (int64_t)qr * ldq + ch * 8 : nullptr;
-		const uint16_t *bp = v0 + row < v_end ? reinterpret_cast<const uint16_t *>(Xs) + (int64_t)(v0 + row) * ldx + ch * 8 : nullptr;
-		const u32x4g zero = {0u, 0u, 0u, 0u};
-		u32x4g ra, rb;
-		auto load = [&](int k0) {
-			const bool in = k0 + ch * 8 < dp;
-			ra = (ap && in) ? *reinterpret_cast<const u32x4g *>(ap + k0) : zero;
-			rb = (bp && in) ? *reinterpret_cast<const u32x4g *>(bp + k0) : zero;
-		};
-		load(0);
-		for (int k0 = 0; k0 < dp; k0 += 32) {
-			As[slot] = ra; Bs[slot] = rb;
-			__syncthreads();
-			if (k0 + 32 < dp) load(k0 + 32);
-#pragma unroll
-			for (int ks = 0; ks < 2; ++ks) {
-				const int ra_row = wm * 32 + r, rb_row = wn * 32 + r, c = 2 * ks + h;
-				const bf16x8g a = __builtin_bit_cast(bf16x8g, As[ra_row * 4 + (c ^ ((ra_row >> 2) & 3))]);
-				const bf16x8g b = __builtin_bit_cast(bf16x8g, Bs[rb_row * 4 + (c ^ ((rb_row >> 2) & 3))]);
-				acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-			}
-			__syncthreads();
-		}
-	}
-	// C/D layout: col = lane & 31 (vector), row = (e & 3) + 8 (e >> 2) + 4 h (pair)
-#pragma unroll
-	for (int e = 0; e < 16; ++e) {
-		const int m = wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h, n = wn * 32 + r;
-		if (p0 + m < p_end && v0 + n < v_end) S[(int64_t)orow[m] + (vt * GT + n)] = acc[e];
-	}
+	ivf_tile64(Xs, ldx, dp, Q, ldq, arow, obase, 1, p_rows, offsets[l] + vt * GT, offsets[l + 1], vt * GT, S);
 }
 
 // ---- bf16, 128 pairs x 128 vectors per tile (round 5).  Four waves, wave (wm, wn) owns pairs [64 wm, +64) x vectors [64 wn, +64): 2 x 2
@@ -814,32 +738,6 @@ __global__ __launch_bounds__(256) void ivf_map_ids_packed_kernel(const int32_t *
 }
 
 }  // namespace
-
-extern "C" int anncur_ivf_group_scores(const float *Xs, int64_t ldx, int32_t dp, const int32_t *offsets, const float *Q, int64_t ldq, int32_t nprobe,
-									   const int32_t *pair_ids, const int32_t *pair_offsets, const int32_t *tiles, int32_t n_tiles, int64_t lmax, float *S,
-									   void *stream) {
-	ANNCUR_REQUIRE(dp >= 1 && ldx >= dp && ldq >= dp && nprobe >= 1 && lmax >= 1 && n_tiles >= 0, ANNCUR_E_INVALID, "ivf_group_scores: bad sizes");
-	if (n_tiles == 0) return ANNCUR_OK;
-	ANNCUR_REQUIRE(Xs && offsets && Q && pair_ids && pair_offsets && tiles && S, ANNCUR_E_INVALID, "ivf_group_scores: null pointer");
-	hipLaunchKernelGGL(ivf_group_scores_kernel, dim3((unsigned)n_tiles), dim3(256), 0, (hipStream_t)stream, Xs, ldx, dp, offsets, Q, ldq, nprobe, pair_ids,
-					   pair_offsets, tiles, 0, lmax, S);
-	ANNCUR_LAUNCH_OK();
-	return ANNCUR_OK;
-}
-
-extern "C" int anncur_ivf_group_scores_bf16(const void *Xs, int64_t ldx, int32_t dp, const int32_t *offsets, const void *Q, int64_t ldq, int32_t nprobe,
-											const int32_t *pair_ids, const int32_t *pair_offsets, const int32_t *tiles, int32_t n_tiles, int64_t lmax, float *S,
-											void *stream) {
-	ANNCUR_REQUIRE(dp >= 16 && (dp % 16) == 0 && ldx >= dp && ldq >= dp && (ldx % 8) == 0 && (ldq % 8) == 0 && nprobe >= 1 && lmax >= 1 && n_tiles >= 0,
-				   ANNCUR_E_INVALID, "ivf_group_scores_bf16: bad sizes (rows zero-padded to a multiple of 16 elements, 16-byte aligned)");
-	if (n_tiles == 0) return ANNCUR_OK;
-	ANNCUR_REQUIRE(Xs && offsets && Q && pair_ids && pair_offsets && tiles && S && ((uintptr_t)Xs % 16) == 0 && ((uintptr_t)Q % 16) == 0, ANNCUR_E_INVALID,
-				   "ivf_group_scores_bf16: null or misaligned pointer");
-	hipLaunchKernelGGL(ivf_group_scores_bf16_kernel, dim3((unsigned)n_tiles), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)Xs, ldx, dp, offsets,
-					   (const uint16_t *)Q, ldq, nprobe, pair_ids, pair_offsets, tiles, 0, lmax, S);
-	ANNCUR_LAUNCH_OK();
-	return ANNCUR_OK;
-}
 
 extern "C" int anncur_ivf_group_scores_dev(const void *Xs, int dtype, int64_t ldx, int32_t dp, const int32_t *offsets, int32_t nlist, const void *Q, int64_t ldq,
 										   int32_t nprobe, const int32_t *pair_ids, const int32_t *pair_offsets, int32_t *tile_start, int32_t max_tiles, int64_t lmax,

@@ -71,7 +71,7 @@ int anncur_event_pool(hipEvent_t **out, int n) {
 }
 
 
-extern "C" int anncur_version(void) { return 1000 * 0 + 3; }
+extern "C" int anncur_version(void) { return 1000 * 0 + 4; }
 
 extern "C" const char *anncur_last_error(void) { return g_err; }
 

@@ -653,31 +653,42 @@ def filter_topk(val, idx, exclude, k_out):
 FUSED_WS_LIMIT_BYTES = 32 << 30   # default workspace above this size -> score_topk_fused runs the queries in row chunks
 
 
-class _Workspace:
-	"""Grow-only device scratch for the fused kernel (one per device)."""
-	_bufs = {}
-
-	@classmethod
-	def get(cls, nbytes, device):
-		key = (device.type, device.index)
-		buf = cls._bufs.get(key)
-		if buf is None or buf.numel() < nbytes:
-			cls._bufs[key] = buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-		off = (-buf.data_ptr()) % 256
-		return buf[off:off + nbytes]
+def _aligned_bytes(n, device, buf=None):
+	"""A 256-byte aligned uint8 tensor of n bytes: freshly allocated, or inside `buf` (uint8, n + 256 bytes or more)."""
+	if buf is None:
+		buf = torch.empty(n + 256, dtype=torch.uint8, device=device)
+	off = (-buf.data_ptr()) % 256
+	return buf[off:off + n]
 
 
-class _ScoreScratch:
-	"""Grow-only fp32 scratch per device (the batched IVF search's score matrix)."""
-	_bufs = {}
+class _Scratch:
+	"""Grow-only device scratch: one buffer per device in each subclass' own _bufs (the subclasses never share memory).  A byte scratch
+	hands out 256-byte aligned views and keeps 256 bytes of room for that; an element scratch hands out the buffer's front."""
+	_dtype, _room = torch.uint8, 256
 
 	@classmethod
 	def get(cls, n, device):
 		key = (device.type, device.index)
 		buf = cls._bufs.get(key)
-		if buf is None or buf.numel() < n:
-			cls._bufs[key] = buf = torch.empty(n, dtype=torch.float32, device=device)
-		return buf[:n]
+		if buf is None or buf.numel() < n + cls._room:
+			cls._bufs[key] = buf = torch.empty(n + cls._room, dtype=cls._dtype, device=device)
+		return _aligned_bytes(n, device, buf) if cls._room else buf[:n]
+
+
+class _Workspace(_Scratch):
+	"""The fused kernels' workspace."""
+	_bufs = {}
+
+
+class _ScoreScratch(_Scratch):
+	"""fp32 elements: the batched IVF searches' score matrix."""
+	_bufs = {}
+	_dtype, _room = torch.float32, 0
+
+
+class _ByteScratch(_Scratch):
+	"""The workspace of ivf_search_grouped."""
+	_bufs = {}
 
 
 def fused_supported(Q, I, Kp, k):
@@ -690,9 +701,7 @@ def fused_workspace(Q, I, Kp, k, device):
 	nbytes = _lib.load().anncur_score_topk_workspace_bytes(Q, I, Kp, k)
 	if nbytes == 0:
 		raise _lib.AnncurHipError(f"score_topk: shape (Q={Q}, I={I}, Kp={Kp}, k={k}) is outside the fused path")
-	buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-	off = (-buf.data_ptr()) % 256
-	return buf[off:off + nbytes]
+	return _aligned_bytes(nbytes, device)
 
 
 def _item_ids_arg(item_ids, I, device):
@@ -821,9 +830,7 @@ def few_workspace(Q, I, Kp, k, device):
 	"""A private workspace for score_topk_few (256-byte aligned uint8 tensor), as fused_workspace."""
 	_few_check("few_workspace", Q, I, Kp, k)
 	nbytes = _lib.load().anncur_score_topk_few_workspace_bytes(Q, I, Kp, k)
-	buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-	off = (-buf.data_ptr()) % 256
-	return buf[off:off + nbytes]
+	return _aligned_bytes(nbytes, device)
 
 
 @_on_device
@@ -2189,10 +2196,37 @@ def ivf_scan(Xs, offsets, ids, Q, probe, k):
 	return TopK(val, idx)
 
 
+def _ivf_max_tiles(n_pairs, sizes_host, T):
+	"""An upper bound on the number of T-pair x T-vector tiles of a batched search that needs no look at the pairs-per-list counts (they stay
+	on the device: no synchronisation inside a search): sum_l ceil(pairs_l / T) vt_l <= (pairs // T) max_l vt_l + sum_l vt_l, vt_l =
+	ceil(size_l / T).  Workgroups past the last tile exit."""
+	vt = -(-sizes_host // T)
+	return (n_pairs // T) * int(max(int(vt.max()), 1)) + int(vt.sum())
+
+
+def _ivf_chunked(nq_all, step, k, k_eff, device, run):
+	"""The query-chunk loop of the batched searches: run(q0, q1, out_val, out_idx) fills the [q1 - q0 x k_eff] results of queries q0 .. q1 - 1
+	-- rows of the [nq_all x k] outputs themselves when k_eff == k, temporaries otherwise: no more than k_eff vectors can be found, and the
+	rows' tails are (-inf, -1)."""
+	val = torch.empty((nq_all, k), dtype=torch.float32, device=device)
+	idx = torch.empty((nq_all, k), dtype=torch.int32, device=device)
+	for q0 in range(0, nq_all, step):
+		q1 = min(nq_all, q0 + step)
+		if k_eff == k:
+			run(q0, q1, val[q0:q1], idx[q0:q1])
+			continue
+		ov = torch.empty((q1 - q0, k_eff), dtype=torch.float32, device=device)
+		oi = torch.empty((q1 - q0, k_eff), dtype=torch.int32, device=device)
+		run(q0, q1, ov, oi)
+		val[q0:q1, :k_eff] = ov; idx[q0:q1, :k_eff] = oi
+		val[q0:q1, k_eff:] = float("-inf"); idx[q0:q1, k_eff:] = -1
+	return TopK(val, idx)
+
+
 @_on_device
 def ivf_scan_grouped(Xs, offsets, ids, sizes_host, Q, probe, k, max_bytes=8 << 30, lists_bf16=None, profile=None):
-	"""The same search as ivf_scan for MANY queries: pairs (query, probe slot) sorted by list, every list one small fp32-MFMA GEMM against
-	its pairs' queries (anncur_ivf_group_scores), then the exact scan over each query's nprobe lists side by side and the column -> id map.
+	"""The same search as ivf_scan for MANY queries: pairs (query, probe slot) sorted by list, every list one small MFMA GEMM against its
+	pairs' queries (anncur_ivf_group_scores_dev), then the exact scan over each query's nprobe lists side by side and the column -> id map.
 	sizes_host: the lists' lengths on the host (numpy int64, known since add()); they bound the tile count of the launch, the worklist itself is
 	built on the device (no synchronisation inside the call: the search is stream-ordered like every other op).
 	lists_bf16: a bf16 copy of Xs (same layout) -> the per-list GEMMs run on the bf16 matrix cores (queries rounded to bf16 here).
@@ -2203,50 +2237,34 @@ def ivf_scan_grouped(Xs, offsets, ids, sizes_host, Q, probe, k, max_bytes=8 << 3
 	nq_all, dp = Q.shape
 	probe = probe.to(torch.int32).contiguous()
 	nprobe, nlist = probe.shape[1], sizes_host.shape[0]
-	lmax = int(max(int(sizes_host.max()), 1))
-	lmax = -(-lmax // 8) * 8
-	k_eff = min(k, nprobe * lmax)
-	val = torch.empty((nq_all, k), dtype=torch.float32, device=Q.device)
-	idx = torch.empty((nq_all, k), dtype=torch.int32, device=Q.device)
-	step = max(64, min(nq_all, max_bytes // (nprobe * lmax * 4)))
-	vt = -(-sizes_host // 64)                                        # 64-vector tiles per list
-	vt_sum, vt_max = int(vt.sum()), int(max(int(vt.max()), 1))
-	for q0 in range(0, nq_all, step):
-		q1 = min(nq_all, q0 + step)
-		nq = q1 - q0
+	lmax = -(-max(int(sizes_host.max()), 1) // 8) * 8
+	lists = Xs if lists_bf16 is None else lists_bf16
+
+	def run(q0, q1, ov, oi):
+		nq, k_eff = ov.shape
 		pr = probe[q0:q1].contiguous()
 		cnt, poff, pair_ids = ivf_build_lists(pr.reshape(-1).clamp(min=0), nlist)     # (probe slots are valid list ids here: nprobe <= nlist)
-		# tile worklist built on the device (round 4: round 3 copied the pairs-per-list counts to the host here -- a synchronisation in the
-		# middle of every search -- and built the triples in numpy): the launch takes an upper bound on the number of 64 x 64 tiles that
-		# needs no look at the counts, sum_l ceil(pairs_l / 64) vt_l <= (pairs / 64) max vt + sum vt; workgroups past the last tile exit
-		max_tiles = (nq * nprobe // 64) * vt_max + vt_sum
+		max_tiles = _ivf_max_tiles(nq * nprobe, sizes_host, 64)
 		tile_start = torch.empty(nlist + 1, dtype=torch.int32, device=Q.device)
 		S = _ScoreScratch.get(nq * nprobe * lmax, Q.device).view(nq, nprobe * lmax)   # grow-only scratch: a fresh 100s-of-MB allocation per call cost more than the search
 		S.fill_(float("-inf"))
-		Qc = Q[q0:q1]
 		if profile is not None:
 			evs = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
 			profile.setdefault("events", []).append(evs)
 			profile.setdefault("max_tiles", []).append(int(max_tiles))
 			profile.setdefault("tile_starts", []).append(tile_start)
 			evs[0].record()
-		if lists_bf16 is not None:
-			Qb = convert(Qc, torch.bfloat16)
-			check(lib.anncur_ivf_group_scores_dev(_p(lists_bf16), BF16, _ld(lists_bf16), dp, _p(offsets), nlist, _p(Qb), _ld(Qb), nprobe, _p(pair_ids), _p(poff),
-												  _p(tile_start), max_tiles, lmax, _p(S), _stream()), "ivf_group_scores_dev")
-		else:
-			check(lib.anncur_ivf_group_scores_dev(_p(Xs), F32, _ld(Xs), dp, _p(offsets), nlist, _p(Qc), _ld(Qc), nprobe, _p(pair_ids), _p(poff),
-												  _p(tile_start), max_tiles, lmax, _p(S), _stream()), "ivf_group_scores_dev")
+		Qc = Q[q0:q1] if lists_bf16 is None else convert(Q[q0:q1], torch.bfloat16)
+		check(lib.anncur_ivf_group_scores_dev(_p(lists), _dt(lists), _ld(lists), dp, _p(offsets), nlist, _p(Qc), _ld(Qc), nprobe, _p(pair_ids), _p(poff),
+											  _p(tile_start), max_tiles, lmax, _p(S), _stream()), "ivf_group_scores_dev")
 		if profile is not None: evs[1].record()
 		v, c = rowwise_topk(S, k_eff)
-		out_i = idx[q0:q1, :k_eff] if k_eff == k else torch.empty((nq, k_eff), dtype=torch.int32, device=Q.device)
-		check(lib.anncur_ivf_map_ids(_p(c), _p(v), nq, k_eff, lmax, _p(pr), nprobe, _p(offsets), _p(ids), _p(out_i), _stream()), "ivf_map_ids")
+		check(lib.anncur_ivf_map_ids(_p(c), _p(v), nq, k_eff, lmax, _p(pr), nprobe, _p(offsets), _p(ids), _p(oi), _stream()), "ivf_map_ids")
 		if profile is not None: evs[2].record()
-		val[q0:q1, :k_eff] = v
-		if k_eff < k:
-			idx[q0:q1, :k_eff] = out_i
-			val[q0:q1, k_eff:] = float("-inf"); idx[q0:q1, k_eff:] = -1
-	return TopK(val, idx)
+		ov.copy_(v)
+
+	step = max(64, min(nq_all, max_bytes // (nprobe * lmax * 4)))
+	return _ivf_chunked(nq_all, step, k, min(k, nprobe * lmax), Q.device, run)
 
 
 IVF_GROUPED_MAX_K, IVF_GROUPED_MAX_NLIST = 128, 8192
@@ -2255,20 +2273,6 @@ IVF_GROUPED_MAX_K, IVF_GROUPED_MAX_NLIST = 128, 8192
 def ivf_search_grouped_ok(k, nlist):
 	"""True where ivf_search_grouped serves the search (the wave-per-row scan's k, list histograms in LDS); ivf_scan_grouped otherwise."""
 	return k <= IVF_GROUPED_MAX_K and nlist <= IVF_GROUPED_MAX_NLIST
-
-
-class _ByteScratch:
-	"""Grow-only 256-byte aligned workspace per device (ivf_search_grouped)."""
-	_bufs = {}
-
-	@classmethod
-	def get(cls, n, device):
-		key = (device.type, device.index)
-		buf = cls._bufs.get(key)
-		if buf is None or buf.numel() < n + 256:
-			cls._bufs[key] = buf = torch.empty(n + 256, dtype=torch.uint8, device=device)
-		off = (-buf.data_ptr()) % 256
-		return buf[off:off + n]
 
 
 @_on_device
@@ -2285,35 +2289,22 @@ def ivf_search_grouped(lists, offsets, ids, sizes_host, Q, probe, k, max_bytes=8
 	nq_all, dp = Q.shape
 	probe = probe.to(torch.int32).contiguous()
 	nprobe, nlist = probe.shape[1], sizes_host.shape[0]
-	lmax = int(max(int(sizes_host.max()), 1))
+	lmax = max(int(sizes_host.max()), 1)
 	k_eff = min(k, nprobe * lmax)
 	pitch = -(-max(nprobe * lmax, k_eff) // 8) * 8                 # any row fits: nprobe lists of at most lmax vectors
-	val = torch.empty((nq_all, k), dtype=torch.float32, device=Q.device)
-	idx = torch.empty((nq_all, k), dtype=torch.int32, device=Q.device)
-	step = max(64, min(nq_all, max_bytes // (pitch * 4), ((1 << 32) - 1) // pitch))
-	for q0 in range(0, nq_all, step):
-		q1 = min(nq_all, q0 + step)
-		nq = q1 - q0
-		Qc = Q[q0:q1]
+
+	def run(q0, q1, ov, oi):
+		nq, Qc, pr = q1 - q0, Q[q0:q1], probe[q0:q1]
 		T = int(lib.anncur_ivf_search_tile(_dt(lists), dp, _ld(lists), _ld(Qc), nq))
-		vt = -(-sizes_host // T)
-		max_tiles = (nq * nprobe // T) * int(max(int(vt.max()), 1)) + int(vt.sum())    # sum_l ceil(pairs_l / T) vt_l <= (pairs / T) max vt + sum vt
-		if _skip_gemm: max_tiles = 0
+		max_tiles = 0 if _skip_gemm else _ivf_max_tiles(nq * nprobe, sizes_host, T)
 		S = _ScoreScratch.get(nq * pitch, Q.device)
 		nbytes = lib.anncur_ivf_search_workspace_bytes(nq, nprobe, nlist, k_eff, max_tiles)
 		ws = _ByteScratch.get(nbytes, Q.device)
-		pr = probe[q0:q1]
-		if k_eff == k:
-			ov, oi = val[q0:q1], idx[q0:q1]
-		else:
-			ov = torch.empty((nq, k_eff), dtype=torch.float32, device=Q.device)
-			oi = torch.empty((nq, k_eff), dtype=torch.int32, device=Q.device)
 		check(lib.anncur_ivf_search_grouped(_p(lists), _dt(lists), _ld(lists), dp, _p(offsets), _p(ids), nlist, _p(Qc), _ld(Qc), nq, _p(pr), nprobe, k_eff, max_tiles,
 											_p(S), pitch, _p(ws), nbytes, _p(ov), _p(oi), _stream()), "ivf_search_grouped")
-		if k_eff < k:
-			val[q0:q1, :k_eff] = ov; idx[q0:q1, :k_eff] = oi
-			val[q0:q1, k_eff:] = float("-inf"); idx[q0:q1, k_eff:] = -1
-	return TopK(val, idx)
+
+	step = max(64, min(nq_all, max_bytes // (pitch * 4), ((1 << 32) - 1) // pitch))
+	return _ivf_chunked(nq_all, step, k, k_eff, Q.device, run)
 
 
 @_on_device

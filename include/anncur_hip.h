@@ -737,23 +737,18 @@ int anncur_ivf_scan(const float *Xs, int64_t ldx, int32_t dp, const int32_t *off
 /* Batched IVF search (many queries, e.g. the reference's hard-negative mining, utils/data_process.py:343-365, where every mention
  * queries the index): the (query, probe slot) pairs are sorted by list -- anncur_ivf_build_lists on the flattened probe array gives
  * pair_offsets[nlist+1] and pair_ids (pair = q * nprobe + slot) -- and every list is scored against its pairs' queries as a small GEMM on
- * the fp32 matrix cores, so a list's vectors are read once per 64 queries instead of once per query.  tiles int32[n_tiles x 3] =
- * (list, 64-pair tile, 64-vector tile) worklist built by the host from the list / pair counts.  S float[nq * nprobe x lmax] (lmax >=
- * longest list), pre-filled with -inf by the caller: S[pair][position in its list] = <query, vector>.  Then anncur_rowwise_topk over
- * S viewed as [nq x nprobe * lmax] and anncur_ivf_map_ids (column -> id of the vector; -1 where the score is the -inf padding). */
-int anncur_ivf_group_scores(const float *Xs, int64_t ldx, int32_t dp, const int32_t *offsets, const float *Q, int64_t ldq, int32_t nprobe,
-                            const int32_t *pair_ids, const int32_t *pair_offsets, const int32_t *tiles, int32_t n_tiles, int64_t lmax, float *S,
-                            void *stream);
-/* The same on bf16 operands (Xs / Q: bf16 rows zero-padded to dp elements, dp a multiple of 16, 16-byte aligned; an index built with
- * dtype = "bf16" keeps such a copy of its lists): v_mfma_f32_32x32x16_bf16, fp32 accumulation, fp32 scores. */
-int anncur_ivf_group_scores_bf16(const void *Xs, int64_t ldx, int32_t dp, const int32_t *offsets, const void *Q, int64_t ldq, int32_t nprobe,
-                                 const int32_t *pair_ids, const int32_t *pair_offsets, const int32_t *tiles, int32_t n_tiles, int64_t lmax, float *S,
-                                 void *stream);
-/* The same with the tile worklist built ON THE DEVICE (no host look at the pairs-per-list counts, no synchronisation inside a search):
- * tile_start int32[nlist + 1] is filled here (tile_start[l] = tiles of the lists before l, a tile = 64 pairs x 64 vectors), the GEMM is
- * launched with max_tiles workgroups -- any upper bound on sum_l ceil(pairs_l / 64) ceil(size_l / 64), e.g.
- * (n_pairs / 64) * max_l ceil(size_l / 64) + sum_l ceil(size_l / 64) -- and workgroup b finds its (list, pair tile, vector tile) by binary
- * search; workgroups past the last tile exit.  dtype ANNCUR_F32 (Xs / Q fp32) or ANNCUR_BF16 (bf16 rows as anncur_ivf_group_scores_bf16). */
+ * the matrix cores, in 64-pair x 64-vector tiles, so a list's vectors are read once per 64 queries instead of once per query.
+ * SLOTTED scores: S float[nq * nprobe x lmax] (lmax >= longest list), pre-filled with -inf by the caller; row pair = q * nprobe + slot
+ * holds S[pair][position in its list] = <query, vector>.  Then anncur_rowwise_topk over S viewed as [nq x nprobe * lmax] and
+ * anncur_ivf_map_ids (column -> id of the vector; -1 where the score is the -inf padding).
+ * Operands: dtype ANNCUR_F32 -- Xs / Q fp32 rows of dp >= 1 floats, products and sums exact fp32 (v_mfma_f32_32x32x2_f32) -- or
+ * ANNCUR_BF16 -- Xs / Q bf16 rows zero-padded to dp elements, dp a multiple of 16, ldx / ldq multiples of 8, 16-byte aligned (an index
+ * built with dtype = "bf16" keeps such a copy of its lists): v_mfma_f32_32x32x16_bf16, fp32 accumulation, fp32 scores.
+ * The tile worklist is built ON THE DEVICE (no host look at the pairs-per-list counts, no synchronisation inside a search):
+ * tile_start int32[nlist + 1] is filled here (tile_start[l] = tiles of the lists before l), the GEMM is launched with max_tiles
+ * workgroups -- any upper bound on sum_l ceil(pairs_l / 64) ceil(size_l / 64), e.g. (n_pairs / 64) * max_l ceil(size_l / 64) +
+ * sum_l ceil(size_l / 64) -- and workgroup b finds its (list, pair tile, vector tile) by binary search; workgroups past the last tile
+ * exit (max_tiles = 0: tile_start only). */
 int anncur_ivf_group_scores_dev(const void *Xs, int dtype, int64_t ldx, int32_t dp, const int32_t *offsets, int32_t nlist, const void *Q, int64_t ldq,
                                 int32_t nprobe, const int32_t *pair_ids, const int32_t *pair_offsets, int32_t *tile_start, int32_t max_tiles, int64_t lmax,
                                 float *S, void *stream);
@@ -764,9 +759,9 @@ int anncur_ivf_map_ids(const int32_t *col, const float *val, int64_t nq, int32_t
  * the reference's hard-negative mining drives it (utils/data_process.py:343-365).  From the probed lists (probe int32[nq x nprobe], entries
  * outside 0..nlist-1 skipped) to the k best (out_val float[nq x k] descending, out_idx int32[nq x k] ids; (-inf, -1) where the probed lists
  * hold fewer than k vectors): pairs grouped by list on the device, one tile GEMM launch on the matrix cores (bf16 rows with dp a multiple
- * of 128: 128 x 128 tiles, v_mfma_f32_32x32x16_bf16; fp32 rows or other bf16 row lengths: the 64 x 64 tiles of anncur_ivf_group_scores),
+ * of 128: 128 x 128 tiles, v_mfma_f32_32x32x16_bf16; fp32 rows or other bf16 row lengths: the 64 x 64 tiles of anncur_ivf_group_scores_dev),
  * scores written to PACKED rows -- S float[nq x pitch], 16-byte aligned, query q's probed lists back to back, nothing pre-filled -- and
- * scanned by anncur_rowwise_topk_ragged.  Xs / Q as for anncur_ivf_group_scores(_bf16) (dtype selects fp32 or bf16 rows for BOTH).
+ * scanned by anncur_rowwise_topk_ragged.  Xs / Q: the operand contracts of anncur_ivf_group_scores_dev (dtype selects fp32 or bf16 rows for BOTH).
  * pitch >= max(k, longest packed row) -- nprobe x longest list always suffices -- a multiple of 4, nq x pitch < 2^32 (split the queries); a
  * probed list that no longer fits a query's row is left out of that query's search (a pitch below the contract loses candidates, never memory).
  * max_tiles: any upper bound on sum_l ceil(pairs_l / T) ceil(size_l / T), T = anncur_ivf_search_tile(...) (the launch's grid: workgroups

@@ -267,7 +267,7 @@ def test_ivf_flat_index_branch(gpu):
 
 def test_ivf_bf16_lists_on_the_bf16_matrix_cores(gpu):
 	"""An index built with dtype = "bf16" keeps a bf16 copy of its list-ordered vectors; the batched search scores it against bf16-rounded
-	queries with one v_mfma_f32_32x32x16_bf16 GEMM per list (anncur_ivf_group_scores_bf16).  Same lists, same probes as the fp32 index;
+	queries with one v_mfma_f32_32x32x16_bf16 GEMM per list (anncur_ivf_group_scores_dev, ANNCUR_BF16).  Same lists, same probes as the fp32 index;
 	on inputs that ARE bf16 values the scores are the exact fp32-accumulated products: equal to the fp32 index's to round-off, same ids.
 	Ragged sizes: d not a multiple of 32 (a partial k-tile), partial 64-tiles of pairs and of vectors, an empty list."""
 	from anncur_amd.nearest_nbr import IVFFlatIPIndex
@@ -333,7 +333,7 @@ def test_ivf_spherical_kmeans_keeps_lists_balanced_on_varying_norms(gpu):
 
 def test_ivf_batched_search_equals_the_per_query_scan(gpu):
 	"""Many queries (the reference's hard-negative mining, utils/data_process.py:343-365): pairs (query, probed list) grouped by list,
-	each list one fp32-MFMA GEMM (anncur_ivf_group_scores), exact scan over the lists side by side, column -> id map.  Same probed
+	each list one fp32-MFMA GEMM (anncur_ivf_group_scores_dev, ANNCUR_F32), exact scan over the lists side by side, column -> id map.  Same probed
 	lists, same exact fp32 inner products as the per-query kernel: same ids (boundary near-ties aside), scores equal to round-off;
 	padding when k exceeds the probed lists; ragged lists incl. an empty one."""
 	from anncur_amd.nearest_nbr import IVFFlatIPIndex

@@ -494,3 +494,29 @@ def test_map_ids_unpacked(ops, gpu):
 	_lib.check(_lib.load().anncur_ivf_map_ids(ops._p(c_d), ops._p(v_d), col.shape[0], k, lmax, ops._p(p_d), nprobe, ops._p(o_d), ops._p(i_d), ops._p(out), ops._stream()), "ivf_map_ids")
 	torch.cuda.synchronize()
 	assert np.array_equal(out.cpu().numpy(), want)
+
+
+@pytest.mark.parametrize("nlist", [1, 255, 256, 257, 1000])
+def test_slotted_tile_start_prefix(ops, gpu, nlist):
+	"""The single-workgroup prefix sum of ivf.hip (ivf_prefix256: 256 lists per step, the total at index nlist) called directly:
+	anncur_ivf_group_scores_dev with max_tiles = 0 returns after its tile-start kernel, and tile_start[0 .. nlist] must equal numpy's exclusive
+	cumulative sum of ceil(pairs_l / 64) * ceil(size_l / 64).  List sizes and pair counts at the tile edges; one list, one step less one, one
+	step, one step plus one, four steps.  Integers only.
+	(The packed search's pair_off / tile_start lie inside its workspace at offsets that only a restatement of ivf.hip's ivf_search_ws would
+	give -- anncur_ivf_search_workspace_bytes returns the total alone -- so they are checked through the whole searches above, at 257 and
+	1000 lists.)"""
+	from anncur_amd import _lib
+	g = np.random.default_rng(nlist)
+	edge = np.array([0, 1, 63, 64, 65, 129], dtype=np.int64)
+	sizes, pairs = g.choice(edge, nlist), g.choice(edge, nlist)
+	sizes[-1], pairs[-1] = 129, 129                               # (the last list has tiles: the total differs from the last start)
+	want = np.concatenate([[0], np.cumsum(-(-pairs // 64) * -(-sizes // 64))]).astype(np.int32)
+	dev = lambda a: torch.from_numpy(np.concatenate([[0], np.cumsum(a)]).astype(np.int32)).to(gpu)
+	off_d, poff_d = dev(sizes), dev(pairs)
+	tile_start = torch.full((nlist + 1,), -7, dtype=torch.int32, device=gpu)
+	x = torch.zeros(16, dtype=torch.float32, device=gpu)          # operands, pair ids and scores: required, not touched without tiles
+	pid = torch.zeros(1, dtype=torch.int32, device=gpu)
+	_lib.check(_lib.load().anncur_ivf_group_scores_dev(ops._p(x), _lib.F32, 16, 16, ops._p(off_d), nlist, ops._p(x), 16, 1,
+													   ops._p(pid), ops._p(poff_d), ops._p(tile_start), 0, 8, ops._p(x), ops._stream()), "ivf_group_scores_dev")
+	torch.cuda.synchronize()
+	assert np.array_equal(tile_start.cpu().numpy(), want)
