@@ -63,7 +63,10 @@ int anncur_gather_rows(const void *A, int dtype, int64_t n_rows, int64_t n_cols,
  * C(m,n) = sum_k A(m,k) * B(k,n), element (i,j) of an operand at base + i*s0 + j*s1
  * (strides in elements), so NN / NT / TN / transposed-output products are one call.
  * Inputs F32 or BF16 (up-converted exactly), products and sums in fp32 on the matrix
- * cores (v_mfma_f32_32x32x2_f32: bit-for-bit a k-ordered fmaf chain).  Replaces
+ * cores (v_mfma_f32_32x32x2_f32: bit-for-bit a k-ordered fmaf chain).  Subnormal numbers are numbers here: subnormal fp32 and bf16
+ * operands are read as they are, every subnormal partial sum is kept and rounded to nearest even like any other, and a bf16 C is one
+ * more such rounding, into bf16's subnormals (measured on gfx950, tests/test_gpu_subnormal_exact.py; no kernel of this library is built
+ * with a flushing denormal mode, tests/test_cpu_denorm_mode.py).  Replaces
  *   latent_cols = U @ R                      eval/matrix_approx_zeshel.py:65
  *   latent_rows = C @ U                      eval/matrix_approx_zeshel.py:61
  *   get / get_rows / get_cols / get_complete_row / get_complete_col
@@ -76,7 +79,8 @@ int anncur_gemm(const void *A, int a_dtype, int64_t a_sm, int64_t a_sk,
                 int64_t M, int64_t N, int64_t K, void *stream);
 
 /* Same product with scaling and accumulation: C = alpha * A.B + beta * Cin (Cin fp32 with its own strides, may be NULL; it may
- * alias C element for element).  Building block of the on-device pseudo-inverse (Newton-Schulz X <- 2X - (X W) X), the
+ * alias C element for element); a subnormal accumulator, a subnormal Cin and a subnormal result are kept, none is flushed.
+ * Building block of the on-device pseudo-inverse (Newton-Schulz X <- 2X - (X W) X), the
  * alternative to the host numpy.linalg.pinv of eval/matrix_approx_zeshel.py:47,49 for large anchor counts. */
 int anncur_gemm_ex(const void *A, int a_dtype, int64_t a_sm, int64_t a_sk,
                    const void *B, int b_dtype, int64_t b_sk, int64_t b_sn,
@@ -88,7 +92,8 @@ int anncur_gemm_ex(const void *A, int a_dtype, int64_t a_sm, int64_t a_sk,
  * anncur_sumsq combines its waves' partial sums by atomic adds, in the order they finish: the last bits of out[0] differ from call to call.
  * anncur_sumsq_ordered adds in an order that depends on the shape alone (one partial per workgroup in `partials`, ANNCUR_SUMSQ_PARTIALS
  * floats of caller-owned workspace, nothing pre-filled, then one workgroup over them): equal inputs give equal bits.  pinv.py scales and
- * stops its fp32 iteration by this sum, so it takes the ordered one. */
+ * stops its fp32 iteration by this sum, so it takes the ordered one.  Subnormal squares and sums are kept by both; anncur_scale_copy's
+ * factor is the IEEE quotient alpha / divide_by[0], a subnormal one included, and a subnormal product is stored as it is. */
 #define ANNCUR_SUMSQ_PARTIALS 1024
 int anncur_sumsq(const float *A, int64_t n_rows, int64_t n_cols, int64_t lda, float *out, void *stream);
 int anncur_sumsq_ordered(const float *A, int64_t n_rows, int64_t n_cols, int64_t lda, float *partials, float *out, void *stream);
@@ -116,7 +121,8 @@ int anncur_diff_sumsq_f64(const double *X, const double *Y, int64_t n, double *o
  *   eval/run_retrieval_eval_wrt_exact_crossenc.py:146-147 (torch.norm over row subsets;
  *   the host sums the per-row terms over anchor / non-anchor / all rows in fp64).
  * X [Q x K] (x_dtype), Et [I x K] = E transposed (e_dtype), A [Q x I] (a_dtype).
- * err_sq / norm_sq: float[Q], overwritten. */
+ * err_sq / norm_sq: float[Q], overwritten.  A difference, a square or a sum inside the subnormal range is kept, here and in the two
+ * packed forms below: rows whose every (S_hat - A)^2 is a subnormal still add up to their exact sum. */
 int anncur_approx_error(const void *X, int x_dtype, int64_t ldx,
                         const void *Et, int e_dtype, int64_t lde,
                         const void *A, int a_dtype, int64_t lda,
@@ -203,6 +209,10 @@ int anncur_rowwise_topk_gather(const void *A, int dtype, int64_t Q, int64_t I, i
  * X makes that query's result k pads; a NaN row of Et is never returned and costs no other item or query its place (the prepass' group
  * maxima skip NaN; a query whose sample holds fewer than k non-NaN maxima, or whose k-th maximum is -inf, sweeps without a threshold and
  * its row is rescanned by the select).
+ * Subnormal values, on every body and under every flag: a subnormal bf16 operand is read as it is and a subnormal product, partial sum or
+ * score is kept (the bf16 MFMAs flush neither A/B nor C/D on gfx950), and the group maxima, tau, the ladder levels and every filter
+ * compare it as the number it is: n 2^-149 never ties with 0.  The coarse threshold (a 16-bit key prefix) of a row of such scores is
+ * +-0, about half of the row passes it and the select may repair: slower, and exact.  The same holds for anncur_eval_fused.
  * ldx: the pitch of X in elements, >= Kp and a multiple of 8.  On the wide route (Kp > 512) the kernel addresses the queries of a 256-row
  * block with 32-bit byte offsets: 255 x ldx x 2 + 64 < 2^32, i.e. ldx <= 8 421 504; a longer pitch is refused (ANNCUR_E_UNSUPPORTED, also by
  * anncur_score_topk_ex / _timed and anncur_eval_topk; anncur_score_topk_supported does not see the pitch): pass a compact copy of X.
@@ -256,7 +266,8 @@ int anncur_score_topk_ex(const void *X, int64_t ldx, const void *Et, int64_t lde
  * anncur_score_topk's) and writes S_hat [Q x ceil32(I)] fp32 plus one maximum per 64 consecutive items into the workspace;
  * few_select_kernel takes the k-th largest group maximum as threshold, reads only the groups that reach it, and selects.  A query with
  * more than cand_cap candidates at or above its threshold (heavy ties) is scanned in full by the same workgroup: always exact.
- * Et is in ITEM order (no leading-sample hint, no id map).  Rows >= Q of X are never read. */
+ * Et is in ITEM order (no leading-sample hint, no id map).  Rows >= Q of X are never read.  Subnormal operands, scores and group
+ * maxima are kept as in anncur_score_topk, so the two routes agree on them bit for bit as well. */
 #define ANNCUR_FEW_MAX_Q 64             /* queries per call */
 #define ANNCUR_FEW_STAGE_BYTES 65536    /* LDS stage of the queries: 16 ceil(Q / 16) x Kp x 2 bytes must fit (Q <= 16: Kp <= 2048; Q > 48: Kp <= 512) */
 #define ANNCUR_FEW_PLAN_WORDS 12
@@ -293,7 +304,8 @@ int anncur_score_topk_few_plan(int64_t Q, int64_t I, int32_t Kp, int32_t k, int3
  * matrix [I x V], term_ptr int64[V + 1], post_item int32[nnz] (ascending inside a term), post_val fp32[nnz].  All on the device.
  * Score: S[q, i] = the fp32 chain over the terms t that q and i share, in ascending t, from +0.0f, each step two separately rounded
  * operations acc = fadd_rn(acc, fmul_rn(w_qt, v_it)); an item that shares no term with q scores +0.0 (bit pattern 0).  No atomics and no
- * split sums: a score does not depend on the launch shape, on Q or on the position of q in the call, and equals a float32 loop on the host.
+ * split sums: a score does not depend on the launch shape, on Q or on the position of q in the call, and equals a float32 loop on the host
+ * -- on a host that does not flush: subnormal weights, products and sums are kept by both steps.
  * One launch: a four-wave workgroup per (query, run of item windows); a wave owns a span of consecutive windows of ANNCUR_SPARSE_WINDOW
  * items with private accumulators in LDS and one cursor per query term into that term's posting list (found once per span by a lower
  * bound, carried from window to window).  LDS per workgroup: 8 bytes per staged query term (8 KB) + 4 waves x (8 KB accumulators + 8 bytes
@@ -356,7 +368,7 @@ int anncur_pack_split_bf16(const void *src, int src_dtype, int64_t lds_, int64_t
                            void *dst, int64_t ldd, int64_t n_rows_pad, void *stream);
 /* anncur_rescore_topk: for query q and each of its n_cand candidate ids i = cand_idx[q*ld_idx + j] (distinct per row; an id < 0 or
  *   >= I is a hole and is skipped), s = fmaf(X[q,K-1], Et[i,K-1], ... fmaf(X[q,0], Et[i,0], 0)) in fp32, k ascending -- the k-ordered
- *   fmaf chain anncur_gemm is bit for bit -- and the k_out best: out_val float[Q x k_out], out_idx int32[Q x k_out] (item ids), score
+ *   fmaf chain anncur_gemm is bit for bit, subnormal operands and partial sums included -- and the k_out best: out_val float[Q x k_out], out_idx int32[Q x k_out] (item ids), score
  *   descending, ties by the smaller id, NaN never selected, (-inf, -1) where fewer than k_out valid candidates exist.
  *   X [Q x K] (x_dtype, pitch ldx), Et [I x K] (e_dtype, pitch lde; rows are read with 16-byte loads when Et and its pitch are 16-byte
  *   aligned).  k_out <= n_cand <= ANNCUR_MAX_TOPK.  An HBM gather of Q n_cand K elements; no matrix cores.
@@ -463,7 +475,8 @@ int anncur_overlap_counts(const int32_t *a, int32_t la, const int32_t *b, int32_
  *     rank = #{ i != id : s[i] > a  or  (s[i] == a and i < id) }
  *
  * i.e. the position of id in the row sorted by score descending, ties to the smaller id -- the order of anncur_rowwise_topk.  The compare
- * is the float compare: -0.0 and +0.0 tie; a NaN score is never ahead of anything; a target whose own score is NaN gets rank -1, and so
+ * is the float compare: -0.0 and +0.0 tie, and only they: a subnormal of either sign, fp32 or bf16, is ahead of or behind the zeros
+ * (anncur_score_rank keeps subnormal operands and scores as anncur_score_topk does); a NaN score is never ahead of anything; a target whose own score is NaN gets rank -1, and so
  * does a hole (id == -1).  Any other id outside [0, I) is the caller's error (the Python binding raises ValueError); the kernels treat it
  * as a hole and never read through it.  Duplicate ids in a row are allowed, each reports that item's rank.
  *   ids int32[Q x t], rank int32[Q x t], score float[Q x t] or NULL, all contiguous; 1 <= t <= ANNCUR_RANK_MAX_T.
@@ -517,7 +530,7 @@ int anncur_gather_pairs(const void *A, int dtype, int64_t Q, int64_t I, int64_t 
  *   w_q = c_q . pinv(R[:, S_q])        replaces numpy.linalg.pinv of eval/matrix_approx_zeshel.py:47,49 called once PER QUERY AND ROUND
  *                                      (the index' own pseudo-inverse, anncur_amd/pinv.py, is one matrix: ~28 dependent products)
  * Rt float[m x kq], pitch ldr >= kq, item-major: row i = item i's scores under the kq anchor queries (the pitch pad is never read into a
- * sum).  ids int32[Q x n] (pitch ld_ids), an id < 0 (or >= m) marks a hole; the ids of a row are distinct (a contract, as for
+ * sum; a subnormal fp32 entry is gathered as it is and widens to a normal fp64).  ids int32[Q x n] (pitch ld_ids), an id < 0 (or >= m) marks a hole; the ids of a row are distinct (a contract, as for
  * anncur_rerank).  C float[Q x n] (pitch ldc): C[q, j] = the exact score of query q on item ids[q, j], ignored at holes.  ridge = lambda >= 0.
  * Row q of W float[Q x kq] (pitch ldw) becomes
  *     w_q = argmin_w || w R_S - c ||^2 + lambda ||w||^2,      R_S = the columns Rt[ids[q, j], :]^T of the non-hole entries, kq x n_q,
@@ -727,7 +740,8 @@ int anncur_svd_scale_cols(const double *V, int64_t ldv, int64_t n, int32_t g, co
  *    every k-means update (faiss/IndexIVF.cpp Level1Quantizer::train_q1; the reference reaches it through models/nearest_nbr.py:46-49);
  *  anncur_ivf_scan: per query, exact inner products with every vector of its nprobe lists (probe int32[nq x nprobe], -1 = skip)
  *    and the k best: out_val float[nq x k] descending, out_idx int32[nq x k] (ids of the points; (-inf, -1) where the probed lists
- *    hold fewer than k vectors).  Xs / Q rows zero-padded to dp floats, dp a multiple of 16, 16-byte aligned. */
+ *    hold fewer than k vectors).  Xs / Q rows zero-padded to dp floats, dp a multiple of 16, 16-byte aligned.  Subnormal vector or
+ *    query entries and subnormal inner products are kept, here and in the batched searches below. */
 int anncur_ivf_build_lists(const int32_t *assign, int64_t n, int32_t nlist, int32_t *counts, int32_t *offsets, int32_t *ids, void *stream);
 int anncur_ivf_list_means(const float *Xs, int64_t ldx, int32_t d, const int32_t *offsets, int32_t nlist, float *centroids, int64_t ldc, void *stream);
 int anncur_renorm_rows(float *M, int64_t n_rows, int64_t n_cols, int64_t ld, void *stream);
@@ -766,7 +780,8 @@ int anncur_ivf_map_ids(const int32_t *col, const float *val, int64_t nq, int32_t
  * probed list that no longer fits a query's row is left out of that query's search (a pitch below the contract loses candidates, never memory).
  * max_tiles: any upper bound on sum_l ceil(pairs_l / T) ceil(size_l / T), T = anncur_ivf_search_tile(...) (the launch's grid: workgroups
  * past the last tile exit), e.g. (nq nprobe / T) max_l ceil(size_l / T) + sum_l ceil(size_l / T).  k <= 128 and nlist <= 8192
- * (ANNCUR_E_UNSUPPORTED otherwise: the calls above).  Workspace: anncur_ivf_search_workspace_bytes, 256-byte aligned. */
+ * (ANNCUR_E_UNSUPPORTED otherwise: the calls above).  Workspace: anncur_ivf_search_workspace_bytes, 256-byte aligned.
+ * All three tile bodies (fp32 and bf16 64 x 64, bf16 128 x 128) read subnormal operands as they are and keep subnormal scores. */
 int32_t anncur_ivf_search_tile(int dtype, int32_t dp, int64_t ldx, int64_t ldq, int64_t nq);
 size_t anncur_ivf_search_workspace_bytes(int64_t nq, int32_t nprobe, int32_t nlist, int32_t k, int64_t max_tiles);
 int anncur_ivf_search_grouped(const void *Xs, int dtype, int64_t ldx, int32_t dp, const int32_t *offsets, const int32_t *ids, int32_t nlist,

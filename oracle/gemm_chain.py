@@ -21,11 +21,22 @@ MAX_E = 4        # value = m * 2^-e, e in 0 .. MAX_E
 SCALE = float(1 << (2 * MAX_E))   # every product and every sum is an integer multiple of 1 / SCALE
 
 
-def grid(rng, shape, mant_bits=MANT_F32):
-	"""float32 array of fixed-point grid values m * 2^-e, |m| < 2^mant_bits, e in 0 .. MAX_E."""
+def _pow2(s):
+	"""A scale must be a power of two (scaling by it is exact in fp64 wherever the result is representable)."""
+	s = float(s)
+	assert s > 0 and np.frexp(s)[0] == 0.5, s
+	return s
+
+
+def grid(rng, shape, mant_bits=MANT_F32, scale=1.0):
+	"""float32 array of fixed-point grid values m * 2^-e, |m| < 2^mant_bits, e in 0 .. MAX_E, times the power of two `scale`.  The scaled
+	values must be float32 numbers (normal or subnormal): scale >= 2^(MAX_E - 149)."""
 	m = rng.integers(-(1 << mant_bits) + 1, 1 << mant_bits, size=shape)
 	e = rng.integers(0, MAX_E + 1, size=shape)
-	return (m * np.exp2(-e.astype(np.float64))).astype(np.float32)
+	wide = m * np.exp2(-e.astype(np.float64)) * _pow2(scale)
+	out = wide.astype(np.float32)
+	assert (out.astype(np.float64) == wide).all()   # nothing rounded: the grid fits under the scale
+	return out
 
 
 def small_ints(rng, shape, bound=8):
@@ -33,11 +44,18 @@ def small_ints(rng, shape, bound=8):
 	return rng.integers(-bound, bound + 1, size=shape).astype(np.float32)
 
 
-def assert_exact_in_fp64(A, B, cin=None):
+def assert_exact_in_fp64(A, B, cin=None, sa=1.0, sb=1.0):
 	"""The precondition of chain(): the operands are finite multiples of 2^-MAX_E, and no sum of |a||b| terms (so no partial sum in any
 	order, rounded to fp32 or not) reaches 2^52 / SCALE.  With cin: it lies on the grid as well, and the epilogue's fp64 sum stays exact
-	for |alpha|, |beta| <= 8."""
-	ops = [np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)] + ([np.asarray(cin, dtype=np.float64)] if cin is not None else [])
+	for |alpha|, |beta| <= 8.
+	sa, sb: A and B are grid values times these powers of two (cin: times sa * sb).  The scales are taken off first (exact in fp64), so
+	the same bounds hold in units of u = sa * sb / SCALE.  A partial sum rounded to fp32 is a multiple of its own ulp, a power of two that
+	is either >= u or so small that the sum was representable and did not move: every accumulator stays a multiple of u, inside the
+	subnormal range too (ulp 2^-149), and every fp64 step spans fewer than 53 bits.  u itself must be a normal fp64 and the largest sum a
+	finite fp32 (asserted)."""
+	sa, sb = _pow2(sa), _pow2(sb)
+	assert sa * sb / SCALE >= 2.0 ** -960 and sa * sb / SCALE * 2.0 ** 52 < 2.0 ** 127
+	ops =[np.asarray(A, dtype=np.float64) / sa, np.asarray(B, dtype=np.float64) / sb] + ([np.asarray(cin, dtype=np.float64) / (sa * sb)] if cin is not None else [])
 	for x in ops:
 		assert np.isfinite(x).all()
 		s = x * (1 << MAX_E)
@@ -50,14 +68,38 @@ def assert_exact_in_fp64(A, B, cin=None):
 	return True
 
 
-def chain(A, B, ks=None, dtype=np.float64):
+def is_subnormal(x):
+	"""Elementwise: a non-zero float32 / float64 below the smallest normal number of its own type (exponent field 0)."""
+	x = np.asarray(x)
+	return (x != 0) & (np.abs(x) < np.finfo(x.dtype).tiny)
+
+
+def flush(x):
+	"""Every subnormal replaced by a zero of its sign (what a flush-to-zero mode does to a result, a denormals-are-zero mode to an operand)."""
+	x = np.asarray(x)
+	return np.where(is_subnormal(x), np.copysign(x.dtype.type(0), x), x)
+
+
+def chain(A, B, ks=None, dtype=np.float64, sa=1.0, sb=1.0, daz=False, ftz=False):
 	"""The fp32 fmaf chain over k in `ks` (default 0 .. K-1 ascending) for the whole M x N block, one numpy expression per k.
-	dtype: the wide type the unrounded step is computed in (np.float64; np.longdouble for the self-test)."""
-	Aw, Bw = np.asarray(A).astype(dtype), np.asarray(B).astype(dtype)
+	dtype: the wide type the unrounded step is computed in (np.float64; np.longdouble for the self-test).
+	sa, sb: A and B are grid values times these powers of two, as grid(scale=) makes them and as the device receives them (float32
+	numbers, subnormals included).  Given, the chain checks its own precondition with them.  The step is as exact as on the unscaled
+	grid, and its one rounding to fp32 is round-to-nearest-even inside the subnormal range as well.
+	daz / ftz: the two ways a flushing device would differ -- every subnormal operand read as a zero of its sign; every subnormal
+	partial sum replaced by a zero of its sign."""
+	A32, B32 = np.asarray(A, dtype=np.float32), np.asarray(B, dtype=np.float32)
+	if sa != 1.0 or sb != 1.0:
+		assert_exact_in_fp64(A32, B32, sa=sa, sb=sb)
+	if daz:
+		A32, B32 = flush(A32), flush(B32)
+	Aw, Bw = A32.astype(dtype), B32.astype(dtype)
 	M, K = Aw.shape
 	acc = np.zeros((M, Bw.shape[1]), dtype=np.float32)
 	for k in (range(K) if ks is None else ks):
 		acc = (Aw[:, k:k + 1] * Bw[k:k + 1, :] + acc.astype(dtype)).astype(np.float32)
+		if ftz:
+			acc = flush(acc)
 	return acc
 
 

@@ -32,6 +32,32 @@ def kernel_notes(lib: str):
 		shutil.rmtree(tmp, ignore_errors=True)
 
 
+def kernel_descriptors(lib: str):
+	"""The kernel descriptors of every code object of the library as llvm-objdump prints them (.amdhsa_kernel NAME ... .end_amdhsa_kernel,
+	one .amdhsa_* directive per field of compute_pgm_rsrc1..3)."""
+	tmp = tempfile.mkdtemp(prefix="anncur_co_")
+	try:
+		return [subprocess.run([f"{LLVM}/llvm-objdump", "-d", "-j", ".rodata", f], cwd=tmp, check=True, capture_output=True, text=True).stdout for f in _code_objects(lib, tmp)]
+	finally:
+		shutil.rmtree(tmp, ignore_errors=True)
+
+
+def denorm_modes(text: str):
+	"""{kernel name: (float_denorm_mode_32, float_denorm_mode_16_64)} of one descriptor listing; None for a field the listing lacks.
+	Mode 3 keeps subnormal sources and results, 0 flushes both (compute_pgm_rsrc1 bits 16..19)."""
+	out, name = {}, None
+	for line in text.splitlines():
+		w = line.split()
+		if len(w) == 2 and w[0] == ".amdhsa_kernel":
+			name = w[1]
+			out[name] = [None, None]
+		elif w and w[0] == ".end_amdhsa_kernel":
+			name = None
+		elif name and len(w) == 2 and w[0] in (".amdhsa_float_denorm_mode_32", ".amdhsa_float_denorm_mode_16_64"):
+			out[name][w[0].endswith("16_64")] = int(w[1], 0)
+	return {k: tuple(v) for k, v in out.items()}
+
+
 def functions(dis: str):
 	name, body = None, []
 	for line in dis.splitlines():

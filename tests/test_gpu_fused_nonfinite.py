@@ -55,19 +55,7 @@ BF16, F32 = torch.bfloat16, torch.float32
 NAN, INF = nf.NAN, nf.INF
 SENTINEL_V, SENTINEL_I = 12345.0, -7
 
-# body -> (Kp, logical K, flags, {k: (I, lg, QT, ladder, stage_pred)}); I = the smallest the plan takes for the body at that k, + 17.
-# Kp <= 256: 32 max(Kp, 256) + 17 = 8209 at k = 100; k = 700 needs 1400 full tiles (found with ops.fused_supported): 44817.
-# qt1 is honoured from Kp = 128 on (at Kp = 64 the plan keeps QT = 2), and moves the shape to the 32x32x16 body; staged keeps the 16x16x32
-# body up to k = 384 and takes 32x32x16 above.  Kp = 512: 8209; wide: 16 block tiles of 256 + 17 = 4113.
-_BODY = {
-	"ladder": (256, 250, {}, {100: (8209, 1, 2, True, 2), 700: (44817, 1, 2, True, 2)}),
-	"staged": (64, 56, {"staged": True}, {100: (8209, 1, 2, False, 2), 700: (44817, 2, 2, False, 1)}),
-	"mfma32": (128, 120, {"mfma32": True}, {100: (8209, 2, 2, False, 1), 700: (44817, 2, 2, False, 1)}),
-	"qt1": (256, 200, {"qt1": True}, {100: (8209, 2, 1, False, 1), 700: (44817, 2, 1, False, 1)}),
-	"q16": (512, 400, {}, {100: (8209, 1, 1, False, 4)}),
-	"ring": (512, 257, {"mfma32": True}, {100: (8209, 2, 1, False, 1)}),
-	"wide": (640, 513, {}, {100: (4113, 4, 2, False, 1)}),
-}
+_BODY = fx.BODIES   # body -> (Kp, logical K, flags, {k: (I, lg, QT, ladder, stage_pred)}): shared with tests/test_gpu_subnormal_exact.py
 _RUNS = [(b, k) for b in _BODY for k in _BODY[b][3]]
 
 

@@ -9,8 +9,9 @@ No comparison here has a tolerance.  Operands are views into larger buffers fill
 into NaN, and stays inside the test's own allocation); outputs are views into buffers filled with one fixed NaN bit pattern, and
 every word outside the M x N view must still hold it after the call.
 
-Left out on purpose: denormal inputs and intermediates.  The grid never produces them (the smallest non-zero operand is 2^-4, the
-smallest non-zero product 2^-8), and how the fp32 MFMA treats denormals is not something this project has measured.
+Subnormal inputs and intermediates: the grid here never produces them (the smallest non-zero operand is 2^-4, the smallest non-zero
+product 2^-8).  tests/test_gpu_subnormal_exact.py runs the same chain on the same grid scaled by powers of two, with subnormal
+partial sums and with subnormal operands, in these buffers.
 
 anncur_gemm_f64 (csrc/gemm64.hip) is held to integer data, where fp64 is exact in any order, at its own tile edges (64 x 64 x 32, MFMA
 16 x 16 x 4), in the same poisoned buffers.
