@@ -20,6 +20,10 @@ int anncur_internal_approx_error_acc(const void *X, int x_dtype, int64_t ldx, co
 int anncur_ensure_dyn_lds(const void *fn, int bytes);  // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (function, device)
 int anncur_num_cu();                                   // CU count of the current device
 int anncur_event_pool(hipEvent_t **out, int n);        // n (<= 16) cached timing-less events of the current device
+// dst[0 .. n_words) = word, by a kernel on `st`: what a call uses to clear its counters and sums.  Not hipMemsetAsync: calls that cleared with it
+// were right eagerly and wrong when replayed from a captured graph (sums that start from 1.0 or 1024.0 instead of 0: DESIGN 3b has the cases,
+// the values, and what is not known about the cause).  dst 4-byte aligned.
+int anncur_fill_words_async(void *dst, uint32_t word, size_t n_words, hipStream_t st);
 // topk.hip: rows the one-wave-per-row exact scan keeps in flight on the whole chip (occupancy x CUs x 4 rows per workgroup)
 int anncur_internal_scan_rows_in_flight(int dtype);
 
@@ -38,6 +42,13 @@ int anncur_internal_scan_rows_in_flight(int dtype);
 			anncur_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
 			return ANNCUR_E_HIP;                                                         \
 		}                                                                                \
+	} while (0)
+
+// a call of the library's own that returns ANNCUR_OK or an error code
+#define ANNCUR_TRY(expr)                                \
+	do {                                                \
+		const int rc__ = (expr);                        \
+		if (rc__ != ANNCUR_OK) return rc__;             \
 	} while (0)
 
 #define ANNCUR_LAUNCH_OK()                                                               \

@@ -226,8 +226,8 @@ extern "C" int anncur_approx_error(const void *X, int x_dtype, int64_t ldx, cons
 								   float *norm_sq, void *stream) {
 	ANNCUR_REQUIRE(err_sq && norm_sq && Q >= 0, ANNCUR_E_INVALID, "approx_error: null pointer");
 	if (Q == 0) return ANNCUR_OK;
-	ANNCUR_HIP_OK(hipMemsetAsync(err_sq, 0, (size_t)Q * 4, (hipStream_t)stream));
-	ANNCUR_HIP_OK(hipMemsetAsync(norm_sq, 0, (size_t)Q * 4, (hipStream_t)stream));
+	ANNCUR_TRY(anncur_fill_words_async(err_sq, 0u, (size_t)Q, (hipStream_t)stream));
+	ANNCUR_TRY(anncur_fill_words_async(norm_sq, 0u, (size_t)Q, (hipStream_t)stream));
 	return anncur_internal_approx_error_acc(X, x_dtype, ldx, Et, e_dtype, lde, Aex, a_dtype, lda, Q, I, K, err_sq, norm_sq, stream);
 }
 
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(256) void scale_copy_kernel(const float *__restrict
 extern "C" int anncur_sumsq(const float *A, int64_t n_rows, int64_t n_cols, int64_t lda, float *out, void *stream) {
 	ANNCUR_REQUIRE(out && n_rows >= 0 && n_cols >= 0 && lda >= n_cols, ANNCUR_E_INVALID, "sumsq: bad arguments");
 	hipStream_t st = (hipStream_t)stream;
-	ANNCUR_HIP_OK(hipMemsetAsync(out, 0, 4, st));
+	ANNCUR_TRY(anncur_fill_words_async(out, 0u, 1, st));
 	if (n_rows * n_cols == 0) return ANNCUR_OK;   // (empty tensors have null data pointers: nothing to do comes first)
 	ANNCUR_REQUIRE(A, ANNCUR_E_INVALID, "sumsq: null pointer");
 	const int64_t blocks = ceil_div64(n_rows * n_cols, 256 * 8);
@@ -295,7 +295,7 @@ extern "C" int anncur_sumsq_ordered(const float *A, int64_t n_rows, int64_t n_co
 	ANNCUR_REQUIRE(out && n_rows >= 0 && n_cols >= 0 && lda >= n_cols, ANNCUR_E_INVALID, "sumsq_ordered: bad arguments");
 	hipStream_t st = (hipStream_t)stream;
 	if (n_rows * n_cols == 0) {
-		ANNCUR_HIP_OK(hipMemsetAsync(out, 0, 4, st));
+		ANNCUR_TRY(anncur_fill_words_async(out, 0u, 1, st));
 		return ANNCUR_OK;
 	}
 	ANNCUR_REQUIRE(A && partials, ANNCUR_E_INVALID, "sumsq_ordered: null pointer");

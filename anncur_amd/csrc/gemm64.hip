@@ -152,7 +152,7 @@ extern "C" int anncur_convert_f64(const void *src, int src_dtype, int64_t s0, in
 extern "C" int anncur_diff_sumsq_f64(const double *X, const double *Y, int64_t n, double *out2, void *stream) {
 	ANNCUR_REQUIRE(out2 && n >= 0 && (n == 0 || X), ANNCUR_E_INVALID, "diff_sumsq_f64: bad arguments");
 	hipStream_t st = (hipStream_t)stream;
-	ANNCUR_HIP_OK(hipMemsetAsync(out2, 0, 16, st));
+	ANNCUR_TRY(anncur_fill_words_async(out2, 0u, 4, st));
 	if (n == 0) return ANNCUR_OK;
 	const int64_t blocks = ceil_div64(n, 256 * 8);
 	hipLaunchKernelGGL(diff_sumsq_f64_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, st, X, Y, n, out2);

@@ -807,7 +807,7 @@ extern "C" int anncur_ivf_search_grouped(const void *Xs, int dtype, int64_t ldx,
 	hipStream_t st = (hipStream_t)stream;
 	const bool t128 = ivf_use_tile128(dtype, dp, ldx, ldq, nq);
 	const unsigned qgrid = (unsigned)ceil_div64(nq, 256);
-	ANNCUR_HIP_OK(hipMemsetAsync(counts, 0, (size_t)nlist * 4, st));
+	ANNCUR_TRY(anncur_fill_words_async(counts, 0u, (size_t)nlist, st));
 	hipLaunchKernelGGL(ivf_layout_kernel, dim3(qgrid), dim3(256), (size_t)nlist * 4, st, probe, nq, nprobe, offsets, nlist, k, pitch, coff, row_len, counts, S);
 	hipLaunchKernelGGL(ivf_pair_offsets_kernel, dim3(1), dim3(256), 0, st, counts, offsets, nlist, t128 ? T128 : GT, pair_off, cursor, tile_start);
 	hipLaunchKernelGGL(ivf_scatter_kernel, dim3(qgrid), dim3(256), (size_t)nlist * 8, st, probe, nq, nprobe, nlist, pitch, coff, cursor, pair_q, pair_out);
@@ -908,7 +908,10 @@ extern "C" int anncur_ivf_scan(const float *Xs, int64_t ldx, int32_t dp, const i
 // of the matrix.  Followed by anncur_ivf_build_lists (a stable counting sort) this yields the coarse descending-norm row order the
 // index builder passes to anncur_score_topk_ex -- an ordering that only moves speed, so a coarse one does.
 namespace {
-__global__ __launch_bounds__(256) void row_sumsq_kernel(const float *__restrict__ A, int64_t n_rows, int64_t n_cols, int64_t lda, float *__restrict__ out) {
+// (minmax: the running minimum / maximum of norm_minmax_kernel, the next launch on the stream, start here -- no launch of their own)
+__global__ __launch_bounds__(256) void row_sumsq_kernel(const float *__restrict__ A, int64_t n_rows, int64_t n_cols, int64_t lda, float *__restrict__ out,
+														 uint32_t *__restrict__ minmax) {
+	if (blockIdx.x == 0 && threadIdx.x == 0) { minmax[0] = 0xffffffffu; minmax[1] = 0u; }
 	const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
 	if (r >= n_rows) return;
 	const float *row = A + r * lda;
@@ -960,9 +963,7 @@ extern "C" int anncur_norm_buckets(const float *A, int64_t n_rows, int64_t n_col
 	if (n_rows == 0) return ANNCUR_OK;
 	ANNCUR_REQUIRE(A && norms && minmax2 && bucket, ANNCUR_E_INVALID, "norm_buckets: null pointer");
 	hipStream_t st = (hipStream_t)stream;
-	ANNCUR_HIP_OK(hipMemsetAsync(minmax2, 0xff, 4, st));      // running minimum of the sortable keys
-	ANNCUR_HIP_OK(hipMemsetAsync(minmax2 + 1, 0, 4, st));     // running maximum
-	hipLaunchKernelGGL(row_sumsq_kernel, dim3((unsigned)ceil_div64(n_rows, 4)), dim3(256), 0, st, A, n_rows, n_cols, lda, norms);
+	hipLaunchKernelGGL(row_sumsq_kernel, dim3((unsigned)ceil_div64(n_rows, 4)), dim3(256), 0, st, A, n_rows, n_cols, lda, norms, minmax2);
 	const int64_t mm_blocks = ceil_div64(n_rows, 256 * 16);
 	hipLaunchKernelGGL(norm_minmax_kernel, dim3((unsigned)(mm_blocks > 256 ? 256 : mm_blocks)), dim3(256), 0, st, norms, n_rows, minmax2);
 	hipLaunchKernelGGL(norm_bucket_kernel, dim3((unsigned)ceil_div64(n_rows, 256)), dim3(256), 0, st, norms, n_rows, minmax2, n_buckets, bucket);

@@ -70,6 +70,20 @@ int anncur_event_pool(hipEvent_t **out, int n) {
 	return ANNCUR_OK;
 }
 
+// The library's memset (common.hpp says why it is a kernel): grid-strided, one word per lane and step.
+namespace {
+__global__ __launch_bounds__(256) void fill_words_kernel(uint32_t *__restrict__ dst, uint32_t word, size_t n_words) {
+	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (size_t)gridDim.x * 256) dst[i] = word;
+}
+}
+int anncur_fill_words_async(void *dst, uint32_t word, size_t n_words, hipStream_t st) {
+	if (n_words == 0) return ANNCUR_OK;
+	ANNCUR_REQUIRE(dst && ((uintptr_t)dst % 4) == 0, ANNCUR_E_INVALID, "fill_words: null or misaligned pointer");
+	const size_t blocks = (n_words + 255) / 256;
+	hipLaunchKernelGGL(fill_words_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, st, (uint32_t *)dst, word, n_words);
+	ANNCUR_LAUNCH_OK();
+	return ANNCUR_OK;
+}
 
 extern "C" int anncur_version(void) { return 1000 * 0 + 4; }
 

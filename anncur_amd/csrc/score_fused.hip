@@ -845,8 +845,8 @@ extern "C" int anncur_eval_fused_ex(const void *X, int64_t ldx, const void *Et, 
 				   (long long)Q, (long long)I, Kp, k);
 	if (Q == 0) return ANNCUR_OK;
 	hipStream_t st = (hipStream_t)stream;
-	ANNCUR_HIP_OK(hipMemsetAsync(err_sq, 0, (size_t)Q * 4, st));
-	ANNCUR_HIP_OK(hipMemsetAsync(norm_sq, 0, (size_t)Q * 4, st));
+	ANNCUR_TRY(anncur_fill_words_async(err_sq, 0u, (size_t)Q, st));
+	ANNCUR_TRY(anncur_fill_words_async(norm_sq, 0u, (size_t)Q, st));
 	const int64_t I_full = I / TILE_I * TILE_I;
 	if (I_full < I) {  // the last I % 32 columns' error terms: strided kernel of gemm.hip, accumulating into the same sums
 		const int rc = anncur_internal_approx_error_acc((const uint16_t *)X, ANNCUR_BF16, ldx, (const uint16_t *)Et + I_full * lde, ANNCUR_BF16, lde,
@@ -1003,8 +1003,8 @@ extern "C" int anncur_approx_error_packed(const void *X, int64_t ldx, const void
 				   "approx_error_packed: the exact matrix must be 16-byte aligned with lda a multiple of 4 (use anncur_approx_error otherwise)");
 	if (Q == 0) return ANNCUR_OK;
 	hipStream_t st = (hipStream_t)stream;
-	ANNCUR_HIP_OK(hipMemsetAsync(err_sq, 0, (size_t)Q * 4, st));
-	ANNCUR_HIP_OK(hipMemsetAsync(norm_sq, 0, (size_t)Q * 4, st));
+	ANNCUR_TRY(anncur_fill_words_async(err_sq, 0u, (size_t)Q, st));
+	ANNCUR_TRY(anncur_fill_words_async(norm_sq, 0u, (size_t)Q, st));
 	const int64_t I_full = I / TILE_I * TILE_I;
 	if (I_full < I) {  // the last I % 32 columns: strided kernel of gemm.hip, accumulating into the same sums
 		const int rc = anncur_internal_approx_error_acc((const uint16_t *)X, ANNCUR_BF16, ldx, (const uint16_t *)Et + I_full * lde, ANNCUR_BF16, lde,

@@ -282,7 +282,7 @@ extern "C" int anncur_svd_sweep(int64_t rows, int64_t cols, void *workspace, siz
 	hipStream_t st = (hipStream_t)stream;
 	double *H = (double *)workspace, *Vt = (double *)((unsigned char *)workspace + q.vt_off);
 	const double tol = sqrt((double)q.L) * 0x1p-53;
-	ANNCUR_HIP_OK(hipMemsetAsync(rotations, 0, sizeof(int32_t), st));
+	ANNCUR_TRY(anncur_fill_words_async(rotations, 0u, 1, st));
 	for (int step = 0; step < q.gE - 1; ++step) {
 		if (q.L <= SV_REG_L) hipLaunchKernelGGL((svd_pair_kernel<true>), dim3((unsigned)(q.gE / 2)), dim3(SV_THREADS), 0, st, H, q.Lp, q.L, Vt, q.gp, q.g, q.gE, step, tol, rotations);
 		else hipLaunchKernelGGL((svd_pair_kernel<false>), dim3((unsigned)(q.gE / 2)), dim3(SV_THREADS), 0, st, H, q.Lp, q.L, Vt, q.gp, q.g, q.gE, step, tol, rotations);
@@ -300,7 +300,7 @@ extern "C" int anncur_svd_finish(int64_t rows, int64_t cols, const void *workspa
 	ANNCUR_REQUIRE(ldu >= q.g && ldv >= q.g, ANNCUR_E_INVALID, "svd_finish: ldu = %lld or ldv = %lld is shorter than a row of g = %d", (long long)ldu, (long long)ldv, q.g);
 	hipStream_t st = (hipStream_t)stream;
 	const double *H = (const double *)workspace, *Vt = (const double *)((const unsigned char *)workspace + q.vt_off);
-	ANNCUR_HIP_OK(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
+	ANNCUR_TRY(anncur_fill_words_async(flag, 0u, 1, st));
 	// rows >= cols: U [rows x g] = the normalised vectors, V [cols x g] = Vt^T; otherwise the roles swap
 	double *long_out = q.tall ? U : V, *short_out = q.tall ? V : U;
 	const int64_t ld_long = q.tall ? ldu : ldv, ld_short = q.tall ? ldv : ldu;

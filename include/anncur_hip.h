@@ -11,7 +11,11 @@
  *  - the caller owns every buffer; pointers are DEVICE pointers unless stated;
  *  - `stream` is a hipStream_t passed as void* (NULL = default stream); all work is
  *    asynchronous on that stream; no hidden allocation, no host synchronisation:
- *    scratch comes from an explicit workspace sized by the *_workspace_bytes() query;
+ *    scratch comes from an explicit workspace sized by the *_workspace_bytes() query; every call can be captured into a HIP graph
+ *    and replayed on other data in the same buffers (tests/test_gpu_graph_replay.py) -- with ONE EXCEPTION: the fused top-k at Kp > 512
+ *    (the wide route of anncur_score_topk / _ex and anncur_eval_topk), whose replay on a workspace overwritten since the capture ended in
+ *    a GPU memory fault; its cause is supposed, not established, so capture it only if nothing else writes the workspace;
+ *    the calls documented to synchronise (_timed, _survivors, _ladder_state) cannot be captured at all;
  *  - matrices are row-major; `ld*` are leading dimensions in ELEMENTS;
  *  - dtype codes: ANNCUR_F32 (float) / ANNCUR_BF16 (bfloat16, 2 bytes);
  *  - top-k results are sorted by score descending, ties broken by the smaller index
