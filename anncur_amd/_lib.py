@@ -137,6 +137,12 @@ SIGNATURES = {
 	"anncur_convert": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p]),
 }
 
+# exported with C linkage for tests and measurements, not declared in the public header (csrc/common.hpp)
+INTERNAL_SIGNATURES = {
+	"anncur_rowwise_topk_ex": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+	"anncur_internal_scan_spec_rank": (c_int, [c_int64, c_int32, c_int]),
+}
+
 _lib = None
 
 
@@ -158,7 +164,7 @@ def load():
 	# the kernels here would launch on one that never saw torch's device context ("no ROCm-capable device is detected").
 	import torch  # noqa: F401
 	lib = ctypes.CDLL(LIB_PATH)
-	for name, (res, args) in SIGNATURES.items():
+	for name, (res, args) in list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()):
 		fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
 		fn.restype = res
 		fn.argtypes = args

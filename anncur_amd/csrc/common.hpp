@@ -26,6 +26,20 @@ int anncur_event_pool(hipEvent_t **out, int n);        // n (<= 16) cached timin
 int anncur_fill_words_async(void *dst, uint32_t word, size_t n_words, hipStream_t st);
 // topk.hip: rows the one-wave-per-row exact scan keeps in flight on the whole chip (occupancy x CUs x 4 rows per workgroup)
 int anncur_internal_scan_rows_in_flight(int dtype);
+// topk.hip: rank of the seed maximum the wave-per-row scan starts from speculatively, 0 = off (C linkage for the host tests only)
+extern "C" int anncur_internal_scan_spec_rank(int64_t I, int32_t k, int dtype);
+/* topk.hip: anncur_rowwise_topk with the wave-per-row scan's speculative start (k <= 128, I > 1024) in the caller's hands and on show.  The
+ * scan may start a row from a threshold that is a guess -- the spec_rank-th largest of the maxima of the row's first 512 16-byte vectors --
+ * instead of a bound, checks the guess at a quarter of the row and at its end, and scans the row again from the valid bound where it was
+ * too high: the result is the same, bit for bit, whatever the rank.
+ *   spec_rank: -1 = as anncur_rowwise_topk chooses (a Poisson tail of 1e-5 on iid rows; off for short rows, small k, or with
+ *              ANNCUR_SCAN_SPEC=0 in the environment), 0 = off, 1..k = that rank (k itself is the valid bound).
+ *   stats:     NULL, or uint32[2] on the device that the launch ADDS to (the caller zeroes it): [0] rows scanned twice, [1] rows started
+ *              from a guess.  Left untouched by the other kernels (short rows, k > 128).
+ * Same stream contract as every entry: no host synchronisation, capturable into a graph (anncur_rowwise_topk is this call with -1 and NULL).
+ * A test and measurement entry with C linkage (ops.rowwise_topk(_spec=, _stats=)), kept out of include/anncur_hip.h. */
+extern "C" int anncur_rowwise_topk_ex(const void *A, int dtype, int64_t Q, int64_t I, int64_t lda, int32_t k,
+                           float *out_val, int32_t *out_idx, void *stream, int spec_rank, uint32_t *stats);
 
 #define ANNCUR_REQUIRE(cond, code, ...)                 \
 	do {                                                \

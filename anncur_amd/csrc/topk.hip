@@ -299,14 +299,30 @@ struct ScanGather {
 	int64_t ldo;
 };
 // RAGGED (round 5, the IVF search's packed score rows): row q holds row_len[q] elements (k <= row_len[q] <= I_all, the caller's contract).
-template <typename T, bool GATHER = false, bool BUF = true, bool RAGGED = false, int E = 2>   // E: keys per lane of the final sort (k <= 64 E; E = 1 from the ragged entry only)
+// SPECULATIVE START (plain instantiations only: neither GATHER nor RAGGED; spec_rank > 0).  The seed's valid bound -- the k-th largest group
+// maximum -- lets ~k ln(I / k) elements through before the threshold has risen to the row's k-th best; the r-th largest maximum, r << k, is
+// NOT a bound but on iid rows lies just below the k-th best (anncur_internal_scan_spec_rank picks r).  The row is scanned against it as against
+// any threshold and the guess is CHECKED: every element dropped lay below the speculative threshold or below a later, valid one (a compaction
+// sets the exact k-th kept key, which is at or above it), so the result is exact iff at least k candidates beat the speculative threshold --
+// i.e. iff a compaction has run (it saw > k of them) or the buffer holds >= k entries at the row's end.  Otherwise the wave scans the row
+// AGAIN from an empty buffer with the valid seed (rank k, speculation off): that pass is the kernel as it was.  A row that will fail is
+// mostly caught early: at the block boundary nearest a quarter of the row the staged vectors are drained, and with no compaction yet and
+// fewer than k / 8 candidates the wave restarts there (a descending row costs ~1.25 passes, not 2).  stats (optional, device): [0] += rows
+// that restarted, [1] += rows that started under a speculative threshold.
+// SPECULATE: the instantiation with the restart loop.  A launch with rank 0 takes the one without it, which is the kernel as it was: the loop, its
+// opaque lane index and the out-of-line seed select cost +0.5 % on the whole chip even when no row speculates.
+template <typename T, bool GATHER = false, bool BUF = true, bool RAGGED = false, int E = 2, bool SPECULATE = false>   // E: keys per lane of the final sort (k <= 64 E; E = 1 from the ragged entry only)
 __global__ __launch_bounds__(256) void rowwise_topk_wave_kernel(const T *__restrict__ A, int64_t Q, int64_t I_all, int64_t lda, uint32_t k,
 																 uint32_t trig, float *__restrict__ out_val, int32_t *__restrict__ out_idx,
-																 const ScanGather gt = ScanGather{}, const int32_t *__restrict__ row_len = nullptr) {
+																 const ScanGather gt = ScanGather{}, const int32_t *__restrict__ row_len = nullptr,
+																 uint32_t spec_rank = 0, uint32_t *__restrict__ stats = nullptr) {
+	constexpr bool SPEC = SPECULATE;
+	static_assert(!SPEC || (!GATHER && !RAGGED), "the speculative start is for the plain scan only");
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	// (the wave index through readfirstlane: the compiler then knows the row pointer is wave-uniform and keeps the stream's base address
 	//  in scalar registers -- without it every load of the stream carried 64-bit per-lane address arithmetic)
-	const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	int lane = lane_id();   // (not const: see scan_row)
+	const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	const int64_t q = (int64_t)blockIdx.x * 4 + wave;
 	if (q >= Q) return;
 	const int64_t I = RAGGED ? min((int64_t)max(__builtin_amdgcn_readfirstlane(row_len[q]), 0), I_all) : I_all;   // (a length outside 0..I_all is clamped: no read past the row)
@@ -320,21 +336,31 @@ __global__ __launch_bounds__(256) void rowwise_topk_wave_kernel(const T *__restr
 	const uintptr_t addr = reinterpret_cast<uintptr_t>(row);
 	int64_t head = (int64_t)(((16 - (addr & 15)) & 15) / sizeof(T));
 	if (head > I) head = I;
-	const int64_t nvec = (I - head) / VEC;
-	const int64_t tail0 = head + nvec * VEC;
+	int64_t nvec = (I - head) / VEC;   // (not const: see scan_row)
 	const u32x4 *vp = reinterpret_cast<const u32x4 *>(row + head);
-	const int64_t vlast = nvec > 0 ? nvec - 1 : 0;
-	const int64_t nsteps = (nvec + WAVE - 1) / WAVE;
 	// (BUF, round 4) the stream's loads as raw buffer loads: the row's vectors behind a resource in scalar registers, the lane's 16 bytes as
 	// a 32-bit offset, the step as an immediate and the block as a scalar offset -- no per-lane 64-bit address arithmetic (three to four
 	// VALU instructions per step of the pointer form: a fifth of the loop).  Rows under 2 GB (the launcher picks the pointer form otherwise).
-	const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4 *>(vp), 0, BUF ? (int)(nvec * 16) : 0, 0x00027000);
-	const uint32_t voff = (uint32_t)lane * 16u;
 
 	// the first WS_PF vectors of every lane: they seed the threshold AND are the first prefetch set of the stream
 	u32x4 pf[WS_PF];
 	uint32_t pm[GATHER ? WS_PF : 1];   // (GATHER) anchor mask of the prefetched vector; 0 for the clamped duplicates past the row
 	T *cqrow = GATHER ? reinterpret_cast<T *>(gt.cq) + q * gt.ldo : nullptr;
+	// (SPEC; all wave-uniform) seed_rank: which group maximum seeds the threshold -- spec_rank on the first pass, k on a restart; spec_cp: the
+	// block at whose start a speculative pass is checked early, -1 while the threshold in force is a valid one
+	uint32_t seed_rank = SPEC && spec_rank != 0u ? spec_rank : k;
+	int64_t spec_cp = -1;
+scan_row: __attribute__((unused));   // (SPEC: a failed speculation comes back here once, with seed_rank = k and everything below as on entry)
+	// (SPEC: the restart makes everything below the body of a loop, and hipcc then hoists what depends on the lane or the row length alone --
+	//  the first prefetch set's eight 64-bit addresses, the head's and the tail's, the seed select's LDS addresses -- out of it and keeps it in
+	//  registers for the whole row: 152 to 157 VGPRs where the kernel had 114 to 118, one wave per SIMD fewer.  So the lane index and the
+	//  vector count are made opaque once per pass, and the seed select is called out of line.)
+	if (SPEC) asm volatile("" : "+v"(lane), "+s"(nvec));
+	const int64_t tail0 = head + nvec * VEC;
+	const int64_t vlast = nvec > 0 ? nvec - 1 : 0;
+	const int64_t nsteps = (nvec + WAVE - 1) / WAVE;
+	const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4 *>(vp), 0, BUF ? (int)(nvec * 16) : 0, 0x00027000);
+	const uint32_t voff = (uint32_t)lane * 16u;
 #pragma unroll
 	for (int d = 0; d < WS_PF; ++d) {
 		const int64_t iv = (int64_t)d * WAVE + lane;
@@ -347,13 +373,22 @@ __global__ __launch_bounds__(256) void rowwise_topk_wave_kernel(const T *__restr
 		for (int d = 0; d < WS_PF; ++d) w.whi[d * WAVE + lane] = ScanPre<T>::group_max_key(pf[d]);
 		__builtin_amdgcn_wave_barrier();
 		uint32_t need;
-		const uint32_t kth = wsel_kth<false, HP>(w, w.whi, (uint32_t)(WS_PF * WAVE), k, need, w.whi, 0u);
+		uint32_t kth;
+		if constexpr (SPEC) {  // (out of line: inline, the select's per-lane LDS addresses are hoisted out of the restart loop like the ones above)
+			(void)need;
+			kth = wsel_kth_call<WS_CAP, HP>(w, (uint32_t)(WS_PF * WAVE), seed_rank);
+		} else kth = wsel_kth<false, HP>(w, w.whi, (uint32_t)(WS_PF * WAVE), k, need, w.whi, 0u);
 		// admit the bound itself: the threshold is the fp32 value just below it (the buffer is still empty).  If fewer than k
 		// maxima are finite the bound is -inf (or the NaN key 0): the threshold stays at -inf = "none yet".
 		if (kth > f32_sortable(-INFINITY)) {  // (a bound of -inf or below is no bound: stay unthresholded)
 			float t = f32_unsortable(kth - 1u);
 			if (fabsf(t) < 1.17549435e-38f) t = -1.17549435e-38f;  // bound = +-0 or a denormal: any negative normal admits it (and +0 == -0)
 			w.tau = t;
+			if (SPEC && seed_rank < k) {  // a guess, not a bound: checked at the quarter mark and at the row's end
+				spec_cp = ((nsteps / 4 + WS_PF / 2) / WS_PF) * WS_PF;
+				if (spec_cp < WS_PF) spec_cp = WS_PF;
+				if (stats != nullptr && lane == 0) atomicAdd(stats + 1, 1u);
+			}
 		}
 	}
 	{  // unaligned head (fewer than VEC elements): lowest indices first
@@ -455,8 +490,20 @@ __global__ __launch_bounds__(256) void rowwise_topk_wave_kernel(const T *__restr
 	// arithmetic and no clamp (the one-loop version spent ~130 instructions per 16-byte step, most of them 64-bit address and mask
 	// work for a case that arises in the last block only; that did not matter with 256 CUs on the stream, HBM-bound either way, but it
 	// caps what a PART of the chip can stream: 31 GB/s per CU -- see bench.py --scan-mode partition).
+	// (w.tau_hi is 0 from wsel_init until the first compaction sets it to a real number's key, never 0: "no compaction yet")
+#define SCAN_RESTART()                                                                                                          \
+	{                                                                                                                           \
+		if (stats != nullptr && lane == 0) atomicAdd(stats, 1u);                                                                \
+		w.cnt = 0; w.tau_hi = 0; w.tau_lo = 0; w.tau = -INFINITY;                                                               \
+		seed_rank = k; spec_cp = -1;                                                                                            \
+		goto scan_row;                                                                                                          \
+	}
 	int64_t s0 = 0;
 	for (; (s0 + 2 * WS_PF) * WAVE <= nvec; s0 += WS_PF) {
+		if (SPEC && s0 == spec_cp) {  // the quarter mark of a speculative pass: candidates so far = elements of the blocks before this one
+			if (scnt > 0u) SCAN_DRAIN()
+			if (w.tau_hi == 0u && w.cnt < (k >> 3)) SCAN_RESTART()
+		}
 		sp.set(w.tau);  // frozen for the block
 		const u32x4 *blk = vp + s0 * WAVE;  // (uniform)
 		const uint32_t *mblk = GATHER ? gt.vtab + s0 * WAVE : nullptr;
@@ -477,12 +524,15 @@ __global__ __launch_bounds__(256) void rowwise_topk_wave_kernel(const T *__restr
 		SCAN_STEP(0, false, false) SCAN_STEP(1, false, false) SCAN_STEP(2, false, false) SCAN_STEP(3, false, false) SCAN_STEP(4, false, false) SCAN_STEP(5, false, false) SCAN_STEP(6, false, false) SCAN_STEP(7, false, false)
 	}
 	if (scnt > 0u) SCAN_DRAIN()
-#undef SCAN_STEP
-#undef SCAN_DRAIN
 	{  // the tail (fewer than VEC elements), still in index order
 		const bool in = lane < I - tail0;
 		wsel_offer_inorder(w, in, in ? load_as_f32<T>(row + tail0 + lane) : 0.f, (uint32_t)(tail0 + lane));
 	}
+	// a speculative pass that never compacted holds exactly the row's numbers above its threshold: fewer than k of them = the guess was too high
+	if (SPEC && spec_cp >= 0 && w.tau_hi == 0u && w.cnt < k) SCAN_RESTART()
+#undef SCAN_RESTART
+#undef SCAN_STEP
+#undef SCAN_DRAIN
 	if (GATHER) {  // anchors among the tail elements (no vector covers them): looked up directly
 		for (int j = lane; j < gt.n_idx; j += WAVE) {
 			const int32_t c = gt.col_idx[j];
@@ -867,9 +917,45 @@ int anncur_internal_scan_rows_in_flight(int dtype) {
 	return v;
 }
 
+// The rank r of the group maximum the wave-per-row scan starts from speculatively (rowwise_topk_wave_kernel), 0 = start from the valid
+// bound.  On iid rows the number of seed elements (n_seed = WS_PF * 64 vectors: 4096 bf16 / 2048 fp32) above the row's true k-th best is
+// about Poisson(lambda), lambda = k n_seed / I, and the guess fails -- the row is scanned again -- about when r or more of the seed's group
+// maxima lie above it: r is the smallest rank >= 2 with P[Poisson(lambda) >= r] <= 1e-5 (16 at 100 000 x k = 100, bf16).  The tail prices a
+// restart: a row that fails at its end is read again by ONE wave while its workgroup's slot stays held, and a wave alone streams at 2.2 GB/s,
+// so a restart costs about a microsecond of the LAUNCH, not a row's share of it (measured: 3 restarts in 10 000 rows, the 1e-3 tail first
+// built, +1.0 % on the whole chip and half the gain on 128 CUs: DESIGN 9.1).  1e-5 keeps launches of up to 10 000 rows at a tenth of a restart.
+// Off where the guess buys nothing -- r > k / 2, rows shorter than four seed regions -- and with ANNCUR_SCAN_SPEC=0 in the environment (read
+// once: the A/B switch).  extern "C" only so that the host tests can call it; not part of the public header.
+extern "C" int anncur_internal_scan_spec_rank(int64_t I, int32_t k, int dtype) {
+	static const bool enabled = [] { const char *e = getenv("ANNCUR_SCAN_SPEC"); return !(e && e[0] == '0' && e[1] == '\0'); }();
+	if (!enabled || !dtype_ok(dtype) || k < 1) return 0;
+	const int64_t n_seed = (int64_t)WS_PF * WAVE * (dtype == ANNCUR_F32 ? VecOf<float>::N : VecOf<uint16_t>::N);
+	if (I < 4 * n_seed) return 0;
+	// the launch path asks once per call (co-scan chunks included) and nearly always for the shape it asked for last: remember that one
+	// (per thread: nothing to race on)
+	static thread_local struct { int64_t I; int32_t k; int dtype, rank; } last = {0, 0, 0, 0};
+	if (last.I == I && last.k == k && last.dtype == dtype) return last.rank;
+	const double lambda = (double)k * (double)n_seed / (double)I;
+	int found = 0;   // stays 0 for r > k / 2
+	// upper tail from its own terms (no 1 - cdf), in logarithms so that no lambda underflows: P[X >= r] = sum_{j >= r} exp(-lambda + j ln lambda - ln j!)
+	for (int r = 2; 2 * r <= k && !found; ++r) {
+		if ((double)r <= lambda) continue;   // (a tail that starts at or below the mean is about a half or more)
+		double tail = 0.0, t = exp(-lambda + (double)r * log(lambda) - lgamma((double)r + 1.0));
+		for (int j = r; t > tail * 1e-17 && t > 0.0; ++j) { tail += t; t *= lambda / (double)(j + 1); }
+		if (tail <= 1e-5) found = r;
+	}
+	last.I = I; last.k = k; last.dtype = dtype; last.rank = found;
+	return found;
+}
+
 // =================================================================== C ABI
 extern "C" int anncur_rowwise_topk(const void *A, int dtype, int64_t Q, int64_t I, int64_t lda, int32_t k,
 								   float *out_val, int32_t *out_idx, void *stream) {
+	return anncur_rowwise_topk_ex(A, dtype, Q, I, lda, k, out_val, out_idx, stream, -1, nullptr);
+}
+
+extern "C" int anncur_rowwise_topk_ex(const void *A, int dtype, int64_t Q, int64_t I, int64_t lda, int32_t k,
+									  float *out_val, int32_t *out_idx, void *stream, int spec_rank, uint32_t *stats) {
 	ANNCUR_REQUIRE(dtype_ok(dtype), ANNCUR_E_INVALID, "rowwise_topk: bad dtype %d", dtype);
 	ANNCUR_REQUIRE(Q >= 0 && I >= 1 && lda >= I, ANNCUR_E_INVALID, "rowwise_topk: bad shape Q=%lld I=%lld lda=%lld",
 				   (long long)Q, (long long)I, (long long)lda);
@@ -878,6 +964,7 @@ extern "C" int anncur_rowwise_topk(const void *A, int dtype, int64_t Q, int64_t 
 	ANNCUR_REQUIRE(I < (int64_t)0x7fffffff, ANNCUR_E_INVALID, "rowwise_topk: I too large for int32 indices");
 	ANNCUR_REQUIRE(A && out_val && out_idx, ANNCUR_E_INVALID, "rowwise_topk: null pointer");
 	ANNCUR_REQUIRE(((uintptr_t)A % dtype_size(dtype)) == 0, ANNCUR_E_INVALID, "rowwise_topk: misaligned A");
+	ANNCUR_REQUIRE(spec_rank >= -1 && spec_rank <= k, ANNCUR_E_INVALID, "rowwise_topk: spec_rank=%d outside -1 (auto), 0 (off), 1..k", spec_rank);
 	if (Q == 0) return ANNCUR_OK;
 	hipStream_t st = (hipStream_t)stream;
 	const int kc = kmax_class(k);
@@ -907,13 +994,12 @@ extern "C" int anncur_rowwise_topk(const void *A, int dtype, int64_t Q, int64_t 
 		const unsigned grid = (unsigned)ceil_div64(Q, 4);
 		uint32_t trig = ws_trigger((uint32_t)k);
 		bool buf = I * (int64_t)dtype_size(dtype) < ((int64_t)1 << 31);   // the stream's loads through a buffer resource (32-bit offsets)
-		if (dtype == ANNCUR_F32) {
-			if (buf) hipLaunchKernelGGL((rowwise_topk_wave_kernel<float, false, true>), dim3(grid), dim3(256), lds, st, (const float *)A, Q, I, lda, (uint32_t)k, trig, out_val, out_idx);
-			else hipLaunchKernelGGL((rowwise_topk_wave_kernel<float, false, false>), dim3(grid), dim3(256), lds, st, (const float *)A, Q, I, lda, (uint32_t)k, trig, out_val, out_idx);
-		} else {
-			if (buf) hipLaunchKernelGGL((rowwise_topk_wave_kernel<uint16_t, false, true>), dim3(grid), dim3(256), lds, st, (const uint16_t *)A, Q, I, lda, (uint32_t)k, trig, out_val, out_idx);
-			else hipLaunchKernelGGL((rowwise_topk_wave_kernel<uint16_t, false, false>), dim3(grid), dim3(256), lds, st, (const uint16_t *)A, Q, I, lda, (uint32_t)k, trig, out_val, out_idx);
-		}
+		const uint32_t sr = (uint32_t)(spec_rank < 0 ? anncur_internal_scan_spec_rank(I, k, dtype) : spec_rank);   // (a forced rank of k is the valid seed)
+#define LAUNCH_WAVE(T, B) do { if (sr != 0u && sr < (uint32_t)k) hipLaunchKernelGGL((rowwise_topk_wave_kernel<T, false, B, false, 2, true>), dim3(grid), dim3(256), lds, st, (const T *)A, Q, I, lda, (uint32_t)k, trig, out_val, out_idx, ScanGather{}, (const int32_t *)nullptr, sr, stats); \
+	else hipLaunchKernelGGL((rowwise_topk_wave_kernel<T, false, B>), dim3(grid), dim3(256), lds, st, (const T *)A, Q, I, lda, (uint32_t)k, trig, out_val, out_idx); } while (0)
+		if (dtype == ANNCUR_F32) { if (buf) LAUNCH_WAVE(float, true); else LAUNCH_WAVE(float, false); }
+		else { if (buf) LAUNCH_WAVE(uint16_t, true); else LAUNCH_WAVE(uint16_t, false); }
+#undef LAUNCH_WAVE
 		ANNCUR_LAUNCH_OK();
 		return ANNCUR_OK;
 	}

@@ -314,6 +314,29 @@ __device__ __forceinline__ void wsel_compact_call(WaveSel &w, uint32_t k, uint32
 	__builtin_amdgcn_wave_barrier();
 }
 
+// The k-th largest of whi[0..n), out of line in the same way (the key comes back through the first histogram word).
+template <int CAP, int PASSES>
+__device__ __attribute__((noinline)) void wsel_kth_outlined(uint32_t lds_off, uint32_t n, uint32_t k) {
+	WaveSel w;
+	w.whi = (uint32_t *)(__attribute__((address_space(3))) uint32_t *)(uintptr_t)lds_off;
+	w.wlo = w.whi + CAP;
+	w.sort_buf = reinterpret_cast<uint2 *>(w.wlo + CAP);
+	w.hist = reinterpret_cast<uint32_t *>(w.sort_buf + 128);
+	w.cnt = n; w.tau_hi = 0; w.tau_lo = 0; w.tau = 0.f;
+	uint32_t need;
+	const uint32_t kth = wsel_kth<false, PASSES>(w, w.whi, n, k, need, w.whi, 0u);
+	if (lane_id() == 0) w.hist[0] = kth;
+	__builtin_amdgcn_wave_barrier();
+}
+template <int CAP, int PASSES>
+__device__ __forceinline__ uint32_t wsel_kth_call(WaveSel &w, uint32_t n, uint32_t k) {
+	wsel_kth_outlined<CAP, PASSES>((uint32_t)(size_t)(__attribute__((address_space(3))) uint32_t *)w.whi, n, k);
+	__builtin_amdgcn_wave_barrier();
+	const uint32_t kth = __builtin_amdgcn_readfirstlane(w.hist[0]);
+	__builtin_amdgcn_wave_barrier();
+	return kth;
+}
+
 // Bitonic sort (descending) of 128 64-bit keys held as (hi, lo) pairs, two per lane: element i = e*64 + lane.
 __device__ __forceinline__ void wave_sort128_desc(uint32_t (&hi)[2], uint32_t (&lo)[2]) {
 	const int lane = lane_id();

@@ -336,10 +336,13 @@ def eval_fused(Xp, Etp, A_exact, n_items, k, return_fallbacks=False, hint=None):
 
 # ------------------------------------------------------------------ a7/a8
 @_on_device
-def rowwise_topk(A, k, out=None):
+def rowwise_topk(A, k, out=None, _spec=None, _stats=None):
 	"""Exact torch.topk(A, k, dim=1) on the device: (values f32 [Q,k], indices int32 [Q,k]),
 	sorted descending, ties -> smaller index.  out: (values, indices) contiguous [Q, k] tensors to write into (row slices of a larger
-	result, when a matrix is scanned in several launches)."""
+	result, when a matrix is scanned in several launches).
+	_spec / _stats (tests and measurements; anncur_rowwise_topk_ex): rank of the wave-per-row scan's speculative start -- None = the
+	library's choice, 0 = off, 1..k forced -- and a zeroed int32 [2] device tensor the launch adds (rows scanned twice, rows started from a
+	guess) to.  The result does not depend on either."""
 	_dev(A)
 	A = _rowmajor(A)
 	Q, I = A.shape
@@ -350,7 +353,15 @@ def rowwise_topk(A, k, out=None):
 	else:
 		val = torch.empty((Q, k), dtype=torch.float32, device=A.device)
 		idx = torch.empty((Q, k), dtype=torch.int32, device=A.device)
-	check(_lib.load().anncur_rowwise_topk(_p(A), _dt(A), Q, I, _ld(A), k, _p(val), _p(idx), _stream()), "rowwise_topk")
+	if _spec is None and _stats is None:
+		check(_lib.load().anncur_rowwise_topk(_p(A), _dt(A), Q, I, _ld(A), k, _p(val), _p(idx), _stream()), "rowwise_topk")
+		return TopK(val, idx)
+	if _stats is not None:
+		_dev(_stats)
+		if _stats.dtype != torch.int32 or _stats.numel() < 2 or not _stats.is_contiguous():
+			raise ValueError("rowwise_topk: _stats must be a contiguous int32 tensor of two entries")
+	check(_lib.load().anncur_rowwise_topk_ex(_p(A), _dt(A), Q, I, _ld(A), k, _p(val), _p(idx), _stream(), -1 if _spec is None else int(_spec),
+											 _p(_stats) if _stats is not None else None), "rowwise_topk")
 	return TopK(val, idx)
 
 
